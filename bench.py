@@ -9,10 +9,14 @@ pan theta U(0,pi/2)), already resident in HBM.  With N > 1 GPUs every rank rende
 (weak scaling, no data-path traffic) and the stereo bus is summed onto rank 0 with one RCCL reduce per
 batch (the path's only exchange step), overlapped with the next batch's kernels.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--voices V] [--frames F]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--voices V] [--frames F] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (--prewarm-ms of load, then W steps), times exactly K steps
+and prints the headline: `metric`, `value` (Msamples/s of the K timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the workload's `config`.  `--dump-outputs DIR` writes the stereo bus of the last timed step (what
+`ShardedRenderer.render` hands its caller) as DIR/bus.npy, float32 (rank 0); the inputs depend only on the arguments.
+`--full` adds everything else the benchmark measures or checks:
   * `roofline`: the dominant kernel of the timed steps against the ceiling that bounds it (HIP events around every
     launch, on the launch stream) -- the f64 vector issue rate for the fused voice kernels (their HBM view nested
     under `hbm`), HBM bandwidth for the per-node kernels;
@@ -21,7 +25,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with
   * `sustained`: the same steps repeated for >= 2 s of wall time (clocks settled, visible to a busy sampler);
   * `configs`: BASELINE.json's other single-GPU configurations (C3, C5), each with its own roofline and error;
   * `cpu_baseline`: the CPU oracle, structured like the reference (per-channel butter + sosfilt per block), timed on
-    a bounded sample.
+    a bounded sample;
+  * `alt_schedule`, `fused_schedule_at_other_batch_sizes`, `latency_mode`: the other engine schedule, other batch lengths,
+    one block per request.
 """
 import argparse
 import json
@@ -54,6 +60,21 @@ VALU_BOUND = ('fused_voice_bus', 'fused_cascade_bus')      # kernels whose ceili
 
 synth_params = cfg.c2_params
 build_graph = cfg.c2_graph
+DUMP_LIMIT_BYTES = 60 << 20     # --dump-outputs stays under 64 MB: a larger bus is sampled by rows
+
+
+def dump_outputs(out_dir: str, bus: np.ndarray) -> None:
+    """the last timed step's stereo bus as out_dir/bus.npy (float32).  Past DUMP_LIMIT_BYTES: a fixed sample of its rows
+    (numpy default_rng(0), in row order) as bus.npy, and their row indices, as float64, as bus_rows.npy"""
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    bus = np.ascontiguousarray(bus, dtype=np.float32)
+    if bus.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (bus.itemsize * bus.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(bus.shape[0], size=keep, replace=False))
+        np.save(out / 'bus_rows.npy', rows.astype(np.float64))
+        bus = bus[rows]
+    np.save(out / 'bus.npy', bus)
 
 
 def steady_applies(p, lo, hi, first_frame, last_frame, N, ctx=100):
@@ -465,8 +486,15 @@ def main():
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-configs', action='store_true', help='skip the C3 / C5 legs')
     ap.add_argument('--materialised', action='store_true', help='headline = one kernel per node (no fusion)')
-    ap.add_argument('--single-mode', action='store_true', help='only the headline measurement (profiling runs)')
+    ap.add_argument('--single-mode', action='store_true', help='with --full: only the headline measurement (profiling runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s stereo bus to DIR/bus.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='beyond the headline: roofline and per-kernel table, the sustained leg, the other schedule, other batch '
+                         'lengths, latency mode, the C3 / C5 / modulated / voice-program configurations, the error against the '
+                         'CPU oracle and the CPU baselines (the --no-* and --single-mode options narrow this)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     # The contract is ONE JSON line on stdout.  RCCL prints its version banner to stdout (fd 1) when the first
     # communicator is created, so everything but the final line is sent to stderr at the fd level.
@@ -496,13 +524,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(fuse: bool, steps: int, warmup: int, sustained_s: float = 0.0) -> dict:
+    def measure(fuse: bool, steps: int, warmup: int, sustained_s: float = 0.0, dump: bool = False) -> dict:
         """W untimed + exactly `steps` timed batches of this rank's 1024-voice graph (+ bus reduce); then, optionally,
-        the same steps for `sustained_s` more seconds"""
+        the same steps for `sustained_s` more seconds.  `dump`: a host copy of the last timed batch's bus"""
         # fused schedule: one ~200-us launch per step -- ONE HIP event in front of the first timed launch and one behind the last
         # (nothing between the launches: the stream runs as it does untimed, so avg_launch_ms is the per-step GPU time, gaps
         # included, and cannot exceed ms_per_step); node-materialised: every launch bracketed
-        timer = None if args.no_kernel_timing else (KernelTimer(region=True) if fuse else KernelTimer(sample_every=1))
+        timer = None if args.no_kernel_timing or not args.full else (KernelTimer(region=True) if fuse else KernelTimer(sample_every=1))
         renderer = parallel.ShardedRenderer(lambda lo, hi: build_graph(params, lo, hi), V * world, bus_channels=2,
                                             rate=RATE, timer=timer, fuse=fuse)
         assert (renderer.lo, renderer.hi) == (rank * V, (rank + 1) * V)
@@ -559,6 +587,8 @@ def main():
             dt = float(t.item())
         samples = V * world * N * K * steps
         res = {'value': samples / dt / 1e6, 'ms_per_step': dt / steps * 1e3, 'last_bus': bus, 'last_position': last_position}
+        if dump and rank == 0:
+            res['dump'] = bus.cpu().numpy()                  # (before any later leg renders on this renderer)
         if timer:
             summ = timer.summary()
             closed = fuse and steady_applies(params, rank * V, (rank + 1) * V, args.position,
@@ -615,14 +645,16 @@ def main():
                                         f'({wrap * N * K / RATE / 3600:.1f} h of audio)'}
         return res
 
+    # a plain run stops at the headline; --full goes on with the legs below (--single-mode: none of them)
+    single_mode = args.single_mode or not args.full
     main_mode = measure(fuse=not args.materialised, steps=args.steps, warmup=args.warmup,
-                        sustained_s=0.0 if args.single_mode else args.sustained_s)
+                        sustained_s=0.0 if single_mode else args.sustained_s, dump=bool(args.dump_outputs))
     other = None
-    if not args.single_mode:
+    if not single_mode:
         other = measure(fuse=args.materialised, steps=max(3, args.steps // 2), warmup=min(2, args.warmup))
 
     by_batch = None
-    if world == 1 and not args.single_mode and not args.materialised:
+    if world == 1 and not single_mode and not args.materialised:
         # the same schedule at other batch lengths, clocks already settled.  K = 256 is SURVEY.md 8d's "throughput mode": a leg of its
         # own with a roofline entry (region-timed like the headline)
         from signals_amd.engine import BatchRenderer
@@ -682,7 +714,7 @@ def main():
             by_batch[str(k)] = entry
 
     latency = None
-    if world == 1 and not args.single_mode:
+    if world == 1 and not single_mode:
         # latency mode: ONE 256-frame block per request, as a real-time sink would pull it
         from signals_amd.chain import BlockLoc, Shape
         from signals_amd.chain.driver import BlockDriver
@@ -709,7 +741,7 @@ def main():
             latency[name] = {'us_per_block': us, 'Msamples_per_s': V * N / us, 'x_realtime': (N / RATE * 1e6) / us}
 
     configs = None
-    if world == 1 and not args.single_mode and not args.no_configs and not args.no_cpu_baseline:
+    if world == 1 and not single_mode and not args.no_configs and not args.no_cpu_baseline:
         configs = {name: run_config(name) for name in ('C3', 'C5')}
         configs['C2_modulated'] = run_modulated()
         configs['voice_programs'] = run_programs()
@@ -752,7 +784,7 @@ def main():
             line['fused_schedule_at_other_batch_sizes'] = by_batch
         if latency is not None:
             line['latency_mode'] = latency
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # BASELINE.json's second metric, on the output of the LAST TIMED batch of each schedule: blocks 0..7, the middle
             # one and the last one against float32(oracle float64); the batch starts (warmup + steps - 1) batches into the stream
             errors = {}
@@ -777,6 +809,8 @@ def main():
                 line['cpu_baseline_sharded'] = cpu_baseline_sharded(params, V, N, workers)
         if configs:
             line['configs'] = configs
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, main_mode['dump'])
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + '\n').encode())
     if dist.is_initialized():

@@ -34,7 +34,8 @@ def _free_port():
 
 
 def _worker(rank, world, port, total, frames, out):
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    # gloo on a GPU box too: two RCCL ranks cannot share its one GPU
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), SIG_DIST_BACKEND='gloo')
     from signals_amd.parallel import init_process_group
     r, w = init_process_group()
     assert (r, w) == (rank, world) and dist.get_backend() == 'gloo'

@@ -8,7 +8,7 @@ root=$PWD
 out=$root/gpurun_out/prof$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $root/bench.py --no-cpu-baseline --single-mode"
+BENCH="python3 $root/bench.py --full --no-cpu-baseline --single-mode"
 modes="fused materialised"
 [ "${2:-}" = configs ] && modes=""          # tools/profile_round.sh <tag> configs: only the passes over tools/measure_configs.py
 for mode in $modes; do
