@@ -73,8 +73,8 @@ __device__ __forceinline__ void restart(double na1, double na2, int e, double s0
     z1 -= fma(m.c, s0, m.d * s1);
 }
 
-// The envelope stage a voice is in at time q, as a line in t.  Not inlined: it runs five times per voice over a whole stream,
-// and inlined into every row of the checked row groups it set the register budget of the whole kernel.
+// The envelope stage a voice is in at time q, as a line in t.  Not inlined: it runs a handful of times per voice over a
+// whole stream, and inlined into every row of the checked row groups it set the register budget of the whole kernel.
 struct StageLine { double end, slope, l; };
 __device__ __attribute__((noinline)) StageLine stage_line(const sig_env::AdsrRows& env, int v, double q) {
     const sig_env::Segment s = sig_env::segment_at(sig_env::load_voice(env, v), q);
@@ -187,7 +187,7 @@ __device__ __forceinline__ void cascade_wave(const CascadeArgs& a, const sig_env
 
     // One group of R output rows starting at frame n.  SNAP: the states are copied before row `snap_at` of the group (the
     // block's row N - ctx).  CHECKED: some voice's envelope stage ends inside the group, so every row re-derives the
-    // stages that have ended (rare: five boundaries per voice).
+    // stages that have ended (rare: five boundaries per voice, one or two re-derivations each).
     auto group = [&](int64_t n, int snap_at, auto snap_tag, auto checked_tag) {
         constexpr bool SNAP = decltype(snap_tag)::value, CHECKED = decltype(checked_tag)::value;
         ensure(n, R);

@@ -52,10 +52,13 @@ __device__ __forceinline__ double level(const Voice& p, double t) {
 
 // Piecewise-linear tracking for kernels that walk time forwards and only need the envelope to rounding (the fused
 // bus kernel, not the ADSR node itself): within one stage  level(t) = L0 + slope * (t - t0)  exactly up to rounding,
-// so a voice carries (t0, L0, slope, end) and re-derives them from the definition only when t reaches `end` -- at
-// most five times per voice over a whole stream.  The stage boundaries are those of the definition (gate_on,
-// + attack, + decay, gate_off, + release); a boundary computed here may sit one ulp of t away from where the
-// definition's comparisons switch, which moves the level by slope * ulp(t) < 1e-9.
+// so a voice carries (t0, L0, slope, end) and re-derives them from the definition only when t reaches `end`.  The
+// stage boundaries are those of the definition (gate_on, + attack, + decay, gate_off, + release), but a boundary
+// computed here may sit an ulp of t away from where the definition's comparisons switch.  When it sits at or before
+// t -- a boundary that lands on a sample row, as round-number and whole-frame parameters make it do, while
+// (t - on) - attack still rounds below zero -- the stage is right for t itself but ends there: `end` is then kept at
+// t, so that the next row re-derives.  So a voice re-derives once or twice per boundary: a handful of times over a
+// whole stream.
 struct Segment { double t0, l0, slope, end; };
 
 __device__ __forceinline__ Segment segment_at(const Voice& p, double t) {
@@ -74,7 +77,8 @@ __device__ __forceinline__ Segment segment_at(const Voice& p, double t) {
         if (p.rel_bias - w * p.ir > 0.0) { s.slope = -(p.hold_off * p.ir); s.end = p.off + 1.0 / p.ir; }
         else { s.slope = 0.0; s.end = inf; }
     }
-    if (!(s.end > t)) s.end = inf;                      // NaN parameters or a boundary at t itself: never re-enter for this t
+    if (!(s.end > t)) s.end = (s.end == s.end) ? t : inf;   // a boundary at or before t: the next row re-derives;
+                                                         // NaN parameters: never
     return s;
 }
 

@@ -542,7 +542,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                                 bool stale = false;
 #pragma unroll
                                 for (int i = 0; i < VPT; ++i) stale |= !(qr < seg[i].end);
-                                if (__any(stale)) seed_envelope(qr);           // a stage ended: at most five times per voice and stream
+                                if (__any(stale)) seed_envelope(qr);           // a stage ended: a handful of times per voice and stream
 #pragma unroll
                                 for (int i = 0; i < VPT; ++i) acc[r][i] = fma(seg[i].slope, qr - seg[i].t0, seg[i].l0);
                             }
