@@ -122,6 +122,16 @@ int sig_band_coldstart(int type, int32_t rate, int64_t position,
                        const void* in, int64_t in_ld, int64_t in_history,
                        void* out, int64_t out_ld, int32_t dtype,
                        int32_t* status, void* stream);
+/* sig_band_coldstart with per-block bands (a swept BandPass / BandStop): param_blocks is 1 (the rows hold for
+ * every block) or nblocks (row b of low / high, each (nblocks, V)|(nblocks, 1) contiguous, is block b's band).
+ * A bad band in block b (low >= high, or outside (0, rate/2)) is NaN for that voice in that block only and sets
+ * SIG_STATUS_BAD_CUTOFF. */
+int sig_band_coldstart_blocks(int type, int32_t rate, int64_t position,
+                              int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                              const double* low, int32_t low_stride, const double* high, int32_t high_stride,
+                              int32_t param_blocks, const void* in, int64_t in_ld, int64_t in_history,
+                              void* out, int64_t out_ld, int32_t dtype,
+                              int32_t* status, void* stream);
 
 /* One operand of an element-wise effect.  row_stride / col_stride are in elements; 0 broadcasts
  * that axis (numpy broadcasting of (1,V), (N,1), (1,1) replies). */
@@ -473,6 +483,9 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *   MUL    acc = temp[a] * acc            MIX  acc = m L + (1 - m) R, m = params[b], (L, R) = c ? (acc, temp[a]) : (temp[a], acc)
  *   SAVE   temp[a] = acc                  LOAD acc = temp[a]
  *   ADSR   acc = envelope level at n / rate (the six rows `adsr`)     NOISE acc = White sample (noise_seed[a], frame n, channel)
+ *   BAND   acc = band filter over slots a, a + 1 applied to acc    (BandPass / BandStop: cutoff[a] = low rows, cutoff[a + 1] = high
+ *          rows, filter_type both SIG_FILT_BANDPASS or both SIG_FILT_BANDSTOP, one filter_level; a run of band slots pairs up from
+ *          its first slot; designed per block like butter(2, [low, high]) and run as its two sections)
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -493,7 +506,7 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * sig_fused_voice_bus_workspace(voices, rows, bus_channels) bytes.  f64 arithmetic, no float32 rounding between the nodes.
  * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF. */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
-       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10 };
+       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
 typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;

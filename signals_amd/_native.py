@@ -35,7 +35,7 @@ EXPORTS = ('sig_abi_version', 'sig_osc_bank', 'sig_osc_bank_mod', 'sig_biquad_co
            'sig_fused_osc_biquad_fm', 'sig_fused_voice_bus_fm', 'sig_control_program',
            'sig_voice_program', 'sig_voice_program_set_tuning', 'sig_voice_program_geometry', 'sig_voice_program_args_size',
            'sig_voice_program_attach', 'sig_voice_program_detach_all', 'sig_voice_program_use_attached',
-           'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound')
+           'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound', 'sig_band_coldstart_blocks')
 
 
 class NativeError(RuntimeError):
@@ -59,7 +59,9 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
-VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10}
+VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
+          'Band': 11}
+VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 
 
@@ -106,6 +108,9 @@ def lib() -> ctypes.CDLL:
         L.sig_biquad_coldstart.restype = ctypes.c_int
         L.sig_biquad_coldstart.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, i32,
                                            vp, i64, i64, vp, i64, i32, vp, vp]
+        L.sig_band_coldstart_blocks.restype = ctypes.c_int
+        L.sig_band_coldstart_blocks.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, dp, i32, i32,
+                                                vp, i64, i64, vp, i64, i32, vp, vp]
         L.sig_elementwise.restype = ctypes.c_int
         L.sig_elementwise.argtypes = [ctypes.c_int, i64, i32, ctypes.POINTER(Operand), ctypes.POINTER(Operand),
                                       ctypes.POINTER(Operand), vp, i64, i32, vp]
@@ -1036,6 +1041,41 @@ def band_coldstart(btype: str, rate: int, position: int, block_frames: int, nblo
                                     in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
                                     status.data_ptr() if status is not None else None, _stream(out)),
            'sig_band_coldstart')
+    return out
+
+
+def band_coldstart_blocks(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
+                          low: torch.Tensor, high: torch.Tensor, buf: torch.Tensor, history: int, out: torch.Tensor,
+                          status: torch.Tensor | None = None) -> torch.Tensor:
+    """`band_coldstart` with per-block bands: low / high f64 (1|nblocks, V|1), row b (of a multi-row edge) is block b's.
+    A single-row edge beside a multi-row one is repeated for every block."""
+    _gpu(low, high, buf, out, status)
+    _audio(buf, 'band in')
+    _audio(out, 'band out')
+    rows, voices = out.shape
+    if rows != block_frames * nblocks or buf.shape[0] != history + rows or buf.shape[1] != voices or buf.dtype != out.dtype:
+        raise NativeError(f'band shapes: in {tuple(buf.shape)} history {history} out {tuple(out.shape)}')
+    blocks = max(low.shape[0], high.shape[0])
+    ptrs = []
+    for row, name in ((low, 'low'), (high, 'high')):
+        if row.dtype != torch.float64 or row.dim() != 2 or not row.is_contiguous():
+            raise NativeError(f'{name} must be a contiguous float64 2-D tensor')
+        if row.shape[0] not in (1, nblocks):
+            raise NativeError(f'{name} has {row.shape[0]} rows for {nblocks} blocks')
+        if row.shape[1] != voices and voices != 1:
+            raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
+        if row.shape[1] not in (1, voices):
+            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
+        if row.shape[0] != blocks:
+            row = row.expand(blocks, row.shape[1]).contiguous()
+        ptrs.extend((row.data_ptr(), 0 if row.shape[1] == 1 else 1))
+        ptrs.append(row)                                                       # (kept alive until the call returns)
+    in_ptr = buf.data_ptr() + history * buf.stride(0) * buf.element_size()
+    _check(lib().sig_band_coldstart_blocks(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
+                                           ptrs[0], ptrs[1], ptrs[3], ptrs[4], blocks, in_ptr, buf.stride(0), history,
+                                           out.data_ptr(), out.stride(0), _dt(out),
+                                           status.data_ptr() if status is not None else None, _stream(out)),
+           'sig_band_coldstart_blocks')
     return out
 
 

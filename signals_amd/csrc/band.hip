@@ -5,6 +5,8 @@
 // with the same [<=100 context | block] cold start as LowPass/HighPass.  Same mapping as biquad.hip's plain
 // kernel (wave = 64*VPT voices of one block, serial over rows, register ring of row loads); 4 f64 state
 // registers and 10 coefficients per voice.  HBM-bound: 8 B per voice-sample, 18 f64 ops.
+// `param_blocks` > 1: row b of `low` / `high` holds block b's band (a swept band: an LFO on either edge, read at
+// the block's position like biquad.hip's cutoff rows); the design stays once per wave, a wave being one block.
 #include "sig_biquad.h"
 
 namespace {
@@ -31,7 +33,7 @@ constexpr int kRing = 8;
 template <typename T, int VPT>
 __global__ __launch_bounds__(256) void band_coldstart_kernel(
     int type, double rate, int64_t position, int N, int K, int ctx, int voices,
-    const double* __restrict__ low, int ls, const double* __restrict__ high, int hs,
+    const double* __restrict__ low, int ls, const double* __restrict__ high, int hs, int param_blocks,
     const T* __restrict__ in, int64_t in_ld, T* __restrict__ out, int64_t out_ld,
     int voice_tiles, int* __restrict__ status)
 {
@@ -50,10 +52,12 @@ __global__ __launch_bounds__(256) void band_coldstart_kernel(
     Biquad q1[VPT], q2[VPT];
     double s10[VPT], s11[VPT], s20[VPT], s21[VPT];
     bool ok = true;
+    const int64_t lrow = (param_blocks > 1) ? b * (int64_t)(ls ? voices : 1) : 0;   // block b's row of each edge
+    const int64_t hrow = (param_blocks > 1) ? b * (int64_t)(hs ? voices : 1) : 0;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
         const int v = (vc + i < voices) ? vc + i : vc;
-        ok &= design_band2(type, low[(int64_t)v * ls], high[(int64_t)v * hs], rate, q1[i], q2[i]);
+        ok &= design_band2(type, low[lrow + (int64_t)v * ls], high[hrow + (int64_t)v * hs], rate, q1[i], q2[i]);
         s10[i] = s11[i] = s20[i] = s21[i] = 0.0;
     }
     if (!ok && live && status) atomicOr(status, SIG_STATUS_BAD_CUTOFF);
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(256) void band_coldstart_kernel(
 
 template <typename T>
 int launch_band(int type, int32_t rate, int64_t position, int32_t N, int32_t K, int32_t ctx, int32_t voices,
-                const double* low, int ls, const double* high, int hs,
+                const double* low, int ls, const double* high, int hs, int param_blocks,
                 const T* in, int64_t in_ld, T* out, int64_t out_ld, int32_t* status, hipStream_t stream)
 {
     const bool vec4 = (voices % 4 == 0) && (in_ld % 4 == 0) && (out_ld % 4 == 0) &&
@@ -108,11 +112,33 @@ int launch_band(int type, int32_t rate, int64_t position, int32_t N, int32_t K, 
     if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
     if (vec4)
         band_coldstart_kernel<T, 4><<<(unsigned)nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
-                                                                         low, ls, high, hs, in, in_ld, out, out_ld, voice_tiles, status);
+                                                                         low, ls, high, hs, param_blocks, in, in_ld, out, out_ld, voice_tiles, status);
     else
         band_coldstart_kernel<T, 1><<<(unsigned)nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
-                                                                         low, ls, high, hs, in, in_ld, out, out_ld, voice_tiles, status);
+                                                                         low, ls, high, hs, param_blocks, in, in_ld, out, out_ld, voice_tiles, status);
     return sig_launch_status();
+}
+
+int run_band(int type, int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+             const double* low, int32_t low_stride, const double* high, int32_t high_stride, int32_t param_blocks,
+             const void* in, int64_t in_ld, int64_t in_history, void* out, int64_t out_ld, int32_t dtype,
+             int32_t* status, void* stream)
+{
+    SIG_CHECK_ARG(type == SIG_FILT_BANDPASS || type == SIG_FILT_BANDSTOP);
+    SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
+    SIG_CHECK_ARG(low && high && in && out && in_ld >= voices && out_ld >= voices);
+    SIG_CHECK_ARG((low_stride | 1) == 1 && (high_stride | 1) == 1);
+    SIG_CHECK_ARG(param_blocks == 1 || param_blocks == nblocks);
+    SIG_CHECK_ARG(in_history >= (position < context ? position : context));
+    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == SIG_F32)
+        return launch_band<float>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
+                                  param_blocks, static_cast<const float*>(in), in_ld, static_cast<float*>(out), out_ld, status, s);
+    if (dtype == SIG_F64)
+        return launch_band<double>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
+                                   param_blocks, static_cast<const double*>(in), in_ld, static_cast<double*>(out), out_ld, status, s);
+    return (int)hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -124,18 +150,17 @@ extern "C" int sig_band_coldstart(int type, int32_t rate, int64_t position,
                                   void* out, int64_t out_ld, int32_t dtype,
                                   int32_t* status, void* stream)
 {
-    SIG_CHECK_ARG(type == SIG_FILT_BANDPASS || type == SIG_FILT_BANDSTOP);
-    SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
-    SIG_CHECK_ARG(low && high && in && out && in_ld >= voices && out_ld >= voices);
-    SIG_CHECK_ARG((low_stride | 1) == 1 && (high_stride | 1) == 1);
-    SIG_CHECK_ARG(in_history >= (position < context ? position : context));
-    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == SIG_F32)
-        return launch_band<float>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
-                                  static_cast<const float*>(in), in_ld, static_cast<float*>(out), out_ld, status, s);
-    if (dtype == SIG_F64)
-        return launch_band<double>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
-                                   static_cast<const double*>(in), in_ld, static_cast<double*>(out), out_ld, status, s);
-    return (int)hipErrorInvalidValue;
+    return run_band(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride, 1,
+                    in, in_ld, in_history, out, out_ld, dtype, status, stream);
+}
+
+extern "C" int sig_band_coldstart_blocks(int type, int32_t rate, int64_t position,
+                                         int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                                         const double* low, int32_t low_stride, const double* high, int32_t high_stride,
+                                         int32_t param_blocks, const void* in, int64_t in_ld, int64_t in_history,
+                                         void* out, int64_t out_ld, int32_t dtype,
+                                         int32_t* status, void* stream)
+{
+    return run_band(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride, param_blocks,
+                    in, in_ld, in_history, out, out_ld, dtype, status, stream);
 }

@@ -43,39 +43,49 @@ __device__ __forceinline__ Cx cx_div(Cx a, Cx b) {
     const double d = b.re * b.re + b.im * b.im;
     return {(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
 }
+template <bool HYPOT = true>
 __device__ __forceinline__ Cx cx_sqrt(Cx z) {
-    const double m = hypot(z.re, z.im);
+    const double m = HYPOT ? hypot(z.re, z.im) : sqrt(z.re * z.re + z.im * z.im);
     if (m == 0.0) return {0.0, 0.0};
     if (z.re >= 0.0) { const double t = sqrt((m + z.re) * 0.5); return {t, z.im / (2.0 * t)}; }
     const double t = sqrt((m - z.re) * 0.5);
     return {fabs(z.im) / (2.0 * t), copysign(t, z.im)};
 }
 
+struct LibmTan { __device__ double operator()(double x) const { return tan(x); } };
+
 // type: SIG_FILT_BANDPASS / SIG_FILT_BANDSTOP.  Returns false where scipy raises (Wn outside (0,1) after the
 // clip, or lo >= hi); the coefficients are then NaN.
-__device__ __forceinline__ bool design_band2(int type, double lo_hz, double hi_hz, double rate, Biquad& first, Biquad& last) {
+// `tan_half_pi`: tan(x) for x = pi Wn / 2 in [0, pi/2]; HYPOT false: |z| as sqrt(re^2 + im^2) and the pole pairing by
+// squared magnitudes -- the same pairing (both poles lie inside the unit circle, so |1 - |P|| = 1 - |P|), no overflow
+// guard needed for Wn < 1, and no libm hypot in a kernel that designs per block (voice_program.hip).
+template <bool HYPOT = true, typename Tan = LibmTan>
+__device__ __forceinline__ bool design_band2(int type, double lo_hz, double hi_hz, double rate, Biquad& first, Biquad& last,
+                                             double* beta_first = nullptr, double* beta_last = nullptr, Tan tan_half_pi = Tan{}) {
     auto scaled = [&](double hz) { double w = hz / (rate * 0.5); return (w < 0.0) ? 0.0 : ((w > 1.0) ? 1.0 : w); };
     const double wl = scaled(lo_hz), wh = scaled(hi_hz);
     const bool bad = !(wl > 0.0 && wl < 1.0 && wh > 0.0 && wh < 1.0 && wl < wh);   // NaN fails every comparison: bad
-    const double w1 = 4.0 * tan(kPi * wl / 2.0), w2 = 4.0 * tan(kPi * wh / 2.0);
+    const double w1 = 4.0 * tan_half_pi(kPi * wl / 2.0), w2 = 4.0 * tan_half_pi(kPi * wh / 2.0);
     const double bw = w2 - w1, wo2 = w1 * w2;
     const Cx p = {-0.70710678118654757, 0.70710678118654757};
     Cx c;                                                   // centre: p bw/2 (bp) or (bw/2)/p (bs)
     if (type == SIG_FILT_BANDPASS) c = {p.re * bw * 0.5, p.im * bw * 0.5};
     else c = cx_div({bw * 0.5, 0.0}, p);
     Cx c2 = cx_mul(c, c);
-    const Cx s = cx_sqrt({c2.re - wo2, c2.im});
+    const Cx s = cx_sqrt<HYPOT>({c2.re - wo2, c2.im});
     const Cx qa = {c.re + s.re, c.im + s.im}, qb = {c.re - s.re, c.im - s.im};
     auto bilinear = [](Cx q) { Cx r = cx_div({4.0 + q.re, q.im}, {4.0 - q.re, -q.im}); if (r.im < 0.0) r.im = -r.im; return r; };
     const Cx Pa = bilinear(qa), Pb = bilinear(qb);
     const double den = ((4.0 - qa.re) * (4.0 - qa.re) + qa.im * qa.im) * ((4.0 - qb.re) * (4.0 - qb.re) + qb.im * qb.im);
-    const bool a_worst = fabs(1.0 - hypot(Pa.re, Pa.im)) <= fabs(1.0 - hypot(Pb.re, Pb.im));
+    const bool a_worst = HYPOT ? fabs(1.0 - hypot(Pa.re, Pa.im)) <= fabs(1.0 - hypot(Pb.re, Pb.im))
+                               : Pa.re * Pa.re + Pa.im * Pa.im >= Pb.re * Pb.re + Pb.im * Pb.im;
     const Cx worst = a_worst ? Pa : Pb, other = a_worst ? Pb : Pa;
     double kz, bl1, bl2, bf1, bf2;                          // b = [1, b1, b2] per section (before the gain)
     if (type == SIG_FILT_BANDPASS) {
         kz = bw * bw * 16.0 / den;
         // nearest real zeros to the worst pole, one at a time, from {+1, +1, -1, -1}
-        const double dp = hypot(worst.re - 1.0, worst.im), dm = hypot(worst.re + 1.0, worst.im);
+        const double dp = HYPOT ? hypot(worst.re - 1.0, worst.im) : (worst.re - 1.0) * (worst.re - 1.0) + worst.im * worst.im;
+        const double dm = HYPOT ? hypot(worst.re + 1.0, worst.im) : (worst.re + 1.0) * (worst.re + 1.0) + worst.im * worst.im;
         // first pick: nearer of +1 / -1; second pick: nearer of what is left (the same value again is still available)
         const double z1 = (dp <= dm) ? 1.0 : -1.0;
         const double z2 = z1;                               // two copies of each zero exist, so the second pick repeats
@@ -89,6 +99,9 @@ __device__ __forceinline__ bool design_band2(int type, double lo_hz, double hi_h
     }
     first = {kz, kz * bf1, kz * bf2, -2.0 * other.re, other.re * other.re + other.im * other.im};
     last = {1.0, bl1, bl2, -2.0 * worst.re, worst.re * worst.re + worst.im * worst.im};
+    // every section is g [1, beta, 1] / [1, a1, a2] (bp: beta = +-2, bs: beta = -2 Re z0): the b0-normalised middle taps
+    if (beta_first) *beta_first = bad ? __builtin_nan("") : bf1;
+    if (beta_last) *beta_last = bad ? __builtin_nan("") : bl1;
     if (bad) {
         const double nan = __builtin_nan("");
         first = {nan, nan, nan, nan, nan};

@@ -107,13 +107,18 @@ __device__ __forceinline__ uint64_t vp_mix64(uint64_t z) {                     /
 // temporaries set the register budget of the whole kernel (+110 VGPRs, measured), and the argument here is pi Wn / 2 with
 // Wn in (0, 1): tan = sin / cos from the odd polynomial of sig_osc.h on [0, pi/2], cos(x) = sin(pi/2 - x) with pi/2 as hi + lo.
 // Coefficients within 1e-15 (relative) of the libm form.
+struct VpTan {                                              // tan(x), x in [0, pi/2]
+    __device__ __forceinline__ double operator()(double x) const {
+        const double xc = (1.5707963267948966 - x) + 6.123233995736766e-17;
+        return sig_osc::sin_poly(x) / sig_osc::sin_poly(xc);
+    }
+};
 __device__ __forceinline__ bool vp_design(int type, double cutoff, double rate, Biquad& q) {
     double wn = cutoff / (rate * 0.5);                      // scaled_crit /= rate / 2  (fx.py:99-101)
     wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
     const bool bad = !(wn > 0.0 && wn < 1.0);               // scipy raises (NaN too)
     const double x = sig_biquad::kPi * wn / 2.0;
-    const double xc = (1.5707963267948966 - x) + 6.123233995736766e-17;
-    const double k = sig_osc::sin_poly(x) / sig_osc::sin_poly(xc);
+    const double k = VpTan{}(x);
     const double k2 = k * k;
     const double nrm = 1.0 / (1.0 + sig_biquad::kSqrt2 * k + k2);
     q.b0 = (type == SIG_FILT_LOWPASS) ? k2 * nrm : nrm;
@@ -154,7 +159,9 @@ template <bool SMALL> struct VpLimits {
 };
 
 // C == 0: store (float) acc to a.out; C > 0: C bus channels into a.partials.  EXT: Amp, ADSR and White instructions.
-template <int VPT, bool SMALL, int C>
+// BAND: the Band instruction (band filters' per-voice middle taps and their design; a variant of its own, so that programs
+// without one keep the registers they had -- the band state and its inlined design cost the SMALL file ~200 B of scratch per lane)
+template <int VPT, bool SMALL, int C, bool BAND>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave)
 {
     constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
@@ -182,9 +189,22 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     double acc[RG][VPT], T[NT > 0 ? NT : 1][RG][VPT], pr[NP][VPT], ohz[NO][VPT], oph[NO][VPT];
     double z0[NF][VPT], z1[NF][VPT], w0[NF][VPT], w1[NF][VPT], na1[NF][VPT], na2[NF][VPT], fb0[NF][VPT], xa1[NF][VPT], xa2[NF][VPT];
     double s2[NF];
+    // band filters (Band): two consecutive slots f, f + 1 -- the sections of butter(2, [low, high]) -- whose middle taps vary per
+    // voice and block: beta of the first section (current and next chains) in bq / xbq[f / 2]; the second's is -beta (bp) or beta
+    // (bs); the band's gain is the second slot's fb0.  A run of band slots pairs up from its start (the host emits them that way,
+    // sig_voice_program checks it)
+    constexpr int NB = NF / 2 > 0 ? NF / 2 : 1;
+    double bq[NB][VPT], xbq[NB][VPT];
+    bool bfirst[NF];
     double wt[CC][VPT];
 #pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) bq[b][i] = xbq[b][i] = 0.0;
+#pragma unroll
     for (int f = 0; f < NF; ++f) {
+        const bool band = f < a.n_filters && (a.ftype[f] == SIG_FILT_BANDPASS || a.ftype[f] == SIG_FILT_BANDSTOP);
+        bfirst[f] = BAND && band && f + 1 < NF && !(f > 0 && bfirst[f > 0 ? f - 1 : 0]);
         s2[f] = (f < a.n_filters && a.ftype[f] == SIG_FILT_HIGHPASS) ? -2.0 : 2.0;
 #pragma unroll
         for (int i = 0; i < VPT; ++i) { z0[f][i] = z1[f][i] = w0[f][i] = w1[f][i] = 0.0; na1[f][i] = na2[f][i] = fb0[f][i] = xa1[f][i] = xa2[f][i] = 0.0; }
@@ -233,8 +253,25 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     auto design = [&](int64_t cri, int min_level, auto next_tag) {
         constexpr bool NEXT = decltype(next_tag)::value;
 #pragma unroll
-        for (int f = 0; f < NF; ++f)
-            if (f < a.n_filters && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1)) {
+        for (int f = 0; f < NF; ++f) {
+            const int g = (f + 1 < NF) ? f + 1 : f;                            // the second slot of a band filter at f
+            if (BAND && f < a.n_filters && a.flevel[f] >= min_level && bfirst[f] && (!designed || a.cutoff[f].rows > 1 || a.cutoff[g].rows > 1)) {
+                bool ok = true;
+#pragma unroll
+                for (int i = 0; i < VPT; ++i) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    Biquad q1, q2;
+                    double beta = 0.0;
+                    ok &= sig_biquad::design_band2<false>(a.ftype[f], row_at(a.cutoff[f], cri, voice(i)), row_at(a.cutoff[g], cri, voice(i)),
+                                                          a.rate, q1, q2, &beta, nullptr, VpTan{}) || !(v0 + i < a.voices);
+                    if (NEXT) { xa1[f][i] = -q1.a1; xa2[f][i] = -q1.a2; xa1[g][i] = -q2.a1; xa2[g][i] = -q2.a2; xbq[f / 2][i] = beta; }
+                    else { na1[f][i] = -q1.a1; na2[f][i] = -q1.a2; fb0[f][i] = 1.0; na1[g][i] = -q2.a1; na2[g][i] = -q2.a2; fb0[g][i] = q1.b0; bq[f / 2][i] = beta; }
+                    if (!NEXT && !designed) { xa1[f][i] = -q1.a1; xa2[f][i] = -q1.a2; xa1[g][i] = -q2.a1; xa2[g][i] = -q2.a2; xbq[f / 2][i] = beta; }
+                }
+                if (!ok && a.status) atomicOr(a.status, SIG_STATUS_BAD_CUTOFF);
+            }
+            const bool single = f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
+            if (single && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1)) {
                 bool ok = true;
 #pragma unroll
                 for (int i = 0; i < VPT; ++i) {
@@ -247,6 +284,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                 }
                 if (!ok && a.status) atomicOr(a.status, SIG_STATUS_BAD_CUTOFF);
             }
+        }
     };
     auto start_next = [&](int64_t cri, int min_level) {                        // the next block's chains (of filters at that level of a cascade or deeper): zero state, its design
         design(cri, min_level, std::true_type{});
@@ -371,6 +409,37 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     int64_t qbase = 0;
     bool q_valid = false;
     sig_bus::FoldedGroup<CC> folded(tile, lane, dstp);                         // whole groups of the bus sink: sums folded across lanes in registers
+    // one biquad section of filter slot F over the group's R rows, in place on the accumulator: DF2T of [1, beta, 1] / [1, a1, a2]
+    // (b0-normalised; `scale`: times the slot's b0 after).  beta(i) / xbeta(i): the current and next chains' middle taps
+    auto section = [&](auto I, int warm_r, auto rows_tag, auto beta, auto xbeta, bool scale) {
+        constexpr int F = decltype(I)::value;
+        constexpr int R = decltype(rows_tag)::value;
+        if (warm_r < R) {                                                      // wave-uniform: the next block's chain, on the same input rows
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r >= warm_r) {                                             // (wave-uniform too: a group may straddle the first warm row)
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) {
+                        const double x = acc[r][i];
+                        const double yw = x + w0[F][i];
+                        w0[F][i] = fma(xa1[F][i], yw, fma(xbeta(i), x, w1[F][i]));
+                        w1[F][i] = fma(xa2[F][i], yw, x);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double x = acc[r][i];
+                const double y = x + z0[F][i];
+                z0[F][i] = fma(na1[F][i], y, fma(beta(i), x, z1[F][i]));
+                z1[F][i] = fma(na2[F][i], y, x);
+                acc[r][i] = scale ? fb0[F][i] * y : y;
+            }
+        }
+    };
     auto group = [&](int64_t n, int warm_r, bool out, auto rows_tag) {        // warm_r: the first row of the group that also advances the next chains (R: none)
         constexpr int R = decltype(rows_tag)::value;
         if (!q_valid || n < qbase || n + R > qbase + SIG_WAVE) {                // n / rate (IEEE divide) for 64 rows at a time, one per lane
@@ -387,7 +456,10 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
         constexpr bool kStaticExt = [] {
             constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
             bool ext = false;
-            for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) ext |= (c[k] & 31u) >= (uint32_t)SIG_VP_AMP;
+            for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) {
+                const uint32_t op = c[k] & 31u;
+                ext |= op == (uint32_t)SIG_VP_AMP || op == (uint32_t)SIG_VP_ADSR || op == (uint32_t)SIG_VP_NOISE;
+            }
             return ext;
         }();
         static_assert(EXT || !kStaticExt, "the program uses Amp / ADSR / White: build with -DSIG_VP_S_EXT=1");
@@ -442,30 +514,35 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                 case SIG_VP_FILTER:
                     with_index<NF>(ia, [&](auto I) {
                         constexpr int F = decltype(I)::value;
-                        if (warm_r < R) {                                      // wave-uniform: the next block's chain, on the same input rows
+                        section(I, warm_r, rows_tag, [&](int) { return s2[F]; }, [&](int) { return s2[F]; }, true);
+                    });
+                    break;
+                case SIG_VP_BAND:                                              // two sections in series, the band's gain on the second's output
+                    with_index<NF>(ia, [&](auto I) {
+                        constexpr int F = decltype(I)::value;
+                        if constexpr (BAND && F + 1 < NF) {
+                            constexpr int G = F + 1;
+                            const double sg = (a.ftype[F] == SIG_FILT_BANDPASS) ? -1.0 : 1.0;     // the second section's beta
+                            if (warm_r < R) {                                  // the next block's band: BOTH next chains in series on the input
 #pragma unroll
-                            for (int r = 0; r < R; ++r) {
-                                if (r >= warm_r) {                             // (wave-uniform too: a group may straddle the first warm row)
+                                for (int r = 0; r < R; ++r) {
+                                    if (r >= warm_r) {
 #pragma unroll
-                                    for (int i = 0; i < VPT; ++i) {
-                                        const double x = acc[r][i];
-                                        const double yw = x + w0[F][i];
-                                        w0[F][i] = fma(xa1[F][i], yw, fma(s2[F], x, w1[F][i]));
-                                        w1[F][i] = fma(xa2[F][i], yw, x);
+                                        for (int i = 0; i < VPT; ++i) {
+                                            const double x = acc[r][i];
+                                            const double y1 = x + w0[F][i];
+                                            w0[F][i] = fma(xa1[F][i], y1, fma(xbq[F / 2][i], x, w1[F][i]));
+                                            w1[F][i] = fma(xa2[F][i], y1, x);
+                                            const double y2 = y1 + w0[G][i];
+                                            w0[G][i] = fma(xa1[G][i], y2, fma(sg * xbq[F / 2][i], y1, w1[G][i]));
+                                            w1[G][i] = fma(xa2[G][i], y2, y1);
+                                        }
                                     }
                                 }
                             }
-                        }
-#pragma unroll
-                        for (int i = 0; i < VPT; ++i) {
-#pragma unroll
-                            for (int r = 0; r < R; ++r) {
-                                const double x = acc[r][i];
-                                const double y = x + z0[F][i];                 // DF2T of [1, s2, 1] / [1, a1, a2]
-                                z0[F][i] = fma(na1[F][i], y, fma(s2[F], x, z1[F][i]));
-                                z1[F][i] = fma(na2[F][i], y, x);
-                                acc[r][i] = fb0[F][i] * y;
-                            }
+                            section(I, R, rows_tag, [&](int i) { return bq[F / 2][i]; }, [&](int i) { return bq[F / 2][i]; }, false);
+                            section(std::integral_constant<int, G>{}, R, rows_tag, [&](int i) { return sg * bq[F / 2][i]; },
+                                    [&](int i) { return sg * bq[F / 2][i]; }, true);
                         }
                     });
                     break;
@@ -638,14 +715,14 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C>
+template <int VPT, bool SMALL, int C, bool BAND>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a)
 {
     constexpr bool BUS = C > 0;
     __shared__ double lds[BUS ? 4 : 1][BUS ? sig_bus::kPairs * kTileStride : 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C>(a, lds[BUS ? wave : 0], lane, wave);
+    vp_wave<VPT, SMALL, C, BAND>(a, lds[BUS ? wave : 0], lane, wave);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -657,7 +734,16 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a)
 // constant -- the dispatch loop unrolls and every switch folds.  Attached to the library with sig_voice_program_attach.
 }  // namespace
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
-void sig_vp_specialised(VpArgs a) { vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C>(a); }
+void sig_vp_specialised(VpArgs a)
+{
+    constexpr bool kBand = [] {
+        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
+        bool band = false;
+        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) band |= (c[k] & 31u) == (uint32_t)SIG_VP_BAND;
+        return band;
+    }();
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand>(a);
+}
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
 extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 {
@@ -666,10 +752,10 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
     for (unsigned k = 0; k < sizeof(code) / sizeof(code[0]); ++k) out[4 + k] = code[k];
 }
 #else
-template <int VPT, bool SMALL, int C>
+template <int VPT, bool SMALL, int C, bool BAND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C>(a);
+    vp_kernel_body<VPT, SMALL, C, BAND>(a);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -685,7 +771,7 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_NOISE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15))
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_BAND && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)x.c << 16);
     }
@@ -702,7 +788,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -731,15 +817,21 @@ void vp_geometry(const VpArgs& a, int store_aligned, bool four, int& vpt, int& s
     }
 }
 
-template <int VPT, bool SMALL>
+template <int VPT, bool SMALL, bool BAND>
 int vp_launch_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
     switch (C) {
-        case 0: voice_program_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a); break;
-        case 1: voice_program_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a); break;
-        case 2: voice_program_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a); break;
+        case 0: voice_program_kernel<VPT, SMALL, 0, BAND><<<nwg, 256, 0, s>>>(a); break;
+        case 1: voice_program_kernel<VPT, SMALL, 1, BAND><<<nwg, 256, 0, s>>>(a); break;
+        case 2: voice_program_kernel<VPT, SMALL, 2, BAND><<<nwg, 256, 0, s>>>(a); break;
         default: return (int)hipErrorInvalidValue;
     }
     return sig_launch_status();
+}
+
+template <int VPT>
+int vp_launch_file(const VpArgs& a, bool small_file, bool band, int C, unsigned nwg, hipStream_t s) {
+    if (band) return small_file ? vp_launch_sink<VPT, true, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, true>(a, C, nwg, s);
+    return small_file ? vp_launch_sink<VPT, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, false>(a, C, nwg, s);
 }
 
 }  // namespace
@@ -841,15 +933,16 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false};
     bool has_adsr = false;
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_NOISE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_BAND && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15);
         switch (x.op) {
             case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
+            case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
             case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
             case SIG_VP_MIX: SIG_CHECK_ARG(x.a < P.n_temps && x.b < P.n_params); break;
@@ -858,6 +951,7 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         }
         if (x.op == SIG_VP_AMP || x.op == SIG_VP_ADSR || x.op == SIG_VP_NOISE) need.ext = true;
         if (x.op == SIG_VP_ADSR) has_adsr = true;
+        if (x.op == SIG_VP_BAND) need.band = true;
     }
     SIG_CHECK_ARG(vp_encode(P, a.code));
     a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
@@ -870,8 +964,29 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         SIG_CHECK_ARG(rows_ok(P.params[k], false));
         a.params[k] = Rows{P.params[k].ptr, P.params[k].col_stride, P.params[k].rows};
     }
+    // filter slots: a Filter instruction runs a LowPass / HighPass slot; a Band instruction at slot f runs the pair f, f + 1 (its
+    // low and high rows), of one band type and one level, which the kernel finds by pairing every run of band slots from its start
+    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second
+    for (int k = 0; k < P.n_ins; ++k) {
+        const sig_vp_ins& x = P.ins[k];
+        if (x.op == SIG_VP_FILTER) {
+            SIG_CHECK_ARG(role[x.a] == 0 || role[x.a] == 1);
+            role[x.a] = 1;
+        } else if (x.op == SIG_VP_BAND) {
+            SIG_CHECK_ARG((role[x.a] == 0 || role[x.a] == 2) && (role[x.a + 1] == 0 || role[x.a + 1] == 3));
+            role[x.a] = 2; role[x.a + 1] = 3;
+        }
+    }
+    for (int k = 0, run = 0; k < P.n_filters; ++k) {
+        const bool band = P.filter_type[k] == SIG_FILT_BANDPASS || P.filter_type[k] == SIG_FILT_BANDSTOP;
+        run = band ? run + 1 : 0;
+        if (role[k] == 1) SIG_CHECK_ARG(P.filter_type[k] == SIG_FILT_LOWPASS || P.filter_type[k] == SIG_FILT_HIGHPASS);
+        else if (role[k] == 2) SIG_CHECK_ARG(band && run % 2 == 1 && P.filter_type[k + 1] == P.filter_type[k] &&
+                                             P.filter_level[k + 1] == P.filter_level[k]);
+        else if (role[k] == 3) SIG_CHECK_ARG(band && run % 2 == 0);
+    }
     for (int k = 0; k < P.n_filters; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && (P.filter_type[k] == SIG_FILT_LOWPASS || P.filter_type[k] == SIG_FILT_HIGHPASS));
+        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_BANDSTOP);
         a.cutoff[k] = Rows{P.cutoff[k].ptr, P.cutoff[k].col_stride, P.cutoff[k].rows};
         a.ftype[k] = P.filter_type[k];
         SIG_CHECK_ARG(P.filter_level[k] >= 1 && P.filter_level[k] <= P.depth);
@@ -911,10 +1026,8 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         err = (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = small_file ? vp_launch_sink<2, true>(a, bus_channels, (unsigned)nwg, s)
-                                   : vp_launch_sink<2, false>(a, bus_channels, (unsigned)nwg, s);
-    else err = small_file ? vp_launch_sink<1, true>(a, bus_channels, (unsigned)nwg, s)
-                          : vp_launch_sink<1, false>(a, bus_channels, (unsigned)nwg, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, small_file, need.band, bus_channels, (unsigned)nwg, s);
+    else err = vp_launch_file<1>(a, small_file, need.band, bus_channels, (unsigned)nwg, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);

@@ -32,8 +32,8 @@ Node classes without a kernel schedule (plugins, including ones written against 
 answer numpy arrays) are pulled block by block through their own `respond()` and laid out as a batch
 buffer; everything downstream of them still runs one launch per node.
 
-Graphs that do not fit (a filter inside a control path, per-block ADSR / band-filter parameters,
-cascaded filters with N <= 100) raise `NotBatchable`; callers fall back to the eager path
+Graphs that do not fit (a filter inside a control path, per-block ADSR parameters, cascaded filters with
+N <= 100 that the voice program does not cover) raise `NotBatchable`; callers fall back to the eager path
 (`BlockDriver` does so by itself).
 """
 from __future__ import annotations
@@ -1088,22 +1088,28 @@ class _Batch:
         o = self.owner
         N, K, pos = self.N, self.K, self.pos
         band = isinstance(node, fx.DoubleCritFilter)
-        cutoff, window, c0 = self._filter_window(node, channels, self._control_const(node.low, 'low') if band else None)
+        cutoff, window, c0 = self._filter_window(node, channels, self._control(node.low, 'low') if band else None)
         result = torch.empty((rows, channels), dtype=AUDIO_DTYPE, device=window.device)
         main = result[hist:]
         btype = str(node.type())
         status = o._status_word(node)
         if band:
-            high = self._control_const(node.high, 'high')
+            high = self._control(node.high, 'high')
             if high.shape[1] < channels:
                 raise IndexError(f'index {high.shape[1]} is out of bounds for axis 1 with size {high.shape[1]}')
             high = high[:, :channels]
             if not high.is_contiguous():
                 high = high.contiguous()
-            o._launch(f'band_coldstart[{btype}]',
-                      lambda: _native.band_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, high, window, c0, main,
-                                                     status=status),
-                      units=N * K * channels)
+            if cutoff.shape[0] == 1 and high.shape[0] == 1:
+                o._launch(f'band_coldstart[{btype}]',
+                          lambda: _native.band_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, high, window, c0, main,
+                                                         status=status),
+                          units=N * K * channels)
+            else:                                                              # a swept band: one design per block
+                o._launch(f'band_coldstart[{btype},blocks]',
+                          lambda: _native.band_coldstart_blocks(btype, self.rate, pos, N, K, CONTEXT, cutoff, high, window, c0,
+                                                                main, status=status),
+                          units=N * K * channels)
         else:
             o._launch(f'biquad_coldstart[{btype}{",env" if envelope else ""}]',
                       lambda: _native.biquad_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, window, c0, main,
@@ -1652,7 +1658,7 @@ class _ProgramRows:
 
 
 class _VoiceProgram:
-    """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass,
+    """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
     Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
@@ -1660,14 +1666,15 @@ class _VoiceProgram:
     per-block rows (`_ProgramRows`).  The block history stays implicit: the launch re-walks the blocks in
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
-    KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White)
+    KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
         self.code: list = []
         self.oscs: list = []                     # (hertz control index, phase control index | None)
         self.params: list = []                   # control index per parameter register
-        self.filters: list = []                  # (cutoff control index, type, level, node)
+        self.filters: list = []                  # (cutoff control index, type, level, node); a band filter: two slots, low then high
+        self.bands: list = []                    # the band filter nodes
         self.controls: list = []                 # (port | None, constant tensor | None, filters between the node and the sink)
         self.adsr = None
         self.seeds: list = []
@@ -1806,6 +1813,18 @@ class _VoiceProgram:
                 raise _NoProgram('more filters than the machine has slots')
             self.filters.append((self._control(n.cutoff, below), str(n.type()), depth, n))
             self.code.append(('Filter', 0, len(self.filters) - 1, 0, 0))
+        elif isinstance(n, fx.DoubleCritFilter):
+            src = n.input.sig
+            if src is None or not src.get_state().enabled:
+                raise _NoProgram('filter without an input')
+            depth = self._emit(src, below + 1) + 1
+            if len(self.filters) + 2 > _native.VP_MAX_FILTERS:
+                raise _NoProgram('more filters than the machine has slots')
+            btype = str(n.type())                                              # ONE cached node: both slots at its level
+            self.filters.append((self._control(n.low, below), btype, depth, n))
+            self.filters.append((self._control(n.high, below), btype, depth, n))
+            self.code.append(('Band', 0, len(self.filters) - 2, 0, 0))
+            self.bands.append(n)
         else:
             raise _NoProgram(f'no voice-program instruction for {n.cls_name()}')
         self.depth_of[n] = depth
@@ -1936,20 +1955,26 @@ class _VoiceProgram:
 
     def worthwhile(self) -> bool:
         """Does the interpreted launch beat one kernel per node?  Measured (tools/time_voice_program.py, 1024 voices): programs
-        that fit the interpreter's SMALL register file -- two filters, three oscillators, four parameter registers, one
+        that fit the interpreter's SMALL register file -- two filter slots, three oscillators, four parameter registers, one
         temporary, no Amp / ADSR / White -- run at two waves per SIMD, 0.36-0.8 T voice-samples/s against 0.2-0.26 T per node;
         the full register file runs at one wave per SIMD and loses (0.14 T for three filters in series; f64 pow dominates an
         Amp either way).  Blocks shorter than the filter context have no per-node schedule at all (the alternative is the eager
-        pull path, ~150 us per block)."""
+        pull path, ~150 us per block).
+        Band filters (two slots each): a swept one (an LFO on `low` / `high`) designs per block either way and takes the program
+        under the same rule (tools/time_band.py); graphs whose bands all hold still keep the per-node schedule
+        they had before the program knew band filters, unless that schedule cannot batch them (short blocks behind a filter)."""
+        b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
-        if self.batch.owner.specialise is True:         # ('background': the interpreter renders meanwhile, so its policy decides)
+        if b.owner.specialise is True:                  # ('background': the interpreter renders meanwhile, so its policy decides)
             # a kernel built for this program has no interpreter to pay for: three filters in series 0.54 T against 0.26 per node,
             # an Amp behind a filter level with it (f64 pow either way)
             from . import specialise
             if specialise.hipcc() is not None:
                 return True
-        return small_file or (self.depth > 0 and self.batch.N < CONTEXT)
+        if self.bands and all(_ctl_const(n.low) and _ctl_const(n.high) for n in self.bands):
+            return b.N <= CONTEXT and any(not _is_pure(n.input.sig, b._pure) for _, _, _, n in self.filters)
+        return small_file or (self.depth > 0 and b.N < CONTEXT)
 
 
 _KNOWN_TYPES = tuple(t for types, _ in _Batch._SCHEDULES for t in (types if isinstance(types, tuple) else (types,)))
