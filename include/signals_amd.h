@@ -293,8 +293,23 @@ int sig_advance_position(int64_t* position_dev, int64_t delta, void* stream);
  * for v < outs[k].cols.  `position` may lie before `min_position` (even be negative): blocks whose frame position + b * step is below
  * min_position are evaluated AT min_position (the virtual blocks in front of short blocks read their controls at max(p - context, 0);
  * what feeds the last filter of a short block read them at an earlier block's position, never before the stream's second block).  A register index of -1 reads 0.  Same expressions as sig_osc_bank (f64 store) and sig_elementwise,
- * so the same bits as the node-by-node evaluation. */
-enum { SIG_CTL_ROW = 0, SIG_CTL_OSC = 1, SIG_CTL_GAIN = 2, SIG_CTL_MIX = 3, SIG_CTL_RINGMOD = 4, SIG_CTL_AMP = 5 };
+ * so the same bits as the node-by-node evaluation.
+ *
+ * Two more ops run only through sig_control_program_windowed (the same arguments; sig_control_program keeps its kernel, and a
+ * program holding one of them must not be given to it):
+ *  - SIG_CTL_NOISE: White at block rate, `row` = the seed (a uint64 in the pointer field), column v = channel v: the same hash
+ *    and scaling as sig_white_noise.
+ *  - SIG_CTL_FILTER: a LowPass / HighPass read at one frame (fx.py:85-106 with forward_with_context): kind = SIG_FILT_LOWPASS |
+ *    SIG_FILT_HIGHPASS, a = its input register, b = its cutoff register (block rate), `row` = an int32 status word (or NULL)
+ *    that collects SIG_STATUS_BAD_CUTOFF.  The instructions that feed `a` are WINDOW-RATE (`reserved` = 1; they form the
+ *    contiguous run right in front of the filter and feed nothing else): for the block evaluated at frame p they run for the
+ *    h = min(100, p) history rows p - h + j, every result rounded to float32 when h > 1 (a reply of more than one row is
+ *    float32 audio), and once more at p in float64; a cold-started Butterworth biquad (sig_biquad.h, transposed direct form
+ *    II) steps over the h + 1 rows and its last output is the filter's register.  Window-rate operands other than window-rate
+ *    registers must be block-invariant (ROW).  A one-column filter spreads its rows over the workgroup's threads (thread j
+ *    evaluates row j); a wider one walks them per column. */
+enum { SIG_CTL_ROW = 0, SIG_CTL_OSC = 1, SIG_CTL_GAIN = 2, SIG_CTL_MIX = 3, SIG_CTL_RINGMOD = 4, SIG_CTL_AMP = 5,
+       SIG_CTL_NOISE = 6, SIG_CTL_FILTER = 7 };
 enum { SIG_CTL_MAX_REGS = 48, SIG_CTL_MAX_INS = 48 };
 typedef struct {
     int32_t op;              /* SIG_CTL_* */
@@ -303,8 +318,8 @@ typedef struct {
     int32_t dst;             /* result register */
     int32_t stride, rows;    /* ROW: a (rows, cols) float64 array, rows 1 | nblocks, rows contiguous, element v * stride (cols 1: stride 0) */
     int32_t cols;            /* EVERY instruction: columns of its result (1: evaluated once per block; the broadcast of its operands' widths otherwise) */
-    int32_t reserved;
-    const double* row;
+    int32_t reserved;        /* 1: a window-rate instruction (in front of a SIG_CTL_FILTER); 0 otherwise */
+    const double* row;       /* ROW: the rows; NOISE: the seed; FILTER: the status word */
 } sig_ctl_ins;
 typedef struct { int32_t reg; int32_t cols; double* out; double* front; } sig_ctl_out;   /* out: (nblocks, cols) float64, contiguous; front: (1, cols) or NULL */
 /* front_position >= 0: the program is evaluated once more, at that frame position, into the outputs' `front` rows (the
@@ -312,9 +327,15 @@ typedef struct { int32_t reg; int32_t cols; double* out; double* front; } sig_ct
 int sig_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position,
                         int64_t min_position,
                         const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream);
+/* sig_control_program for programs with SIG_CTL_NOISE / SIG_CTL_FILTER instructions (a kernel variant of its own, so the
+ * programs without them keep their registers) */
+int sig_control_program_windowed(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position,
+                                 int64_t min_position,
+                                 const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream);
 
 /* SPECIALISED control programs: signals_amd/csrc/control_program.hip built as a gfx950 code object for one program STRUCTURE
- * (macros SIG_CTL_STATIC_INS = {{op, kind, a, b, c, dst, wide}, ...} in evaluation order and SIG_CTL_STATIC_OUTS = {{reg, wide},
+ * (macros SIG_CTL_STATIC_INS = {{op, kind, a, b, c, dst, wide}, ...} in evaluation order -- wide: bit 0 = more than one
+ * column, bit 1 = window-rate and SIG_CTL_STATIC_OUTS = {{reg, wide},
  * ...}; `hipcc --genco`, signals_amd/specialise.py): the registers are VGPRs instead of an LDS file behind an interpretive loop.
  * `description` = [n_ins, n_outs, the seven words per instruction, the two per output]; the image must describe itself the same
  * way (its sig_ctl_specialised_info kernel) or hipErrorInvalidImage.  A set-up call (allocates, launches, synchronises); the

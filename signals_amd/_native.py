@@ -35,7 +35,8 @@ EXPORTS = ('sig_abi_version', 'sig_osc_bank', 'sig_osc_bank_mod', 'sig_biquad_co
            'sig_fused_osc_biquad_fm', 'sig_fused_voice_bus_fm', 'sig_control_program',
            'sig_voice_program', 'sig_voice_program_set_tuning', 'sig_voice_program_geometry', 'sig_voice_program_args_size',
            'sig_voice_program_attach', 'sig_voice_program_detach_all', 'sig_voice_program_use_attached',
-           'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound', 'sig_band_coldstart_blocks')
+           'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound', 'sig_band_coldstart_blocks',
+           'sig_control_program_windowed')
 
 
 class NativeError(RuntimeError):
@@ -54,7 +55,8 @@ class CtlOut(ctypes.Structure):
     _fields_ = [('reg', ctypes.c_int32), ('cols', ctypes.c_int32), ('out', ctypes.c_void_p), ('front', ctypes.c_void_p)]
 
 
-CTL_OPS = {'Row': 0, 'Osc': 1, 'Gain': 2, 'Mix': 3, 'RingMod': 4, 'Amp': 5}
+CTL_OPS = {'Row': 0, 'Osc': 1, 'Gain': 2, 'Mix': 3, 'RingMod': 4, 'Amp': 5, 'Noise': 6, 'Filter': 7}
+CTL_WINDOWED_OPS = (6, 7)      # run only through sig_control_program_windowed
 CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 
@@ -190,6 +192,8 @@ def lib() -> ctypes.CDLL:
                                              dp, i32, i32, dp, dp, i32, i32, dp, dp, i32, i32, dp, i32, i32, dp, i64, i32, vp, vp, i64, vp, vp]
         L.sig_control_program.restype = ctypes.c_int
         L.sig_control_program.argtypes = [i32, i64, i32, i32, i32, i64, i64, vp, i32, vp, i32, vp]
+        L.sig_control_program_windowed.restype = ctypes.c_int
+        L.sig_control_program_windowed.argtypes = L.sig_control_program.argtypes
         L.sig_control_program_attach.restype = ctypes.c_int
         L.sig_control_program_attach.argtypes = [ctypes.POINTER(i32), i32, ctypes.c_char_p, ctypes.POINTER(i32)]
         L.sig_control_program_attached.restype = ctypes.c_int
@@ -889,21 +893,22 @@ def runtime_device():
 
 
 def control_program(rate: int, position: int, step: int, nblocks: int, cols: int, program: torch.Tensor, n_ins: int,
-                    outs: torch.Tensor, n_outs: int, front_position: int = -1, min_position: int = 0) -> None:
+                    outs: torch.Tensor, n_outs: int, front_position: int = -1, min_position: int = 0, windowed: bool = False) -> None:
     """run a block-rate control program (sig_control_program): `program` / `outs` are device byte tensors of CtlIns / CtlOut;
     `front_position` >= 0 also evaluates it at that position into the outputs' `front` rows; blocks whose position lies below
-    `min_position` are evaluated there"""
+    `min_position` are evaluated there.  `windowed`: the program holds Noise / Filter instructions (sig_control_program_windowed)"""
     _gpu(program, outs)
-    _check(lib().sig_control_program(rate, position, step, nblocks, cols, front_position, min_position, program.data_ptr(), n_ins,
+    entry = lib().sig_control_program_windowed if windowed else lib().sig_control_program
+    _check(entry(rate, position, step, nblocks, cols, front_position, min_position, program.data_ptr(), n_ins,
                                      outs.data_ptr(), n_outs, _stream(program)), 'sig_control_program')
 
 
 def control_program_description(ins: list, outs: list) -> list:
     """what a specialised build of control_program.hip is keyed by: [n_ins, n_outs, (op, kind, a, b, c, dst, wide) per
-    instruction, (reg, wide) per output] -- the program's structure without its pointers (CtlIns / CtlOut lists)"""
+    instruction (wide: bit 0 more than one column, bit 1 window-rate), (reg, wide) per output] -- the program's structure without its pointers (CtlIns / CtlOut lists)"""
     words = [len(ins), len(outs)]
     for x in ins:
-        words += [x.op, x.kind, x.a, x.b, x.c, x.dst, 1 if x.cols > 1 else 0]
+        words += [x.op, x.kind, x.a, x.b, x.c, x.dst, (1 if x.cols > 1 else 0) | (2 if x.reserved else 0)]
     for o in outs:
         words += [o.reg, 1 if o.cols > 1 else 0]
     return words

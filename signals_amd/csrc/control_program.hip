@@ -14,7 +14,11 @@
 #include <mutex>
 #include <vector>
 
+#include "sig_biquad.h"
+#include "sig_noise.h"
 #include "sig_osc.h"
+
+#define SIG_CTL_CONTEXT 100                 // a filter's `before` window: min(100, p) rows (fx.py:105, CritFilter.context_frames)
 
 #ifdef SIG_CTL_STATIC_INS
 // A SPECIALISED build of this file (signals_amd/specialise.py: hipcc --genco with the program's structure as macros): the
@@ -30,6 +34,11 @@ constexpr SIns kIns[] = SIG_CTL_STATIC_INS;
 constexpr SOut kOuts[] = SIG_CTL_STATIC_OUTS;
 constexpr int kN = (int)(sizeof(kIns) / sizeof(kIns[0])), kNO = (int)(sizeof(kOuts) / sizeof(kOuts[0]));
 constexpr int kSpecThreads = 256;
+static_assert(kSpecThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h + 1 <= 101 window rows over the threads");
+// wide: bit 0 = more than one column, bit 1 = window-rate (the run right in front of a FILTER)
+constexpr int window_start(int k) { int w = k; while (w > 0 && (kIns[w - 1].wide & 2)) --w; return w; }
+constexpr bool has_filter() { for (int k = 0; k < kN; ++k) if (kIns[k].op == SIG_CTL_FILTER) return true; return false; }
+constexpr bool kHasFilter = has_filter();
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(double rate, int64_t position, int64_t step, int nblocks, int cols,
@@ -37,42 +46,96 @@ extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(d
                                                                                const sig_ctl_ins* __restrict__ program, int n_ins,
                                                                                const sig_ctl_out* __restrict__ outs, int n_outs)
 {
+    // (the header's SIG_CTL_FILTER / SIG_CTL_NOISE semantics, as in the interpreter below)
     const bool front = front_position >= 0 && blockIdx.x == (unsigned)nblocks;
     const int64_t b = front ? 0 : blockIdx.x;
     if (front) { position = front_position; step = 0; }
+    int64_t frame_b = position + b * step;
+    if (!front && frame_b < min_position) frame_b = min_position;
+    const int h = (int)(frame_b < SIG_CTL_CONTEXT ? frame_b : SIG_CTL_CONTEXT);     // a filter's history rows: min(100, p)
     double reg[kN];
 #pragma unroll
     for (int k = 0; k < kN; ++k) reg[k] = 0.0;
+    auto get = [&](int r) { return r < 0 ? 0.0 : reg[r]; };
+    auto exec = [&](int k, int v, int64_t frame, bool narrow) {
+        const SIns I = kIns[k];
+        double x;
+        switch (I.op) {
+            case SIG_CTL_ROW: {
+                const sig_ctl_ins& ins = program[k];
+                x = ins.row[(ins.rows > 1 ? b * (int64_t)(ins.stride ? ins.cols : 1) : 0) + (int64_t)(v < ins.cols ? v : 0) * ins.stride];
+                break;
+            }
+            case SIG_CTL_OSC: {
+                const double t = (double)frame / rate * get(I.a) + get(I.b);          // osc.py:32
+                if (narrow) {                                                          // osc_bank.hip's f32 store path
+                    switch (I.kind) {
+                        case SIG_OSC_SINE: x = sig_osc::osc_wave<SIG_OSC_SINE, float>(t); break;
+                        case SIG_OSC_SQUARE: x = sig_osc::osc_wave<SIG_OSC_SQUARE, float>(t); break;
+                        case SIG_OSC_SAWTOOTH: x = sig_osc::osc_wave<SIG_OSC_SAWTOOTH, float>(t); break;
+                        default: x = sig_osc::osc_wave<SIG_OSC_TRIANGLE, float>(t); break;
+                    }
+                    break;
+                }
+                switch (I.kind) {
+                    case SIG_OSC_SINE: x = sig_osc::osc_sine(t); break;
+                    case SIG_OSC_SQUARE: x = sig_osc::osc_square(t); break;
+                    case SIG_OSC_SAWTOOTH: x = sig_osc::osc_sawtooth(t); break;
+                    default: x = sig_osc::osc_triangle(t); break;
+                }
+                break;
+            }
+            case SIG_CTL_MIX: { const double c = get(I.c); x = c * get(I.a) + (1.0 - c) * get(I.b); break; }   // fx.py:40
+            case SIG_CTL_AMP: { const double a = get(I.a); x = copysign(pow(a, get(I.b)), a); break; }           // fx.py:60
+            case SIG_CTL_NOISE: x = sig_noise::noise_value((uint64_t)(uintptr_t)program[k].row, frame, v); break;   // noise.hip
+            default: x = get(I.a) * get(I.b); break;                                                           // Gain, RingMod: fx.py:46, :52
+        }
+        if (narrow) x = (double)(float)x;
+        return x;
+    };
+    // window-rate instructions [window_start(k), k) of the FILTER k for the row at `frame`
+    auto window = [&](int k, int v, int64_t frame, bool narrow) {
+#pragma unroll
+        for (int w = 0; w < kN; ++w)
+            if (w >= window_start(k) && w < k) reg[kIns[w].dst] = exec(w, v, frame, narrow);
+    };
+    auto design = [&](int k, bool report, sig_biquad::Biquad& q) {
+        const bool ok = sig_biquad::design_butter2(kIns[k].kind, get(kIns[k].b), rate, q);
+        if (!ok && report && program[k].row) atomicOr(reinterpret_cast<int*>(const_cast<double*>(program[k].row)), SIG_STATUS_BAD_CUTOFF);
+    };
+    __shared__ double xs[kHasFilter ? kSpecThreads : 1];                       // a one-column filter's window rows
     auto run = [&](int v, bool wide_pass) {
 #pragma unroll
         for (int k = 0; k < kN; ++k) {
             const SIns I = kIns[k];
-            if ((I.wide != 0) != wide_pass) continue;
-            auto get = [&](int r) { return r < 0 ? 0.0 : reg[r]; };
-            double x;
-            switch (I.op) {
-                case SIG_CTL_ROW: {
-                    const sig_ctl_ins& ins = program[k];
-                    x = ins.row[(ins.rows > 1 ? b * (int64_t)(ins.stride ? ins.cols : 1) : 0) + (int64_t)(v < ins.cols ? v : 0) * ins.stride];
-                    break;
+            if (I.wide & 2) continue;                                          // window-rate: run by its filter
+            if (((I.wide & 1) != 0) != wide_pass) continue;
+            if (I.op != SIG_CTL_FILTER) { reg[I.dst] = exec(k, v, frame_b, false); continue; }
+            sig_biquad::Biquad q;
+            double z0 = 0.0, z1 = 0.0, y = 0.0;
+            if (!wide_pass) {                                                  // thread j evaluates row j; every thread steps the filter
+                const int j = threadIdx.x;
+                if (j <= h) { window(k, 0, frame_b - h + j, j < h && h > 1); xs[j] = get(I.a); }
+                __syncthreads();
+                design(k, threadIdx.x == 0, q);
+                for (int i = 0; i <= h; ++i) {
+                    const double x = xs[i];
+                    y = q.b0 * x + z0;
+                    z0 = q.b1 * x - q.a1 * y + z1;
+                    z1 = q.b2 * x - q.a2 * y;
                 }
-                case SIG_CTL_OSC: {
-                    int64_t frame = position + b * step;
-                    if (!front && frame < min_position) frame = min_position;
-                    const double t = (double)frame / rate * get(I.a) + get(I.b);          // osc.py:32
-                    switch (I.kind) {
-                        case SIG_OSC_SINE: x = sig_osc::osc_sine(t); break;
-                        case SIG_OSC_SQUARE: x = sig_osc::osc_square(t); break;
-                        case SIG_OSC_SAWTOOTH: x = sig_osc::osc_sawtooth(t); break;
-                        default: x = sig_osc::osc_triangle(t); break;
-                    }
-                    break;
+                __syncthreads();
+            } else {                                                           // thread v walks the rows of its column
+                design(k, v < program[k].cols, q);
+                for (int j = 0; j <= h; ++j) {
+                    window(k, v, frame_b - h + j, j < h && h > 1);
+                    const double x = get(I.a);
+                    y = q.b0 * x + z0;
+                    z0 = q.b1 * x - q.a1 * y + z1;
+                    z1 = q.b2 * x - q.a2 * y;
                 }
-                case SIG_CTL_MIX: { const double c = get(I.c); x = c * get(I.a) + (1.0 - c) * get(I.b); break; }   // fx.py:40
-                case SIG_CTL_AMP: { const double a = get(I.a); x = copysign(pow(a, get(I.b)), a); break; }           // fx.py:60
-                default: x = get(I.a) * get(I.b); break;                                                           // Gain, RingMod: fx.py:46, :52
             }
-            reg[I.dst] = x;
+            reg[I.dst] = y;
         }
     };
     run(0, false);
@@ -115,6 +178,7 @@ namespace {
 constexpr int kMaxRegs = SIG_CTL_MAX_REGS;
 
 constexpr int kThreads = 128;
+static_assert(kThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h + 1 <= 101 window rows over the threads");
 
 // One workgroup per block.  The program is copied into LDS once (fetching every instruction from global memory cost a
 // dependent scalar load of ~0.5 us per instruction per wave); the register file behind it is sized by the program (n_regs x
@@ -122,6 +186,8 @@ constexpr int kThreads = 128;
 // ONCE per block, before the loop over the columns; only the wide ones (the final products with per-voice rows) run per
 // column chunk -- a vibrato + sweep + tremolo program over 1024 blocks x 1024 voices took 65 us with every (block, column)
 // thread running all 26 instructions, three f64 sines among them.
+// EXT (sig_control_program_windowed): also NOISE and FILTER with its window-rate instructions (the header's description).
+template <bool EXT>
 __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, int64_t position, int64_t step, int nblocks, int cols,
                                                                    int64_t front_position, int64_t min_position,
                                                                    const sig_ctl_ins* __restrict__ program, int n_ins,
@@ -146,14 +212,29 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     auto row_value = [&](const sig_ctl_ins& ins, int v) {
         return ins.row[(ins.rows > 1 ? b * (int64_t)(ins.stride ? ins.cols : 1) : 0) + (int64_t)(v < ins.cols ? v : 0) * ins.stride];
     };
-    auto execute = [&](const sig_ctl_ins& ins, int v) {
+    auto block_frame = [&]() {
+        int64_t frame = position + b * step;
+        if (!front && frame < min_position) frame = min_position;              // (the first blocks of a run that starts before min_position are evaluated there)
+        return frame;
+    };
+    const int64_t frame_b = EXT ? block_frame() : 0;                           // (EXT: the filters' window position)
+    // `narrow`: a history row of a filter's window -- every node's reply is float32 audio there (EXT only)
+    auto execute = [&](const sig_ctl_ins& ins, int v, int64_t frame, bool narrow) {
         double x;
         switch (ins.op) {
             case SIG_CTL_ROW: x = row_value(ins, v); break;
             case SIG_CTL_OSC: {
-                int64_t frame = position + b * step;
-                if (!front && frame < min_position) frame = min_position;      // (the first blocks of a run that starts before min_position are evaluated there)
+                if (!EXT) frame = block_frame();
                 const double t = (double)frame / rate * get(ins.a) + get(ins.b);      // osc.py:32
+                if (EXT && narrow) {                                                   // osc_bank.hip's f32 store path
+                    switch (ins.kind) {
+                        case SIG_OSC_SINE: x = sig_osc::osc_wave<SIG_OSC_SINE, float>(t); break;
+                        case SIG_OSC_SQUARE: x = sig_osc::osc_wave<SIG_OSC_SQUARE, float>(t); break;
+                        case SIG_OSC_SAWTOOTH: x = sig_osc::osc_wave<SIG_OSC_SAWTOOTH, float>(t); break;
+                        default: x = sig_osc::osc_wave<SIG_OSC_TRIANGLE, float>(t); break;
+                    }
+                    break;
+                }
                 switch (ins.kind) {
                     case SIG_OSC_SINE: x = sig_osc::osc_sine(t); break;
                     case SIG_OSC_SQUARE: x = sig_osc::osc_square(t); break;
@@ -164,9 +245,53 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
             }
             case SIG_CTL_MIX: { const double c = get(ins.c); x = c * get(ins.a) + (1.0 - c) * get(ins.b); break; }   // fx.py:40
             case SIG_CTL_AMP: { const double a = get(ins.a); x = copysign(pow(a, get(ins.b)), a); break; }           // fx.py:60
+            case SIG_CTL_NOISE:
+                if (EXT) { x = sig_noise::noise_value((uint64_t)(uintptr_t)ins.row, frame, v); break; }   // noise.hip
+                [[fallthrough]];
             default: x = get(ins.a) * get(ins.b); break;                                                           // Gain, RingMod: fx.py:46, :52
         }
+        if (EXT && narrow) x = (double)(float)x;
         r[ins.dst * kThreads] = x;
+    };
+    // FILTER `f` over the window-rate instructions [w0, k): the biquad designed from the cutoff register, cold-started over
+    // the rows p - h .. p (biquad.hip: design_butter2, then scipy's _sosfilt step, one rounding per operation)
+    auto design = [&](const sig_ctl_ins& f, bool report, sig_biquad::Biquad& q) {
+        const bool ok = sig_biquad::design_butter2(f.kind, get(f.b), rate, q);
+        if (!ok && report && f.row) atomicOr(reinterpret_cast<int*>(const_cast<double*>(f.row)), SIG_STATUS_BAD_CUTOFF);
+    };
+    const int h = (int)(frame_b < SIG_CTL_CONTEXT ? frame_b : SIG_CTL_CONTEXT);     // BlockLoc.before: min(100, p)
+    // one column: thread j evaluates window row j, then every thread steps the filter over the rows in the register file
+    auto filter_narrow = [&](const sig_ctl_ins& f, int w0, int k) {
+        const int j = threadIdx.x;
+        if (j <= h)
+            for (int w = w0; w < k; ++w) execute(prog[w], 0, frame_b - h + j, j < h && h > 1);
+        __syncthreads();
+        sig_biquad::Biquad q;
+        design(f, threadIdx.x == 0, q);
+        double z0 = 0.0, z1 = 0.0, y = 0.0;
+        const double* xs = regs + f.a * kThreads;
+        for (int i = 0; i <= h; ++i) {
+            const double x = xs[i];
+            y = q.b0 * x + z0;
+            z0 = q.b1 * x - q.a1 * y + z1;
+            z1 = q.b2 * x - q.a2 * y;
+        }
+        __syncthreads();                                                       // (every thread has read the rows)
+        r[f.dst * kThreads] = y;
+    };
+    // wider: thread v walks the rows of its own column
+    auto filter_wide = [&](const sig_ctl_ins& f, int w0, int k, int v) {
+        sig_biquad::Biquad q;
+        design(f, v < f.cols, q);
+        double z0 = 0.0, z1 = 0.0, y = 0.0;
+        for (int j = 0; j <= h; ++j) {
+            for (int w = w0; w < k; ++w) execute(prog[w], v, frame_b - h + j, j < h && h > 1);
+            const double x = get(f.a);
+            y = q.b0 * x + z0;
+            z0 = q.b1 * x - q.a1 * y + z1;
+            z1 = q.b2 * x - q.a2 * y;
+        }
+        r[f.dst * kThreads] = y;
     };
     // ---- one column wide: once per block (every thread computes the same value into its own copy of the register).
     // Leading ROW instructions of that kind keep their global loads four in flight.
@@ -179,8 +304,22 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
 #pragma unroll
         for (int u = 0; u < 4; ++u) if (k + u < k0) r[prog[k + u].dst * kThreads] = x[u];
     }
-    for (int k = k0; k < n_ins; ++k)
-        if (prog[k].cols == 1) execute(prog[k], 0);
+    if (!EXT) {
+        for (int k = k0; k < n_ins; ++k)
+            if (prog[k].cols == 1) execute(prog[k], 0, frame_b, false);
+    } else {
+        int w0 = -1;                                                           // first instruction of the current window run
+        for (int k = k0; k < n_ins; ++k) {
+            const sig_ctl_ins& ins = prog[k];
+            if (ins.reserved) { if (w0 < 0) w0 = k; continue; }
+            if (ins.op == SIG_CTL_FILTER) {
+                if (ins.cols == 1) filter_narrow(ins, w0 < 0 ? k : w0, k);
+                w0 = -1;
+            } else if (ins.cols == 1) {
+                execute(ins, 0, frame_b, false);
+            }
+        }
+    }
     if (threadIdx.x == 0)
         for (int k = 0; k < n_outs; ++k)
             if (outs[k].cols == 1) {
@@ -190,8 +329,22 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     // ---- wider: per chunk of 128 columns
     for (int v0 = 0; v0 < cols; v0 += kThreads) {
         const int v = v0 + threadIdx.x;
-        for (int k = k0; k < n_ins; ++k)
-            if (prog[k].cols > 1) execute(prog[k], v);
+        if (!EXT) {
+            for (int k = k0; k < n_ins; ++k)
+                if (prog[k].cols > 1) execute(prog[k], v, frame_b, false);
+        } else {
+            int w0 = -1;
+            for (int k = k0; k < n_ins; ++k) {
+                const sig_ctl_ins& ins = prog[k];
+                if (ins.reserved) { if (w0 < 0) w0 = k; continue; }
+                if (ins.op == SIG_CTL_FILTER) {
+                    if (ins.cols > 1) filter_wide(ins, w0 < 0 ? k : w0, k, v);
+                    w0 = -1;
+                } else if (ins.cols > 1) {
+                    execute(ins, v, frame_b, false);
+                }
+            }
+        }
         for (int k = 0; k < n_outs; ++k) {
             const sig_ctl_out o = outs[k];
             if (o.cols > 1 && v < o.cols) {
@@ -202,11 +355,10 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     }
 }
 
-}  // namespace
-
-extern "C" int sig_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
-                                   int64_t front_position, int64_t min_position,
-                                   const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
+template <bool EXT>
+int launch_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
+                           int64_t front_position, int64_t min_position,
+                           const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
 {
     SIG_CHECK_ARG(rate > 0 && step >= 0 && nblocks >= 0 && cols >= 1 && n_ins >= 0 && n_outs >= 0 && front_position >= -1 && min_position >= 0);
     SIG_CHECK_ARG((program || n_ins == 0) && (outs || n_outs == 0) && n_ins <= SIG_CTL_MAX_INS);
@@ -215,9 +367,25 @@ extern "C" int sig_control_program(int32_t rate, int64_t position, int32_t step,
     // here -- the LDS register file is sized by n_ins, and n_ins <= SIG_CTL_MAX_INS == SIG_CTL_MAX_REGS was checked above
     static_assert(SIG_CTL_MAX_INS <= SIG_CTL_MAX_REGS, "the register file is sized by the instruction count");
     const int n_regs = n_ins > 0 ? n_ins : 1;
-    control_program_kernel<<<(unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>((double)rate, position, step, nblocks, cols, front_position, min_position,
+    control_program_kernel<EXT><<<(unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>((double)rate, position, step, nblocks, cols, front_position, min_position,
                                                                                           program, n_ins, outs, n_outs);
     return sig_launch_status();
+}
+
+}  // namespace
+
+extern "C" int sig_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
+                                   int64_t front_position, int64_t min_position,
+                                   const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
+{
+    return launch_control_program<false>(rate, position, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, stream);
+}
+
+extern "C" int sig_control_program_windowed(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
+                                            int64_t front_position, int64_t min_position,
+                                            const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
+{
+    return launch_control_program<true>(rate, position, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, stream);
 }
 
 // ---- specialised builds of this file (see the top): attached at run time, launched through a handle.  The program itself is in

@@ -1,21 +1,9 @@
 // White noise for gfx950: uniform [0,1) per (frame, channel), replacing White._eval
 // (reference src/signals/chain/noise.py:22-23, np.random.rand on the global unseeded RNG).
-// Counter-based: one 64-bit mix per PAIR of adjacent channels (high and low words), so a block is
-// the same whatever launch geometry or position batching produced it.  HBM-write-bound (4 B/sample).
-#include "sig_common.h"
+// Counter-based (sig_noise.h).  HBM-write-bound (4 B/sample).
+#include "sig_noise.h"
 
 namespace {
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint32_t noise_bits(uint64_t seed, int64_t frame, int channel) {
-    const uint64_t h = mix64(seed + (uint64_t)frame * 0x9E3779B97F4A7C15ULL + (uint64_t)(channel >> 1) * 0xD1B54A32D192ED03ULL);
-    return (channel & 1) ? (uint32_t)(h >> 32) : (uint32_t)h;
-}
 
 template <typename OUT>
 __global__ __launch_bounds__(256) void white_kernel(uint64_t seed, int64_t position, int64_t rows, int channels,
@@ -25,8 +13,7 @@ __global__ __launch_bounds__(256) void white_kernel(uint64_t seed, int64_t posit
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / channels;
         const int c = (int)(i - r * channels);
-        const uint32_t k = noise_bits(seed, position + r, c) >> 8;           // 24 bits
-        out[r * ld + c] = (OUT)((float)k * 5.9604644775390625e-8f);          // k * 2^-24, exact in f32
+        out[r * ld + c] = (OUT)sig_noise::noise_value(seed, position + r, c);           // k * 2^-24, exact in f32
     }
 }
 

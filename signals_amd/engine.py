@@ -32,9 +32,12 @@ Node classes without a kernel schedule (plugins, including ones written against 
 answer numpy arrays) are pulled block by block through their own `respond()` and laid out as a batch
 buffer; everything downstream of them still runs one launch per node.
 
-Graphs that do not fit (a filter inside a control path, per-block ADSR parameters, cascaded filters with
-N <= 100 that the voice program does not cover) raise `NotBatchable`; callers fall back to the eager path
-(`BlockDriver` does so by itself).
+A LowPass / HighPass inside a control path (an LFO softened by a filter, smoothed random drift from White) is part of the
+control program: its input subgraph runs per window row inside the launch (`_ControlProgram._filter`), for N > 100.
+
+Graphs that do not fit (a filter of a filter or a band filter in a control path, a filtered control with N <= 100, per-block
+ADSR parameters, cascaded filters with N <= 100 that the voice program does not cover) raise `NotBatchable`; callers fall back
+to the eager path (`BlockDriver` does so by itself).
 """
 from __future__ import annotations
 
@@ -415,11 +418,15 @@ class _ControlProgram:
     (an edited value re-uploads into a new tensor: recompile).  Outputs are owned by the program and overwritten by the
     next run -- their consumers are launches enqueued before that on the same stream."""
 
-    def __init__(self, srcs: tuple, K: int, lead: int = 0, into: dict | None = None):
+    def __init__(self, srcs: tuple, K: int, lead: int = 0, into: dict | None = None, channels: int | None = None, status=None):
         """`lead`: every computed output is rows [lead:] of a (lead + K, cols) buffer `self.full[i]` whose row lead - 1 is the
         `front` row -- the layout sig_voice_program takes its per-block rows in ([rows in front | K blocks]); `into`: {source
-        index: (K, cols) tensor} to write into instead of buffers of its own (rows of another program's `full`)"""
+        index: (K, cols) tensor} to write into instead of buffers of its own (rows of another program's `full`); `channels`: the
+        width of the request the ports are read for (a LowPass / HighPass / White in the subgraph answers exactly that many
+        columns); `status`: node -> its status word tensor (the control filters')"""
         self.srcs, self.K = srcs, K
+        self.channels, self._status = channels, status
+        self._window: dict | None = None                   # inside a filter's input: node -> (register, cols), window-rate
         self.full: dict[int, torch.Tensor] = {}
         self.ins: list = []
         self.keep: list[torch.Tensor] = []                  # tensors the instructions point into
@@ -467,6 +474,7 @@ class _ControlProgram:
         for o in outs:
             o.reg = new_of[o.reg]
         self.n_ins, self.n_outs = len(self.ins), len(outs)
+        self.windowed = any(x.op in _native.CTL_WINDOWED_OPS for x in self.ins)      # (sig_control_program_windowed)
         self.description = _native.control_program_description(self.ins, outs)     # (its structure: what a specialised kernel is built for)
         self.program_t = _native.upload_structs(self.ins) if self.ins else None
         self.outs_t = _native.upload_structs(outs) if outs else None
@@ -507,9 +515,82 @@ class _ControlProgram:
             c, cc = self._emit(src.mix.sig) if isinstance(src, fx.Mix) else (-1, 1)
             cols = broadcast_shape((1, ca), (1, cb), (1, cc))[1]
             got = self._push(_native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, 0, None), cols)
+        elif isinstance(src, noise.White):
+            got = self._push(self._noise(src, window=False), self._request_width(src))
+        elif isinstance(src, fx.SingleCritFilter):
+            got = self._filter(src)
+        elif isinstance(src, fx.DoubleCritFilter):
+            raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
         else:
             raise NotBatchable(f'no block-rate program for {src.cls_name()}')
         self._reg[src] = got
+        return got
+
+    def _request_width(self, src) -> int:
+        if self.channels is None:
+            raise NotBatchable(f'{src.cls_name()} in a control path whose request width is not known here')
+        return self.channels
+
+    def _noise(self, src, window: bool):
+        cols = self._request_width(src)
+        return _native.CtlIns(_native.CTL_OPS['Noise'], 0, -1, -1, -1, 0, 0, 0, cols, int(window), src.get_state().seed)
+
+    def _filter(self, src) -> tuple[int, int]:
+        """a LowPass / HighPass read at one frame: its cutoff as a block-rate register, its input subgraph as the window-rate
+        run right in front of the filter instruction (control_program.hip)"""
+        if self._window is not None:
+            raise NotBatchable('a filter whose input contains a filter, in a control path')
+        width = self._request_width(src)
+        cut, ccut = self._emit(src.cutoff.sig)
+        inp = src.input.sig
+        if inp is None or not inp.get_state().enabled or isinstance(inp, fixed.Fixed):
+            raise NotBatchable(f'{src.cls_name()} in a control path over a one-row input')
+        self._window = {}
+        try:
+            a, ca = self._emit_window(inp)
+            inside = set(self._window)
+        finally:
+            self._window = None
+        for n in inside:                                   # (what feeds the filter is evaluated per window row, for it alone)
+            if any(r is not src and r not in inside for _, r in n.outputs_with_ports):
+                raise NotBatchable(f'{n.cls_name()} inside a control filter\'s input has a reader outside that filter')
+        if ca < width or ccut < width:                     # fx.py:110-113: the eager path raises IndexError
+            raise NotBatchable(f'{src.cls_name()} in a control path narrower than its request')
+        status = None if self._status is None else self._status(src)
+        return self._push(_native.CtlIns(_native.CTL_OPS['Filter'], _native.FILT_TYPES[str(src.type())], a, cut, -1, 0, 0, 0,
+                                         width, 0, None if status is None else status.data_ptr()), width)
+
+    def _emit_window(self, src) -> tuple[int, int]:
+        """a node of a control filter's input: evaluated per window row (`reserved` = 1); its own control ports must hold for
+        every row (Fixed / unplugged)"""
+        if src is None or not src.get_state().enabled or isinstance(src, fixed.Fixed):
+            return self._emit(src)                         # a constant row: block rate
+        if src in self._window:
+            return self._window[src]
+        def const(port):
+            if not _ctl_const(port):
+                raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input has a modulated {port.name}')
+            return self._emit(port.sig)
+        if isinstance(src, osc.Osc):
+            (a, ca), (b, cb) = const(src.hertz), const(src.phase)
+            cols = max(ca, cb)
+            ins = _native.CtlIns(_native.CTL_OPS['Osc'], _native.OSC_KINDS[src.kind()], a, b, -1, 0, 0, 0, cols, 1, None)
+        elif isinstance(src, noise.White):
+            ins, cols = self._noise(src, window=True), self._request_width(src)
+        elif isinstance(src, (fx.Gain, fx.Amp)):
+            (a, ca), (b, cb) = self._emit_window(src.left.sig), const(src.right)
+            cols = broadcast_shape((1, ca), (1, cb))[1]
+            ins = _native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, -1, 0, 0, 0, cols, 1, None)
+        elif isinstance(src, (fx.Mix, fx.RingMod)):
+            (a, ca), (b, cb) = self._emit_window(src.left.sig), self._emit_window(src.right.sig)
+            c, cc = const(src.mix) if isinstance(src, fx.Mix) else (-1, 1)
+            cols = broadcast_shape((1, ca), (1, cb), (1, cc))[1]
+            ins = _native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, 1, None)
+        elif isinstance(src, fx.CritFilter):
+            raise NotBatchable('a filter whose input contains a filter, in a control path')
+        else:
+            raise NotBatchable(f'no window-rate program for {src.cls_name()} inside a control filter\'s input')
+        got = self._window[src] = self._push(ins, cols)
         return got
 
     def current(self) -> bool:
@@ -530,7 +611,8 @@ class _ControlProgram:
             else:
                 owner._launch('control_program[block-rate]',
                               lambda: _native.control_program(rate, position, step, self.K, self.cols, self.program_t, self.n_ins,
-                                                              self.outs_t, self.n_outs, front_position, min_position), units=self.K * self.cols)
+                                                              self.outs_t, self.n_outs, front_position, min_position,
+                                                              windowed=self.windowed), units=self.K * self.cols)
         rows = [as_control(src.resident()) if r is None else r for src, r in zip(self.srcs, self.results)]
         if any(t.shape[0] not in (1, self.K) or (r is None and t.shape[0] != 1) for t, r in zip(rows, self.results)):
             raise NotBatchable('multi-row Fixed on a control port')             # (edited since the program was compiled)
@@ -552,6 +634,8 @@ class _Batch:
         self._need: dict[tuple[Emitter, int], int] = {}
         self._impure: dict[Emitter, torch.Tensor] = {}
         self._ctl_memo: dict[Emitter, torch.Tensor] = {}
+        self._widths: list[int] = []            # request widths of the nodes being scheduled (what their control ports are read with)
+        self.history_of: int | None = None      # this batch renders the history block in front of a fresh batch at that position
 
     # -------------------------------------------------------------- control rows
     def _control_const(self, port: Receiver.BoundPort, what: str) -> torch.Tensor:
@@ -571,19 +655,22 @@ class _Batch:
         request at position pos + b*N (forward_at_block_rate of block b)."""
         return self._control_node(port.sig, what)
 
-    def _control_many(self, ports: list, front_position: int = -1):
+    def _control_many(self, ports: list, front_position: int = -1, channels: int | None = None):
         """the block-rate replies of several control ports, their subgraphs evaluated in one launch where they consist of
-        oscillators, element-wise nodes and Fixed rows (else node by node, like `_control`); with `front_position` also their
-        one-row replies at that position: (rows, fronts)"""
+        oscillators, element-wise nodes, Fixed rows, White and LowPass / HighPass over those (else node by node, like `_control`);
+        with `front_position` also their one-row replies at that position: (rows, fronts).  `channels`: the request width the
+        ports are read with."""
         o = self.owner
         srcs = tuple(p.sig for p in ports)
-        key = (tuple(id(x) for x in srcs), self.K)
+        key = (tuple(id(x) for x in srcs), self.K, channels)
         try:
             held = o._ctl_programs.get(key)
             if held is None or held[0] != graph_clock.version or not held[1].current():
                 if len(o._ctl_programs) > 16:
                     o._ctl_programs.clear()
-                held = o._ctl_programs[key] = (graph_clock.version, _ControlProgram(srcs, self.K))
+                held = o._ctl_programs[key] = (graph_clock.version, _ControlProgram(srcs, self.K, channels=channels,
+                                                                                   status=o._status_word))
+            self._check_windowed(held[1], [front_position] if front_position >= 0 else [])
             return held[1].run(o, self.rate, self.pos, self.N, front_position)
         except NotBatchable:
             rows = [self._control(p, p.name) for p in ports]
@@ -611,6 +698,20 @@ class _Batch:
                       lambda: _native.osc_bank(src.kind(), self.pos, self.rate, hertz, phase, result,
                                                step=self.N, rows_per_param=1),
                       units=K * voices)
+        elif isinstance(src, (fx.SingleCritFilter, fx.DoubleCritFilter, noise.White)):
+            # a filter (or White) read at one frame per block: a control program of its own -- the filter's input is evaluated
+            # per window row inside the launch, nothing of it goes through memory
+            if not self._widths:
+                raise NotBatchable(f'{what}: {src.cls_name()} read where the request width is not known')
+            width = self._widths[-1]
+            key = ('node', id(src), K, width)
+            held = o._ctl_programs.get(key)
+            if held is None or held[0] != graph_clock.version or not held[1].current():
+                if len(o._ctl_programs) > 16:
+                    o._ctl_programs.clear()
+                held = o._ctl_programs[key] = (graph_clock.version, _ControlProgram((src,), K, channels=width, status=o._status_word))
+            self._check_windowed(held[1], [])
+            result = held[1].run(o, self.rate, self.pos, self.N)[0]
         elif isinstance(src, (fx.Gain, fx.Amp, fx.Mix, fx.RingMod)):
             name = type(src).__name__
             a = self._control(src.left, 'left')
@@ -626,6 +727,21 @@ class _Batch:
             raise NotBatchable(f'{what}: no block-rate schedule for {src.cls_name()}')
         self._ctl_memo[src] = result
         return result
+
+    def _check_windowed(self, program: '_ControlProgram', ahead: list) -> None:
+        """where a filter in a control path answers what the batch cannot: the reference's block cache serves a one-frame read
+        at p from the `after` window [q + 1, q + 101) of an earlier read at q (chain/cache.py), i.e. the float32 window value --
+        blocks of <= 100 frames, and a read within 100 frames behind another one (`ahead`: the positions read in front of this
+        batch's blocks, oldest first; the history block rendered in front of a fresh batch)"""
+        if not program.windowed:
+            return
+        if self.N <= CONTEXT and (self.K > 1 or self.continuing):
+            raise NotBatchable('a filter in a control path with blocks of <= 100 frames (the next block is served from the '
+                               'after-window cache)')
+        reads = ahead + [self.pos] + ([self.history_of] if self.history_of is not None else [])
+        if any(0 < q1 - q0 <= CONTEXT for q0, q1 in zip(reads, reads[1:])):
+            raise NotBatchable('a filter in a control path read within 100 frames in front of a fresh batch (the batch\'s first '
+                               'block is served from the after-window cache)')
 
     # -------------------------------------------------------------- history requirements
     def _require(self, node: Emitter | None, channels: int, hist: int) -> None:
@@ -678,16 +794,20 @@ class _Batch:
         hist = self._need[key]
         rows = hist + self.N * self.K
 
-        result = _VoiceChain.match_and_launch(self, node, channels, hist) if self.owner.fuse else None
-        if result is None and self.owner.fuse_program and hist == 0 and isinstance(node, _VoiceProgram.KERNEL_NODES):
-            result = self._program_store(node, channels)
-        if result is None:
-            for types, build in self._SCHEDULES:
-                if isinstance(node, types):
-                    result = build(self, node, channels, hist, rows)
-                    break
-            else:
-                result = self._sched_foreign(node, channels, hist, rows)
+        self._widths.append(channels)
+        try:
+            result = _VoiceChain.match_and_launch(self, node, channels, hist) if self.owner.fuse else None
+            if result is None and self.owner.fuse_program and hist == 0 and isinstance(node, _VoiceProgram.KERNEL_NODES):
+                result = self._program_store(node, channels)
+            if result is None:
+                for types, build in self._SCHEDULES:
+                    if isinstance(node, types):
+                        result = build(self, node, channels, hist, rows)
+                        break
+                else:
+                    result = self._sched_foreign(node, channels, hist, rows)
+        finally:
+            self._widths.pop()
         if isinstance(result, tuple):                                          # a pass-through shares its input's buffer
             self._memo[key] = result
             return result
@@ -1133,6 +1253,7 @@ class _Batch:
             result[:hist].copy_(tail[1][tail[1].shape[0] - hist:, :channels])
         else:
             sub = _Batch(o, pos - hist, hist, 1, False)
+            sub.history_of = pos
             result[:hist].copy_(sub.buffer(node, channels, 0))
 
     def impure_outputs(self):
@@ -1243,7 +1364,7 @@ class _VoiceChain:
                 if self.fm:
                     contiguous = o._stream_end == b.pos and bool(o._prev_block_frames) and o._prev_block_frames >= min(CONTEXT, b.pos)
                     q = b.pos - (o._prev_block_frames if contiguous else min(CONTEXT, b.pos))
-                got = b._control_many(ports, q)
+                got = b._control_many(ports, q, channels=self.channels)
                 vals, fronts = (got, None) if q < 0 else got
                 vals = [as_control(t) for t in vals]
                 rows, gains = vals[:3], vals[3:]
@@ -1636,17 +1757,21 @@ class _ProgramRows:
                           blocks' own positions (`inner` False) or where the oldest cached reply containing the block was
                           evaluated (`inner`: the ports in front of the voice's last filter; header of sig_voice_program)."""
 
-    def __init__(self, srcs: tuple, K: int, lead: int, small: bool):
+    def __init__(self, srcs: tuple, K: int, lead: int, small: bool, channels: int | None = None, status=None):
         self.srcs, self.K, self.lead, self.small = srcs, K, lead, small
+        more = dict(channels=channels, status=status)
         if not small:
-            self.main = _ControlProgram(srcs, K, lead=lead)
+            self.main = _ControlProgram(srcs, K, lead=lead, **more)
             self.full = self.main.full
-            self.front = [_ControlProgram(srcs, 1, into={i: t[j:j + 1] for i, t in self.full.items()}) for j in range(lead - 1)]
+            self.front = [_ControlProgram(srcs, 1, into={i: t[j:j + 1] for i, t in self.full.items()}, **more) for j in range(lead - 1)]
         else:
-            probe = _ControlProgram(srcs, K, lead=K)                           # rows [K:] of (2 K, cols) buffers: the blocks themselves
+            probe = _ControlProgram(srcs, K, lead=K, **more)                   # rows [K:] of (2 K, cols) buffers: the blocks themselves
             self.main, self.full = probe, probe.full
-            self.virtual = _ControlProgram(srcs, K, into={i: t[:K] for i, t in self.full.items()})
-            self.first = _ControlProgram(srcs, 1, into={i: t[K:K + 1] for i, t in self.full.items()})
+            if probe.windowed:
+                raise NotBatchable('a filter in a control path with blocks of <= 100 frames (the next block is served from the '
+                                   'after-window cache)')
+            self.virtual = _ControlProgram(srcs, K, into={i: t[:K] for i, t in self.full.items()}, **more)
+            self.first = _ControlProgram(srcs, 1, into={i: t[K:K + 1] for i, t in self.full.items()}, **more)
 
     def current(self) -> bool:
         return self.main.current()
@@ -1869,10 +1994,12 @@ class _VoiceProgram:
             if held is None or held[0] != graph_clock.version or not held[1].current():
                 if len(o._ctl_programs) > 16:
                     o._ctl_programs.clear()
-                held = o._ctl_programs[key] = (graph_clock.version, _ProgramRows(srcs, K, lead, small))
+                held = o._ctl_programs[key] = (graph_clock.version, _ProgramRows(srcs, K, lead, small, channels=self.voices,
+                                                                                 status=o._status_word))
             rows = held[1]
             if not small:
                 ahead = [front] + hist                                         # where the rows in front of the K blocks are read
+                b._check_windowed(rows.main, ahead)
                 rows.main.run(o, b.rate, pos, N, front_position=ahead[lead - 1])       # (the last of them in the same launch)
                 for j, sub in enumerate(rows.front):
                     sub.run(o, b.rate, ahead[j], 0)
