@@ -69,6 +69,22 @@ int sig_osc_bank_mod(int kind, int64_t position, int64_t position_step, int32_t 
                      const double* phase, int32_t phase_stride, int64_t phase_row_stride,
                      void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Phase-modulation (FM) oscillators, chain/ext.py PMSine / PMSquare / PMSawtooth / PMTriangle: sig_osc_bank_mod with the phase
+ * offset by a frame-rate modulator,
+ *   t[n,v]   = ((position + n * position_step) / rate * hertz[v] + phase[v]) + index[v] * (double) mod[n,v]   (f64, that order)
+ *   out[n,v] = wave_kind(t[n,v])
+ * `index` rows: like hertz / phase (per block with rows_per_param); NULL = unplugged = 0.  `mod`: SIG_F32 | SIG_F64,
+ * row n at mod + n * mod_ld, mod_stride 1 = (rows, voices), 0 = (rows, 1); mod_ld 0 = one row for every n; NULL = unplugged = 0.
+ * Position-pure given `mod`.  Same contract as sig_osc_bank: Square / Sawtooth / Triangle bit-exact in f64 before the store,
+ * Sine f64 store within 1 ulp(f64) of the f64 polynomial, f32 store within 1.3e-7. */
+int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                    int32_t voices, int32_t rows_per_param,
+                    const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                    const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                    const double* index, int32_t index_stride, int64_t index_row_stride,
+                    const void* mod, int32_t mod_dtype, int64_t mod_ld, int32_t mod_stride,
+                    void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):
@@ -507,6 +523,9 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *   BAND   acc = band filter over slots a, a + 1 applied to acc    (BandPass / BandStop: cutoff[a] = low rows, cutoff[a + 1] = high
  *          rows, filter_type both SIG_FILT_BANDPASS or both SIG_FILT_BANDSTOP, one filter_level; a run of band slots pairs up from
  *          its first slot; designed per block like butter(2, [low, high]) and run as its two sections)
+ *   OSCPM  acc = wave_kind(n / rate * hertz[a] + phase[a] + params[b] * acc)     oscillator slot a, index = parameter slot b (a
+ *          phase-modulation carrier: the modulator's code runs first and leaves its sample in the accumulator; a program with both
+ *          BAND and OSCPM is refused, hipErrorInvalidValue: the interpreter is built with either, not both)
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -527,7 +546,7 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * sig_fused_voice_bus_workspace(voices, rows, bus_channels) bytes.  f64 arithmetic, no float32 rounding between the nodes.
  * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF. */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
-       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11 };
+       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
 typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;

@@ -36,7 +36,7 @@ EXPORTS = ('sig_abi_version', 'sig_osc_bank', 'sig_osc_bank_mod', 'sig_biquad_co
            'sig_voice_program', 'sig_voice_program_set_tuning', 'sig_voice_program_geometry', 'sig_voice_program_args_size',
            'sig_voice_program_attach', 'sig_voice_program_detach_all', 'sig_voice_program_use_attached',
            'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound', 'sig_band_coldstart_blocks',
-           'sig_control_program_windowed')
+           'sig_control_program_windowed', 'sig_osc_bank_pm')
 
 
 class NativeError(RuntimeError):
@@ -62,7 +62,7 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11}
+          'Band': 11, 'OscPM': 12}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 
@@ -145,6 +145,9 @@ def lib() -> ctypes.CDLL:
                                          vp, i64, i64, vp, i64, i32, vp, vp]
         L.sig_osc_bank_mod.restype = ctypes.c_int
         L.sig_osc_bank_mod.argtypes = [ctypes.c_int, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, vp, i32, i64, vp]
+        L.sig_osc_bank_pm.restype = ctypes.c_int
+        L.sig_osc_bank_pm.argtypes = [ctypes.c_int, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
+                                      vp, i32, i64, i32, vp, i32, i64, vp]
         L.sig_fused_osc_biquad_devpos.restype = ctypes.c_int
         L.sig_fused_osc_biquad_devpos.argtypes = [ctypes.c_int, ctypes.c_int, i32, vp, i32, i32, i32, i32,
                                                   dp, i32, dp, i32, dp, i32, dp, i32, vp, i64, vp, vp]
@@ -323,6 +326,42 @@ def osc_bank(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: to
     _check(lib().sig_osc_bank_mod(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
                                   hp, hs, hrs, pp, ps, prs, out.data_ptr(), _dt(out), out.stride(0), _stream(out)),
            'sig_osc_bank_mod')
+    return out
+
+
+def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None,
+                index: torch.Tensor | None, mod: torch.Tensor | None, out: torch.Tensor, step: int = 1,
+                rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- phase-modulation oscillator `kind` (sig_osc_bank_pm): t = (n / rate * hertz + phase) + index * mod.
+    hertz / phase / index: (1|P, V|1) f64 like `osc_bank`; mod: float32 | float64 (rows|1, V|1), row n modulates output row n."""
+    _gpu(hertz, phase, index, mod, out)
+    _audio(out, 'osc out')
+    rows, voices = out.shape
+    hp, hs, hrs, hrows = _ctrl_rows(hertz, 'hertz')
+    pp, ps, prs, prows = _ctrl_rows(phase, 'phase')
+    ip, is_, irs, irows = _ctrl_rows(index, 'index')
+    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (index, 'index')):
+        if row is not None and row.shape[1] not in (1, voices):
+            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
+    if max(hrows, prows, irows) > 1:
+        if rows_per_param < 1:
+            raise NativeError('per-block oscillator parameters need rows_per_param')
+        need = (rows + rows_per_param - 1) // rows_per_param
+        for n, name in ((hrows, 'hertz'), (prows, 'phase'), (irows, 'index')):
+            if n not in (1, need):
+                raise NativeError(f'{name} has {n} parameter rows, launch needs 1 or {need}')
+    else:
+        rows_per_param = 0
+    mp, mdt, mld, mcs = None, F32, 0, 0
+    if mod is not None:
+        _audio(mod, 'modulator')
+        if mod.shape[0] not in (1, rows) or mod.shape[1] not in (1, voices):
+            raise NativeError(f'modulator {tuple(mod.shape)} does not broadcast to {(rows, voices)}')
+        mp, mdt = mod.data_ptr(), _dt(mod)
+        mld, mcs = (0 if mod.shape[0] == 1 else mod.stride(0)), (0 if mod.shape[1] == 1 else 1)
+    _check(lib().sig_osc_bank_pm(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
+                                 hp, hs, hrs, pp, ps, prs, ip, is_, irs, mp, mdt, mld, mcs,
+                                 out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_pm')
     return out
 
 

@@ -2,6 +2,7 @@
 voice sum (`shape.Flatten`) but it sums over frames and crashes; these nodes are what BASELINE's
 configurations need and are pinned against `oracle/chain_ref.py` ("parity unpinned" by the
 reference itself)."""
+import abc
 import typing
 
 import attr
@@ -94,6 +95,68 @@ class ADSR(BlockCachingEmitter, ImplicitChannels):
         frames, voices = broadcast_shape((request.loc.shape.frames, 1), *(r.shape for r in rows.values()))
         out = torch.empty((frames, voices), dtype=result_dtype(frames), device=runtime.device())
         return _native.adsr(request.loc.position, request.loc.rate, rows, out)
+
+
+class PMOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
+    """Phase-modulation (FM) oscillator: an oscillator of chain/osc.py whose phase is offset by a frame-rate signal,
+    `t = (frame_range / rate * hertz + phase) + index * mod`, `out = wave(t)` in float64 like `osc.Osc` (kernel: sig_osc_bank_pm).
+    Ports: hertz, phase, index at block rate; `mod` at frame rate, in cycles per unit of `index` (a full-scale sine modulator
+    with index I is the textbook modulation index 2 pi I).  Position-pure when `mod` is: no carried phase.  With `mod` or `index`
+    unplugged it is the plain oscillator.  Not an `osc.Osc`: that means a leaf with two control ports to the engine."""
+    hertz: Receiver.BoundPort = port('hertz')
+    phase: Receiver.BoundPort = port('phase')
+    index: Receiver.BoundPort = port('index')
+    mod: Receiver.BoundPort = port('mod')
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR
+
+    @classmethod
+    @abc.abstractmethod
+    def kind(cls) -> str:
+        """kernel selector: 'Sine' | 'Square' | 'Sawtooth' | 'Triangle'"""
+        raise NotImplementedError
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        phase = as_control(self.phase.forward_at_block_rate(request))
+        hertz = as_control(self.hertz.forward_at_block_rate(request))
+        index = as_control(self.index.forward_at_block_rate(request))
+        mod = self.mod.forward(request)
+        if mod.dtype not in (torch.float32, torch.float64) or (mod.shape[1] > 1 and mod.stride(1) != 1):
+            mod = mod.to(result_dtype(mod.shape[0])).contiguous()
+        loc = request.loc
+        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, index.shape, mod.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
+        return _native.osc_bank_pm(self.kind(), loc.position, loc.rate, hertz, phase, index, mod, out)
+
+
+class PMSine(PMOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sine'
+
+
+class PMSquare(PMOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Square'
+
+
+class PMSawtooth(PMOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sawtooth'
+
+
+class PMTriangle(PMOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Triangle'
 
 
 def _validate_matrix(instance, attribute, new_value):

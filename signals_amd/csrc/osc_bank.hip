@@ -117,7 +117,151 @@ int run_osc(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t ou
     return (int)hipErrorInvalidValue;
 }
 
+// ---- phase modulation: t = (n / rate * hertz + phase) + index * mod[n, v], the modulator a frame-rate buffer.
+// Same mapping as osc_bank_kernel (a wave = 64 * VEC voices x 16 rows, n / rate once per row), plus one read per
+// voice-sample: with VEC == 4 and MVEC a lane loads its four float32 modulator samples as one 16-byte access, like its store.
+// Roofline: 4 B read + 4 B written per voice-sample (f32 modulator and store).
+struct PmArgs {
+    const double* index; int is; int64_t irs;                      // (1|P, V|1) f64 like hertz / phase; NULL: unplugged = 0
+    const void* mod; int64_t mld; int mcs;                         // (rows|1, V|1): mld == 0 one row, mcs == 0 one column; NULL: 0
+};
+
+template <int KIND, int VEC, typename OUT, typename MOD, bool MVEC>
+__global__ __launch_bounds__(256) void osc_bank_pm_kernel(OscArgs a, PmArgs m, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int vt = blockIdx.x % voice_tiles;
+    const int64_t rt = blockIdx.x / voice_tiles;
+    const int v0 = (vt * SIG_WAVE + lane) * VEC;
+    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    if (r0 >= a.rows) return;                                      // wave-uniform
+
+    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const MOD* __restrict__ mod = static_cast<const MOD*>(m.mod);
+
+    double hz[VEC], ph[VEC], ix[VEC];
+    int64_t loaded = -1;
+#pragma unroll 2
+    for (int j = 0; j < kRowsPerWave; ++j) {
+        const int64_t row = r0 + j;
+        if (row >= a.rows) break;                                  // wave-uniform
+        const int64_t prow = a.rpp ? row / a.rpp : 0;              // wave-uniform
+        if (prow != loaded) {
+            loaded = prow;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const int v = v0 + i;
+                hz[i] = (v < a.voices) ? a.hertz[prow * a.hrs + (int64_t)v * a.hs] : 0.0;
+                ph[i] = (v < a.voices && a.phase) ? a.phase[prow * a.prs + (int64_t)v * a.ps] : 0.0;
+                ix[i] = (v < a.voices && m.index) ? m.index[prow * m.irs + (int64_t)v * m.is] : 0.0;
+            }
+        }
+        double x[VEC];
+        if (MVEC) {                                                // float32 (rows, V) modulator, 16-byte aligned rows, voices % 4 == 0
+            float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (v0 < a.voices) w = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(m.mod) + row * m.mld + v0);
+            const float f[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) x[i] = (double)f[i & 3];
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                x[i] = (mod && v0 + i < a.voices) ? (double)mod[row * m.mld + (int64_t)(v0 + i) * m.mcs] : 0.0;
+        }
+        const double q = sig_readlane_f64(q_lane, j);
+        OUT y[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const double t = (q * hz[i] + ph[i]) + ix[i] * x[i];   // every operation rounded, in numpy's order
+            y[i] = osc_wave<KIND, OUT>(t);
+        }
+        OUT* dst = out + row * ld + v0;
+        if (VEC == 4) {
+            if (v0 < a.voices) {                                   // voices % 4 == 0 on this path
+                typename sig_vec4<OUT>::type o;
+                o.x = y[0]; o.y = y[1]; o.z = y[2]; o.w = y[3];
+                *reinterpret_cast<typename sig_vec4<OUT>::type*>(dst) = o;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                if (v0 + i < a.voices) dst[i] = y[i];
+        }
+    }
+}
+
+template <int KIND, typename OUT, typename MOD>
+int launch_pm(const OscArgs& a, const PmArgs& m, OUT* out, int64_t ld, hipStream_t stream)
+{
+    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
+                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
+    const bool mvec = vec4 && sizeof(MOD) == 4 && m.mod && m.mcs == 1 && m.mld > 0 && m.mld % 4 == 0 &&
+                      (reinterpret_cast<uintptr_t>(m.mod) % 16) == 0;
+    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
+    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
+    const int span = SIG_WAVE * (vec4 ? 4 : 1);
+    const int voice_tiles = (a.voices + span - 1) / span;
+    const int64_t nwg = row_tiles * voice_tiles;
+    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    if constexpr (sizeof(MOD) == 4) {                              // (the 16-byte modulator load exists for float32 only)
+        if (mvec) {
+            osc_bank_pm_kernel<KIND, 4, OUT, MOD, true><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
+            return sig_launch_status();
+        }
+    }
+    if (vec4)
+        osc_bank_pm_kernel<KIND, 4, OUT, MOD, false><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
+    else
+        osc_bank_pm_kernel<KIND, 1, OUT, MOD, false><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
+    return sig_launch_status();
+}
+
+template <typename OUT, typename MOD>
+int dispatch_pm_kind(int kind, const OscArgs& a, const PmArgs& m, OUT* out, int64_t ld, hipStream_t stream)
+{
+    switch (kind) {
+        case SIG_OSC_SINE: return launch_pm<SIG_OSC_SINE, OUT, MOD>(a, m, out, ld, stream);
+        case SIG_OSC_SQUARE: return launch_pm<SIG_OSC_SQUARE, OUT, MOD>(a, m, out, ld, stream);
+        case SIG_OSC_SAWTOOTH: return launch_pm<SIG_OSC_SAWTOOTH, OUT, MOD>(a, m, out, ld, stream);
+        case SIG_OSC_TRIANGLE: return launch_pm<SIG_OSC_TRIANGLE, OUT, MOD>(a, m, out, ld, stream);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+template <typename MOD>
+int run_pm(int kind, const OscArgs& a, const PmArgs& m, void* out, int32_t out_dtype, int64_t out_ld, hipStream_t s)
+{
+    if (out_dtype == SIG_F32) return dispatch_pm_kind<float, MOD>(kind, a, m, static_cast<float*>(out), out_ld, s);
+    if (out_dtype == SIG_F64) return dispatch_pm_kind<double, MOD>(kind, a, m, static_cast<double*>(out), out_ld, s);
+    return (int)hipErrorInvalidValue;
+}
+
 }  // namespace
+
+extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                               int32_t voices, int32_t rows_per_param,
+                               const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                               const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                               const double* index, int32_t index_stride, int64_t index_row_stride,
+                               const void* mod, int32_t mod_dtype, int64_t mod_ld, int32_t mod_stride,
+                               void* out, int32_t out_dtype, int64_t out_ld, void* stream)
+{
+    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
+    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
+                  (index_stride == 0 || index_stride == 1));
+    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && index_row_stride >= 0);
+    SIG_CHECK_ARG(mod == nullptr || ((mod_dtype == SIG_F32 || mod_dtype == SIG_F64) && (mod_stride == 0 || mod_stride == 1) &&
+                                     (mod_ld == 0 || mod_ld >= (mod_stride ? voices : 1))));
+    if (rows == 0 || voices == 0) return 0;
+    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
+                    phase, phase_stride, phase_row_stride, rows_per_param};
+    const PmArgs m{index, index_stride, index_row_stride, mod, mod_ld, mod_stride};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (mod != nullptr && mod_dtype == SIG_F64) return run_pm<double>(kind, a, m, out, out_dtype, out_ld, s);
+    return run_pm<float>(kind, a, m, out, out_dtype, out_ld, s);
+}
 
 extern "C" int sig_osc_bank(int kind, int64_t position, int32_t rate, int64_t rows, int32_t voices,
                             const double* hertz, int32_t hertz_stride,

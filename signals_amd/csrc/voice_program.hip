@@ -161,7 +161,8 @@ template <bool SMALL> struct VpLimits {
 // C == 0: store (float) acc to a.out; C > 0: C bus channels into a.partials.  EXT: Amp, ADSR and White instructions.
 // BAND: the Band instruction (band filters' per-voice middle taps and their design; a variant of its own, so that programs
 // without one keep the registers they had -- the band state and its inlined design cost the SMALL file ~200 B of scratch per lane)
-template <int VPT, bool SMALL, int C, bool BAND>
+// PM: the OscPM instruction (phase-modulation carriers), a variant of its own for the same reason
+template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave)
 {
     constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
@@ -511,6 +512,50 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                         }
                     });
                     break;
+                case SIG_VP_OSCPM: if constexpr (PM) {                         // the Osc handler, its phase offset by index * accumulator (ext.py PMOsc)
+                    double ix[VPT];
+                    with_index<NP>(ib, [&](auto I) {
+#pragma unroll
+                        for (int i = 0; i < VPT; ++i) ix[i] = pr[decltype(I)::value][i];
+                    });
+                    with_index<NO>(ia, [&](auto I) {
+                        constexpr int S = decltype(I)::value;
+                        double t[R][VPT];
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            const double qr = vp_pin(q[r]);
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) t[r][i] = (qr * ohz[S][i] + oph[S][i]) + ix[i] * acc[r][i];
+                        }
+                        switch (kind) {
+                            case SIG_OSC_SINE:
+#pragma unroll
+                                for (int r = 0; r < R; ++r)
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) acc[r][i] = (double)sig_osc::osc_sine_f32(t[r][i]);
+                                break;
+                            case SIG_OSC_SAWTOOTH:
+#pragma unroll
+                                for (int r = 0; r < R; ++r)
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_sawtooth_fract(t[r][i]);
+                                break;
+                            case SIG_OSC_SQUARE:
+#pragma unroll
+                                for (int r = 0; r < R; ++r)
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_square_fract(t[r][i]);
+                                break;
+                            default:
+#pragma unroll
+                                for (int r = 0; r < R; ++r)
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_triangle_fract(t[r][i]);
+                                break;
+                        }
+                    });
+                }
+                    break;
                 case SIG_VP_FILTER:
                     with_index<NF>(ia, [&](auto I) {
                         constexpr int F = decltype(I)::value;
@@ -715,14 +760,14 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a)
 {
     constexpr bool BUS = C > 0;
     __shared__ double lds[BUS ? 4 : 1][BUS ? sig_bus::kPairs * kTileStride : 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND>(a, lds[BUS ? wave : 0], lane, wave);
+    vp_wave<VPT, SMALL, C, BAND, PM>(a, lds[BUS ? wave : 0], lane, wave);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -742,7 +787,13 @@ void sig_vp_specialised(VpArgs a)
         for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) band |= (c[k] & 31u) == (uint32_t)SIG_VP_BAND;
         return band;
     }();
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand>(a);
+    constexpr bool kPm = [] {
+        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
+        bool pm = false;
+        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) pm |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCPM;
+        return pm;
+    }();
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm>(a);
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
 extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
@@ -752,10 +803,10 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
     for (unsigned k = 0; k < sizeof(code) / sizeof(code[0]); ++k) out[4 + k] = code[k];
 }
 #else
-template <int VPT, bool SMALL, int C, bool BAND>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND>(a);
+    vp_kernel_body<VPT, SMALL, C, BAND, PM>(a);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -771,7 +822,7 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_BAND && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15))
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCPM && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)x.c << 16);
     }
@@ -788,7 +839,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -817,21 +868,22 @@ void vp_geometry(const VpArgs& a, int store_aligned, bool four, int& vpt, int& s
     }
 }
 
-template <int VPT, bool SMALL, bool BAND>
+template <int VPT, bool SMALL, bool BAND, bool PM>
 int vp_launch_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
     switch (C) {
-        case 0: voice_program_kernel<VPT, SMALL, 0, BAND><<<nwg, 256, 0, s>>>(a); break;
-        case 1: voice_program_kernel<VPT, SMALL, 1, BAND><<<nwg, 256, 0, s>>>(a); break;
-        case 2: voice_program_kernel<VPT, SMALL, 2, BAND><<<nwg, 256, 0, s>>>(a); break;
+        case 0: voice_program_kernel<VPT, SMALL, 0, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
+        case 1: voice_program_kernel<VPT, SMALL, 1, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
+        case 2: voice_program_kernel<VPT, SMALL, 2, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
         default: return (int)hipErrorInvalidValue;
     }
     return sig_launch_status();
 }
 
 template <int VPT>
-int vp_launch_file(const VpArgs& a, bool small_file, bool band, int C, unsigned nwg, hipStream_t s) {
-    if (band) return small_file ? vp_launch_sink<VPT, true, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, true>(a, C, nwg, s);
-    return small_file ? vp_launch_sink<VPT, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, false>(a, C, nwg, s);
+int vp_launch_file(const VpArgs& a, bool small_file, bool band, bool pm, int C, unsigned nwg, hipStream_t s) {
+    if (pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);   // (never with a band: refused)
+    if (band) return small_file ? vp_launch_sink<VPT, true, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, true, false>(a, C, nwg, s);
+    return small_file ? vp_launch_sink<VPT, true, false, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, false>(a, C, nwg, s);
 }
 
 }  // namespace
@@ -933,14 +985,15 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false};
     bool has_adsr = false;
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_BAND && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCPM && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15);
         switch (x.op) {
             case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
+            case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
             case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
@@ -952,7 +1005,9 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         if (x.op == SIG_VP_AMP || x.op == SIG_VP_ADSR || x.op == SIG_VP_NOISE) need.ext = true;
         if (x.op == SIG_VP_ADSR) has_adsr = true;
         if (x.op == SIG_VP_BAND) need.band = true;
+        if (x.op == SIG_VP_OSCPM) need.pm = true;
     }
+    SIG_CHECK_ARG(!(need.band && need.pm));                                    // (no interpreter variant with both; the engine keeps such a graph per node)
     SIG_CHECK_ARG(vp_encode(P, a.code));
     a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
     for (int k = 0; k < P.n_oscs; ++k) {
@@ -1026,8 +1081,8 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         err = (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, small_file, need.band, bus_channels, (unsigned)nwg, s);
-    else err = vp_launch_file<1>(a, small_file, need.band, bus_channels, (unsigned)nwg, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, small_file, need.band, need.pm, bus_channels, (unsigned)nwg, s);
+    else err = vp_launch_file<1>(a, small_file, need.band, need.pm, bus_channels, (unsigned)nwg, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);

@@ -357,6 +357,8 @@ def _control_ports(node: Emitter) -> list:
     """ports a node reads with forward_at_block_rate"""
     if isinstance(node, osc.Osc):
         return [node.hertz, node.phase]
+    if isinstance(node, ext.PMOsc):
+        return [node.hertz, node.phase, node.index]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
@@ -380,6 +382,8 @@ def _audio_ports(node: Emitter) -> list:
         return [node.input]
     if isinstance(node, shape.Merge):
         return [node.left, node.right]
+    if isinstance(node, ext.PMOsc):
+        return [node.mod]
     return []
 
 
@@ -521,6 +525,9 @@ class _ControlProgram:
             got = self._filter(src)
         elif isinstance(src, fx.DoubleCritFilter):
             raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
+        elif isinstance(src, ext.PMOsc):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a phase-modulation oscillator has no block-rate program '
+                               f'(its modulator is a frame-rate input)')
         else:
             raise NotBatchable(f'no block-rate program for {src.cls_name()}')
         self._reg[src] = got
@@ -588,6 +595,9 @@ class _ControlProgram:
             ins = _native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, 1, None)
         elif isinstance(src, fx.CritFilter):
             raise NotBatchable('a filter whose input contains a filter, in a control path')
+        elif isinstance(src, ext.PMOsc):
+            raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
+                               f'window-rate program')
         else:
             raise NotBatchable(f'no window-rate program for {src.cls_name()} inside a control filter\'s input')
         got = self._window[src] = self._push(ins, cols)
@@ -723,6 +733,9 @@ class _Batch:
             result = torch.empty((rows, cols), dtype=CTRL_DTYPE, device=dev)
             o._launch(f'elementwise[{name},block-rate]', lambda: _native.elementwise(name, a, b, c, result),
                       units=rows * cols)
+        elif isinstance(src, ext.PMOsc):
+            raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a phase-modulation oscillator has no block-rate '
+                               f'schedule (its modulator is a frame-rate input)')
         else:
             raise NotBatchable(f'{what}: no block-rate schedule for {src.cls_name()}')
         self._ctl_memo[src] = result
@@ -764,6 +777,8 @@ class _Batch:
             self._require(node.right.sig, channels, hist)
         elif isinstance(node, (fx.Gain, fx.Amp)):
             self._require(node.left.sig, channels, hist)
+        elif isinstance(node, ext.PMOsc):
+            self._require(node.mod.sig, channels, hist)
         elif isinstance(node, ext.SumBus):
             self._require(node.input.sig, node.input.channels, hist)
         elif isinstance(node, (ext.MixMatrix, ext.Tap, files.FileWriter)):
@@ -848,6 +863,28 @@ class _Batch:
             start = self.pos - hist
             o._launch(f'osc_bank[{node.kind()}]',
                       lambda: _native.osc_bank(node.kind(), start, self.rate, hertz, phase, result),
+                      units=rows * voices)
+        return result
+
+    def _sched_pm(self, node, channels, hist, rows):
+        """a phase-modulation oscillator: one sig_osc_bank_pm launch over the modulator's rows"""
+        o = self.owner
+        hertz, phase, index = (self._control(p, p.name) for p in (node.hertz, node.phase, node.index))
+        mod = _modulated(node)
+        x = self._operand(node.mod, channels, 0 if mod else hist)  # a modulated node's history comes from its tail
+        _, voices = broadcast_shape((1, 1), *((1, t.shape[1]) for t in (hertz, phase, index, x)))
+        result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
+        if mod:
+            main = result[hist:]
+            o._launch(f'osc_bank_pm[{node.kind()},per-block]',
+                      lambda: _native.osc_bank_pm(node.kind(), self.pos, self.rate, hertz, phase, index, x, main,
+                                                  rows_per_param=self.N),
+                      units=main.shape[0] * voices)
+            self._own_history(node, voices, hist, result)
+        else:
+            start = self.pos - hist
+            o._launch(f'osc_bank_pm[{node.kind()}]',
+                      lambda: _native.osc_bank_pm(node.kind(), start, self.rate, hertz, phase, index, x, result),
                       units=rows * voices)
         return result
 
@@ -1163,6 +1200,7 @@ class _Batch:
     _SCHEDULES = (
         (fixed.Fixed, _sched_fixed),
         (osc.Osc, _sched_osc),
+        (ext.PMOsc, _sched_pm),
         (noise.White, _sched_noise),
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
@@ -1784,14 +1822,15 @@ class _ProgramRows:
 
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
-    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, in any arrangement in which every voice is computed from its own
+    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
     per-block rows (`_ProgramRows`).  The block history stays implicit: the launch re-walks the blocks in
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
-    KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White)
+    KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
+                    ext.PMOsc)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
@@ -1815,6 +1854,8 @@ class _VoiceProgram:
         self.depth = self._emit(top, 0)
         if len(self.code) > _native.VP_MAX_INS:
             raise _NoProgram('program too long')
+        if self.bands and any(op == 'OscPM' for op, *_ in self.code):
+            raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
 
     # ---- pass 1: readers of every node inside the graph
     def _count(self, n):
@@ -1893,6 +1934,12 @@ class _VoiceProgram:
             self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
             self.code.append(('Osc', _native.OSC_KINDS[n.kind()], len(self.oscs) - 1, 0, 0))
             depth = 0
+        elif isinstance(n, ext.PMOsc):
+            depth = self._emit(n.mod.sig, below)                               # the modulator's sample: in the accumulator
+            if len(self.oscs) >= _native.VP_MAX_OSCS:
+                raise _NoProgram('more oscillators than the machine has slots')
+            self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
+            self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], len(self.oscs) - 1, self._param(self._control(n.index, below)), 0))
         elif isinstance(n, noise.White):
             if len(self.seeds) >= 2 or n.channels != self.voices:
                 raise _NoProgram('White: two per program, as wide as the voices')
@@ -2089,7 +2136,9 @@ class _VoiceProgram:
         pull path, ~150 us per block).
         Band filters (two slots each): a swept one (an LFO on `low` / `high`) designs per block either way and takes the program
         under the same rule (tools/time_band.py); graphs whose bands all hold still keep the per-node schedule
-        they had before the program knew band filters, unless that schedule cannot batch them (short blocks behind a filter)."""
+        they had before the program knew band filters, unless that schedule cannot batch them (short blocks behind a filter).
+        Phase-modulation carriers (OscPM) take the program under the same rule: a two-operator voice under a bus runs at 0.54-0.55 T
+        interpreted against 0.22 T per node, 0.40-0.42 against 0.16-0.17 T behind a LowPass (tools/time_pm.py)."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
