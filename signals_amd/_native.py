@@ -23,20 +23,7 @@ STATUS_BAD_CUTOFF = 1
 ABI_VERSION = 7
 SINE_FAST_MAX_CYCLES = 2.0 ** 26     # sig_osc.h kSineFastMaxT: |t| up to which the fused Sine kernels advance the phase incrementally
 
-EXPORTS = ('sig_abi_version', 'sig_osc_bank', 'sig_osc_bank_mod', 'sig_biquad_coldstart', 'sig_elementwise', 'sig_sum_bus',
-           'sig_white_noise', 'sig_adsr', 'sig_mix_matrix', 'sig_fused_osc_biquad',
-           'sig_fused_voice_bus', 'sig_fused_voice_bus_workspace', 'sig_band_coldstart',
-           'sig_fused_osc_biquad_devpos', 'sig_advance_position', 'sig_adsr_apply', 'sig_biquad_coldstart_env',
-           'sig_fused_geometry', 'sig_biquad_coldstart_bus', 'sig_fused_osc_biquad_mix', 'sig_latency_voice_bus',
-           'sig_latency_voice_bus_workspace', 'sig_fused_voice_bus_prepared', 'sig_fused_voice_consts_size',
-           'sig_fused_voice_bus_plan', 'sig_fused_set_tuning', 'sig_fused_voice_bus_walk',
-           'sig_fused_cascade_bus', 'sig_fused_cascade_geometry', 'sig_fused_cascade_set_tuning',
-           'sig_fused_osc_biquad_rows', 'sig_fused_voice_bus_rows', 'sig_fused_osc_pair_biquad', 'sig_fused_voice_pair_bus',
-           'sig_fused_osc_biquad_fm', 'sig_fused_voice_bus_fm', 'sig_control_program',
-           'sig_voice_program', 'sig_voice_program_set_tuning', 'sig_voice_program_geometry', 'sig_voice_program_args_size',
-           'sig_voice_program_attach', 'sig_voice_program_detach_all', 'sig_voice_program_use_attached',
-           'sig_control_program_attach', 'sig_control_program_attached', 'sig_fused_voice_bus_bound', 'sig_band_coldstart_blocks',
-           'sig_control_program_windowed', 'sig_osc_bank_pm')
+ADSR_PARAMS = ('attack', 'decay', 'sustain', 'release', 'gate_on', 'gate_off')
 
 
 class NativeError(RuntimeError):
@@ -92,6 +79,79 @@ class Operand(ctypes.Structure):
                 ('row_div', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+def _argtypes() -> dict:
+    """symbol -> argument types of every entry point of include/signals_amd.h"""
+    cint, i32, i64, u64, vp, dp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p
+    p32, operand = ctypes.POINTER(i32), ctypes.POINTER(Operand)
+    fused = [cint, cint, i32, i64, i32, i32, i32, i32]       # kinds, rate, position, block_frames, nblocks, context, voices
+    cold = [cint, i32, i64, i32, i32, i32, i32]              # type, rate, position, block_frames, nblocks, context, voices
+    rows4 = [dp, i32] * 4                                    # hertz, phase, cutoff, gain: (pointer, stride) each
+    params = [dp, i32, i32] * 2                              # cutoff, gain: (pointer, stride, rows) each
+    env = [ctypes.POINTER(vp), p32]                          # the ADSR rows: six pointers, six strides
+    window = [vp, i64, i64]                                  # input, its leading dimension, history rows
+    bus = [dp, i64, i32, vp]                                 # bus gains, their leading dimension, bus channels, workspace
+    out = [vp, i64, vp, vp]                                  # out, its leading dimension, status, stream
+    program = [i32, i64, i32, i32, i32, i64, i64, vp, i32, vp, i32, vp]
+    return {
+        'sig_abi_version': [],
+        'sig_osc_bank': [cint, i64, i32, i64, i32, dp, i32, dp, i32, vp, i32, i64, vp],
+        'sig_osc_bank_mod': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, vp, i32, i64, vp],
+        'sig_osc_bank_pm': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
+                            vp, i32, i64, i32, vp, i32, i64, vp],
+        'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
+        'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
+        'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
+        'sig_band_coldstart': cold + [dp, i32, dp, i32] + window + [vp, i64, i32, vp, vp],
+        'sig_band_coldstart_blocks': cold + [dp, i32, dp, i32, i32] + window + [vp, i64, i32, vp, vp],
+        'sig_elementwise': [cint, i64, i32, operand, operand, operand, vp, i64, i32, vp],
+        'sig_sum_bus': [i64, i32, vp, i64, i32, dp, i64, i32, vp, i64, i32, vp],
+        'sig_white_noise': [u64, i64, i64, i32, vp, i32, i64, vp],
+        'sig_adsr': [i64, i32, i64, i32] + env + [vp, i32, i64, vp],
+        'sig_adsr_apply': [i64, i32, i64, i32] + env + [vp, i64, vp, i64, vp],
+        'sig_mix_matrix': [i64, i32, vp, i64, vp, vp, i64, vp],
+        'sig_advance_position': [vp, i64, vp],
+        'sig_fused_osc_biquad': fused + rows4 + out,
+        'sig_fused_osc_biquad_devpos': [cint, cint, i32, vp, i32, i32, i32, i32] + rows4 + out,
+        'sig_fused_osc_biquad_mix': fused + rows4 + [vp] + out,
+        'sig_fused_osc_biquad_rows': fused + [dp, i32] * 2 + params + out,
+        'sig_fused_osc_biquad_fm': fused + [dp, i32, i32, dp] * 2 + params + out,
+        'sig_fused_osc_pair_biquad': [cint, cint] + fused + [dp, i32] * 5 + params + out,
+        'sig_fused_voice_bus': fused + rows4 + bus + out,
+        'sig_fused_voice_bus_walk': fused + rows4 + bus + out,
+        'sig_fused_voice_bus_prepared': fused + rows4 + bus + out + [vp, i32],
+        'sig_fused_voice_bus_bound': [vp, i64, vp, i32, i32, vp],
+        'sig_fused_voice_bus_rows': fused + [dp, i32] * 2 + params + bus + out,
+        'sig_fused_voice_bus_fm': fused + [dp, i32, i32, dp] * 2 + params + bus + out,
+        'sig_fused_voice_pair_bus': [cint, cint] + fused + [dp, i32] * 5 + params + bus + out,
+        'sig_fused_voice_bus_workspace': [i32, i64, i32],
+        'sig_fused_voice_consts_size': [i32],
+        'sig_fused_voice_bus_plan': [cint, i64, i32, i32, i32, i32, p32, p32, p32],
+        'sig_fused_geometry': [i32, i32, i32, i32, p32, p32],
+        'sig_fused_set_tuning': [i32, i32, i32, i32],
+        'sig_fused_cascade_bus': [cint, cint, cint, i32, i64, i64, i32, i32, i32, i32] + [dp, i32] * 5 + env + bus + out,
+        'sig_fused_cascade_geometry': [i32, i32, p32, p32],
+        'sig_fused_cascade_set_tuning': [i32, i32],
+        'sig_latency_voice_bus': [cint, i32, i64, vp, i32, i32, i32] + rows4 + bus + out,
+        'sig_latency_voice_bus_workspace': [i32, i32, i32],
+        'sig_control_program': program,
+        'sig_control_program_windowed': program,
+        'sig_control_program_attach': [p32, i32, ctypes.c_char_p, p32],
+        'sig_control_program_attached': [i32] + program,
+        'sig_voice_program': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out,
+        'sig_voice_program_set_tuning': [i32, i32],
+        'sig_voice_program_geometry': [i32, i32, i32, i32, i32, i32, i32, i32, p32, p32],
+        'sig_voice_program_args_size': [],
+        'sig_voice_program_attach': [ctypes.POINTER(VoiceProgramT), i32, i32, ctypes.c_char_p],
+        'sig_voice_program_detach_all': [],
+        'sig_voice_program_use_attached': [i32],
+    }
+
+
+_ARGTYPES = _argtypes()
+_RETURNS_INT64 = ('sig_fused_voice_bus_workspace', 'sig_fused_voice_consts_size', 'sig_latency_voice_bus_workspace',
+                  'sig_voice_program_args_size')                 # sizes in bytes; every other entry point returns an int (a hipError_t)
+EXPORTS = tuple(_ARGTYPES)
+
 _lib = None
 
 
@@ -102,136 +162,10 @@ def lib() -> ctypes.CDLL:
             raise NativeError(f'{LIB_PATH} not built: run `python -c "import __graft_entry__ as g; g.build()"` '
                               f'(signals_amd/csrc/build.sh).  There is no CPU fallback.')
         L = ctypes.CDLL(str(LIB_PATH))
-        i32, i64, vp, dp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p
-        L.sig_abi_version.restype = ctypes.c_int
-        L.sig_abi_version.argtypes = []
-        L.sig_osc_bank.restype = ctypes.c_int
-        L.sig_osc_bank.argtypes = [ctypes.c_int, i64, i32, i64, i32, dp, i32, dp, i32, vp, i32, i64, vp]
-        L.sig_biquad_coldstart.restype = ctypes.c_int
-        L.sig_biquad_coldstart.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, i32,
-                                           vp, i64, i64, vp, i64, i32, vp, vp]
-        L.sig_band_coldstart_blocks.restype = ctypes.c_int
-        L.sig_band_coldstart_blocks.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, dp, i32, i32,
-                                                vp, i64, i64, vp, i64, i32, vp, vp]
-        L.sig_elementwise.restype = ctypes.c_int
-        L.sig_elementwise.argtypes = [ctypes.c_int, i64, i32, ctypes.POINTER(Operand), ctypes.POINTER(Operand),
-                                      ctypes.POINTER(Operand), vp, i64, i32, vp]
-        L.sig_sum_bus.restype = ctypes.c_int
-        L.sig_sum_bus.argtypes = [i64, i32, vp, i64, i32, dp, i64, i32, vp, i64, i32, vp]
-        L.sig_white_noise.restype = ctypes.c_int
-        L.sig_white_noise.argtypes = [ctypes.c_uint64, i64, i64, i32, vp, i32, i64, vp]
-        L.sig_adsr.restype = ctypes.c_int
-        L.sig_adsr.argtypes = [i64, i32, i64, i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32),
-                               vp, i32, i64, vp]
-        L.sig_mix_matrix.restype = ctypes.c_int
-        L.sig_mix_matrix.argtypes = [i64, i32, vp, i64, vp, vp, i64, vp]
-        L.sig_fused_osc_biquad.restype = ctypes.c_int
-        L.sig_fused_osc_biquad.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                           dp, i32, dp, i32, dp, i32, dp, i32, vp, i64, vp, vp]
-        L.sig_fused_voice_bus_workspace.restype = ctypes.c_int64
-        L.sig_fused_voice_bus_workspace.argtypes = [i32, i64, i32]
-        L.sig_fused_voice_bus.restype = ctypes.c_int
-        L.sig_fused_voice_bus.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                          dp, i32, dp, i32, dp, i32, dp, i32, dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_voice_bus_walk.restype = ctypes.c_int
-        L.sig_fused_voice_bus_walk.argtypes = L.sig_fused_voice_bus.argtypes
-        L.sig_fused_voice_consts_size.restype = ctypes.c_int64
-        L.sig_fused_voice_consts_size.argtypes = [i32]
-        L.sig_fused_voice_bus_prepared.restype = ctypes.c_int
-        L.sig_fused_voice_bus_prepared.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                                   dp, i32, dp, i32, dp, i32, dp, i32, dp, i64, i32, vp, vp, i64, vp, vp, vp, i32]
-        L.sig_band_coldstart.restype = ctypes.c_int
-        L.sig_band_coldstart.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, dp, i32,
-                                         vp, i64, i64, vp, i64, i32, vp, vp]
-        L.sig_osc_bank_mod.restype = ctypes.c_int
-        L.sig_osc_bank_mod.argtypes = [ctypes.c_int, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, vp, i32, i64, vp]
-        L.sig_osc_bank_pm.restype = ctypes.c_int
-        L.sig_osc_bank_pm.argtypes = [ctypes.c_int, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
-                                      vp, i32, i64, i32, vp, i32, i64, vp]
-        L.sig_fused_osc_biquad_devpos.restype = ctypes.c_int
-        L.sig_fused_osc_biquad_devpos.argtypes = [ctypes.c_int, ctypes.c_int, i32, vp, i32, i32, i32, i32,
-                                                  dp, i32, dp, i32, dp, i32, dp, i32, vp, i64, vp, vp]
-        L.sig_adsr_apply.restype = ctypes.c_int
-        L.sig_adsr_apply.argtypes = [i64, i32, i64, i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32),
-                                     vp, i64, vp, i64, vp]
-        L.sig_biquad_coldstart_env.restype = ctypes.c_int
-        L.sig_biquad_coldstart_env.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, i32,
-                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32),
-                                               vp, i64, i64, vp, i64, vp, vp]
-        L.sig_advance_position.restype = ctypes.c_int
-        L.sig_advance_position.argtypes = [vp, i64, vp]
-        L.sig_biquad_coldstart_bus.restype = ctypes.c_int
-        L.sig_biquad_coldstart_bus.argtypes = [ctypes.c_int, i32, i64, i32, i32, i32, i32, dp, i32, i32,
-                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32),
-                                               vp, i64, i64, vp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_osc_biquad_mix.restype = ctypes.c_int
-        L.sig_fused_osc_biquad_mix.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                               dp, i32, dp, i32, dp, i32, dp, i32, vp, vp, i64, vp, vp]
-        L.sig_latency_voice_bus_workspace.restype = ctypes.c_int64
-        L.sig_latency_voice_bus_workspace.argtypes = [i32, i32, i32]
-        L.sig_latency_voice_bus.restype = ctypes.c_int
-        L.sig_latency_voice_bus.argtypes = [ctypes.c_int, i32, i64, vp, i32, i32, i32, dp, i32, dp, i32, dp, i32, dp, i32,
-                                            dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_geometry.restype = ctypes.c_int
-        L.sig_fused_geometry.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
-        L.sig_fused_cascade_bus.restype = ctypes.c_int
-        L.sig_fused_cascade_bus.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32, i64, i64, i32, i32, i32, i32,
-                                            dp, i32, dp, i32, dp, i32, dp, i32, dp, i32,
-                                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32),
-                                            dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_cascade_geometry.restype = ctypes.c_int
-        L.sig_fused_cascade_geometry.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
-        L.sig_fused_osc_biquad_rows.restype = ctypes.c_int
-        L.sig_fused_osc_biquad_rows.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                                dp, i32, dp, i32, dp, i32, i32, dp, i32, i32, vp, i64, vp, vp]
-        L.sig_fused_voice_bus_rows.restype = ctypes.c_int
-        L.sig_fused_voice_bus_rows.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                               dp, i32, dp, i32, dp, i32, i32, dp, i32, i32, dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_osc_biquad_fm.restype = ctypes.c_int
-        L.sig_fused_osc_biquad_fm.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                              dp, i32, i32, dp, dp, i32, i32, dp, dp, i32, i32, dp, i32, i32, vp, i64, vp, vp]
-        L.sig_fused_voice_bus_fm.restype = ctypes.c_int
-        L.sig_fused_voice_bus_fm.argtypes = [ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                             dp, i32, i32, dp, dp, i32, i32, dp, dp, i32, i32, dp, i32, i32, dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_control_program.restype = ctypes.c_int
-        L.sig_control_program.argtypes = [i32, i64, i32, i32, i32, i64, i64, vp, i32, vp, i32, vp]
-        L.sig_control_program_windowed.restype = ctypes.c_int
-        L.sig_control_program_windowed.argtypes = L.sig_control_program.argtypes
-        L.sig_control_program_attach.restype = ctypes.c_int
-        L.sig_control_program_attach.argtypes = [ctypes.POINTER(i32), i32, ctypes.c_char_p, ctypes.POINTER(i32)]
-        L.sig_control_program_attached.restype = ctypes.c_int
-        L.sig_control_program_attached.argtypes = [i32, i32, i64, i32, i32, i32, i64, i64, vp, i32, vp, i32, vp]
-        L.sig_fused_voice_bus_bound.restype = ctypes.c_int
-        L.sig_fused_voice_bus_bound.argtypes = [vp, i64, vp, i32, i32, vp]
-        L.sig_voice_program.restype = ctypes.c_int
-        L.sig_voice_program.argtypes = [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), i32,
-                                        dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_voice_program_set_tuning.restype = ctypes.c_int
-        L.sig_voice_program_set_tuning.argtypes = [i32, i32]
-        L.sig_voice_program_geometry.restype = ctypes.c_int
-        L.sig_voice_program_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-        L.sig_voice_program_args_size.restype = ctypes.c_int64
-        L.sig_voice_program_args_size.argtypes = []
-        L.sig_voice_program_attach.restype = ctypes.c_int
-        L.sig_voice_program_attach.argtypes = [ctypes.POINTER(VoiceProgramT), i32, i32, ctypes.c_char_p]
-        L.sig_voice_program_detach_all.restype = ctypes.c_int
-        L.sig_voice_program_detach_all.argtypes = []
-        L.sig_voice_program_use_attached.restype = ctypes.c_int
-        L.sig_voice_program_use_attached.argtypes = [i32]
-        L.sig_fused_osc_pair_biquad.restype = ctypes.c_int
-        L.sig_fused_osc_pair_biquad.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                                dp, i32, dp, i32, dp, i32, dp, i32, dp, i32,
-                                                dp, i32, i32, dp, i32, i32, vp, i64, vp, vp]
-        L.sig_fused_voice_pair_bus.restype = ctypes.c_int
-        L.sig_fused_voice_pair_bus.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, i32, i64, i32, i32, i32, i32,
-                                               dp, i32, dp, i32, dp, i32, dp, i32, dp, i32,
-                                               dp, i32, i32, dp, i32, i32, dp, i64, i32, vp, vp, i64, vp, vp]
-        L.sig_fused_cascade_set_tuning.restype = ctypes.c_int
-        L.sig_fused_cascade_set_tuning.argtypes = [i32, i32]
-        L.sig_fused_voice_bus_plan.restype = ctypes.c_int
-        L.sig_fused_voice_bus_plan.argtypes = [ctypes.c_int, i64, i32, i32, i32, i32] + [ctypes.POINTER(ctypes.c_int32)] * 3
-        L.sig_fused_set_tuning.restype = ctypes.c_int
-        L.sig_fused_set_tuning.argtypes = [i32, i32, i32, i32]
+        for name, argtypes in _ARGTYPES.items():
+            entry = getattr(L, name)
+            entry.restype = ctypes.c_int64 if name in _RETURNS_INT64 else ctypes.c_int
+            entry.argtypes = argtypes
         if L.sig_abi_version() != ABI_VERSION:
             raise NativeError('libsignals_amd.so ABI version mismatch')
         _lib = L
@@ -298,6 +232,79 @@ def _ctrl_rows(t: torch.Tensor | None, what: str):
     return t.data_ptr(), (0 if t.shape[1] == 1 else 1), (0 if t.shape[0] == 1 else t.stride(0)), t.shape[0]
 
 
+def _ptr(t: torch.Tensor | None):
+    """the data pointer of an optional tensor"""
+    return None if t is None else t.data_ptr()
+
+
+def _voice_rows(voices: int, *pairs, form=_ctrl_row) -> list:
+    """the flat (ptr, stride, ...) list of per-voice control rows given as (tensor | None, name) pairs, each one column or
+    `voices` wide; `form`: `_ctrl_row`, or `_ctrl_rows` for (ptr, col_stride, row_stride, rows) each"""
+    flat = []
+    for row, name in pairs:
+        if row is not None and row.shape[1] not in (1, voices):
+            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
+        flat.extend(form(row, name))
+    return flat
+
+
+def _bus_gains(gains: torch.Tensor | None, bus: int, voices: int):
+    """(ptr, leading dimension) of the (C, V) bus gains"""
+    if gains is None:
+        if bus != 1:
+            raise NativeError('a bus without gains is mono')
+        return None, 0
+    if gains.dtype != torch.float64 or gains.shape != (bus, voices) or gains.stride(1) != 1:
+        raise NativeError(f'bus gains must be float64 ({bus},{voices}), got {tuple(gains.shape)} {gains.dtype}')
+    return gains.data_ptr(), gains.stride(0)
+
+
+def _envelope(rows: dict | None, voices: int, into: tuple | None = None):
+    """(pointers, strides) of the six ADSR control rows (name -> (1,V)|(1,1) f64), or (None, None) without an envelope;
+    `into`: the two arrays of six to fill instead of new ones"""
+    if rows is None:
+        return None, None
+    ptrs, strides = into or ((ctypes.c_void_p * 6)(), (ctypes.c_int32 * 6)())
+    flat = _voice_rows(voices, *((rows[name], name) for name in ADSR_PARAMS))
+    for i in range(6):
+        ptrs[i], strides[i] = flat[2 * i], flat[2 * i + 1]
+    return ptrs, strides
+
+
+def _bus_workspace(workspace: torch.Tensor | None, voices: int, rows: int, bus: int, device=None) -> torch.Tensor:
+    """the float64 scratch of the fused bus kernels: `workspace` where it is large enough, else a new one on `device`
+    (without a device: an error -- a bound call keeps the caller's)"""
+    need = lib().sig_fused_voice_bus_workspace(voices, rows, bus)
+    fits = workspace is not None and workspace.numel() * workspace.element_size() >= need
+    if device is None and not (fits and workspace.dtype == torch.float64):
+        raise NativeError('fused bus workspace too small')
+    return workspace if fits else torch.empty(need // 8, dtype=torch.float64, device=device)
+
+
+def _history_input(buf: torch.Tensor, history: int, voices: int, out: torch.Tensor, block_frames: int, nblocks: int, what: str) -> int:
+    """the pointer to row `history` of a cold-start filter's input, `voices` wide: `history` context rows, then one row per
+    row of `out`"""
+    rows = out.shape[0]
+    if rows != block_frames * nblocks or buf.shape[0] != history + rows or buf.shape[1] != voices or buf.dtype != out.dtype:
+        raise NativeError(f'{what} shapes: in {tuple(buf.shape)} {buf.dtype} history {history} out {tuple(out.shape)} {out.dtype} '
+                          f'blocks {nblocks}x{block_frames}')
+    return buf.data_ptr() + history * buf.stride(0) * buf.element_size()
+
+
+def _parameter_rows(rows: int, rows_per_param: int, *counts) -> int:
+    """`rows_per_param` as the oscillator launches take it (0: one parameter row for all), checked against the (rows, name) of
+    every parameter"""
+    if max(n for n, _ in counts) == 1:
+        return 0
+    if rows_per_param < 1:
+        raise NativeError('per-block oscillator parameters need rows_per_param')
+    need = (rows + rows_per_param - 1) // rows_per_param
+    for n, name in counts:
+        if n not in (1, need):
+            raise NativeError(f'{name} has {n} parameter rows, launch needs 1 or {need}')
+    return rows_per_param
+
+
 def osc_bank(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None,
              out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
     """out[(rows, voices)] <- oscillator `kind`; row r is absolute frame `position + r*step`.
@@ -305,24 +312,12 @@ def osc_bank(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: to
     _gpu(hertz, phase, out)
     _audio(out, 'osc out')
     rows, voices = out.shape
-    hp, hs, hrs, hrows = _ctrl_rows(hertz, 'hertz')
-    pp, ps, prs, prows = _ctrl_rows(phase, 'phase')
-    for row, name in ((hertz, 'hertz'), (phase, 'phase')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
+    hp, hs, hrs, hrows, pp, ps, prs, prows = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), form=_ctrl_rows)
     if step == 1 and hrows == 1 and prows == 1:
         _check(lib().sig_osc_bank(OSC_KINDS[kind], position, rate, rows, voices, hp, hs, pp, ps,
                                   out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank')
         return out
-    if max(hrows, prows) > 1:
-        if rows_per_param < 1:
-            raise NativeError('per-block oscillator parameters need rows_per_param')
-        need = (rows + rows_per_param - 1) // rows_per_param
-        for n, name in ((hrows, 'hertz'), (prows, 'phase')):
-            if n not in (1, need):
-                raise NativeError(f'{name} has {n} parameter rows, launch needs 1 or {need}')
-    else:
-        rows_per_param = 0
+    rows_per_param = _parameter_rows(rows, rows_per_param, (hrows, 'hertz'), (prows, 'phase'))
     _check(lib().sig_osc_bank_mod(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
                                   hp, hs, hrs, pp, ps, prs, out.data_ptr(), _dt(out), out.stride(0), _stream(out)),
            'sig_osc_bank_mod')
@@ -337,21 +332,8 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
     _gpu(hertz, phase, index, mod, out)
     _audio(out, 'osc out')
     rows, voices = out.shape
-    hp, hs, hrs, hrows = _ctrl_rows(hertz, 'hertz')
-    pp, ps, prs, prows = _ctrl_rows(phase, 'phase')
-    ip, is_, irs, irows = _ctrl_rows(index, 'index')
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (index, 'index')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-    if max(hrows, prows, irows) > 1:
-        if rows_per_param < 1:
-            raise NativeError('per-block oscillator parameters need rows_per_param')
-        need = (rows + rows_per_param - 1) // rows_per_param
-        for n, name in ((hrows, 'hertz'), (prows, 'phase'), (irows, 'index')):
-            if n not in (1, need):
-                raise NativeError(f'{name} has {n} parameter rows, launch needs 1 or {need}')
-    else:
-        rows_per_param = 0
+    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (index, 'index'), form=_ctrl_rows)
+    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'index'))
     mp, mdt, mld, mcs = None, F32, 0, 0
     if mod is not None:
         _audio(mod, 'modulator')
@@ -360,7 +342,7 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
         mp, mdt = mod.data_ptr(), _dt(mod)
         mld, mcs = (0 if mod.shape[0] == 1 else mod.stride(0)), (0 if mod.shape[1] == 1 else 1)
     _check(lib().sig_osc_bank_pm(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
-                                 hp, hs, hrs, pp, ps, prs, ip, is_, irs, mp, mdt, mld, mcs,
+                                 *params[0:3], *params[4:7], *params[8:11], mp, mdt, mld, mcs,
                                  out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_pm')
     return out
 
@@ -375,12 +357,8 @@ def biquad_coldstart(btype: str, rate: int, position: int, block_frames: int, nb
     _gpu(cutoff, buf, out, status, *(envelope or {}).values())
     _audio(buf, 'biquad in')
     _audio(out, 'biquad out')
-    rows, voices = out.shape
-    if rows != block_frames * nblocks or buf.shape[0] != history + rows or buf.shape[1] != voices:
-        raise NativeError(f'biquad shapes: in {tuple(buf.shape)} history {history} out {tuple(out.shape)} '
-                          f'blocks {nblocks}x{block_frames}')
-    if buf.dtype != out.dtype:
-        raise NativeError('biquad in/out dtype differ')
+    voices = out.shape[1]
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
     if cutoff.dtype != torch.float64 or cutoff.dim() != 2 or not cutoff.is_contiguous():
         raise NativeError('cutoff must be a contiguous float64 2-D tensor')
     if cutoff.shape[0] not in (1, nblocks) or cutoff.shape[1] not in (1, voices):
@@ -388,27 +366,17 @@ def biquad_coldstart(btype: str, rate: int, position: int, block_frames: int, nb
     if cutoff.shape[1] != voices and voices != 1:
         # the reference indexes crit[0, i] for every channel i (fx.py:99)
         raise IndexError(f'index {cutoff.shape[1]} is out of bounds for axis 1 with size {cutoff.shape[1]}')
-    in_ptr = buf.data_ptr() + history * buf.stride(0) * buf.element_size()
+    head = (FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
+            cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0])
     if envelope is not None:
         if out.dtype != torch.float32:
             raise NativeError('the envelope epilogue is float32 only')
-        ptrs = (ctypes.c_void_p * 6)()
-        strides = (ctypes.c_int32 * 6)()
-        for i, name in enumerate(ADSR_PARAMS):
-            ptrs[i], strides[i] = _ctrl_row(envelope[name], name)
-            if envelope[name].shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {envelope[name].shape[1]} channels for {voices} voices')
-        _check(lib().sig_biquad_coldstart_env(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                              cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0],
-                                              ptrs, strides, in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0),
-                                              status.data_ptr() if status is not None else None, _stream(out)),
+        _check(lib().sig_biquad_coldstart_env(*head, *_envelope(envelope, voices), in_ptr, buf.stride(0), history,
+                                              out.data_ptr(), out.stride(0), _ptr(status), _stream(out)),
                'sig_biquad_coldstart_env')
         return out
-    _check(lib().sig_biquad_coldstart(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                      cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0],
-                                      in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
-                                      status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_biquad_coldstart')
+    _check(lib().sig_biquad_coldstart(*head, in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
+                                      _ptr(status), _stream(out)), 'sig_biquad_coldstart')
     return out
 
 
@@ -468,20 +436,11 @@ def white_noise(seed: int, position: int, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
-ADSR_PARAMS = ('attack', 'decay', 'sustain', 'release', 'gate_on', 'gate_off')
-
-
 def adsr(position: int, rate: int, rows: dict, out: torch.Tensor) -> torch.Tensor:
     """rows: name -> f64 control row (1,V)|(1,1) for each of ADSR_PARAMS"""
     _gpu(out, *rows.values())
     _audio(out, 'adsr out')
-    ptrs = (ctypes.c_void_p * 6)()
-    strides = (ctypes.c_int32 * 6)()
-    for i, name in enumerate(ADSR_PARAMS):
-        ptrs[i], strides[i] = _ctrl_row(rows[name], name)
-        if rows[name].shape[1] not in (1, out.shape[1]):
-            raise NativeError(f'{name} has {rows[name].shape[1]} channels for {out.shape[1]} voices')
-    _check(lib().sig_adsr(position, rate, out.shape[0], out.shape[1], ptrs, strides, out.data_ptr(), _dt(out),
+    _check(lib().sig_adsr(position, rate, out.shape[0], out.shape[1], *_envelope(rows, out.shape[1]), out.data_ptr(), _dt(out),
                           out.stride(0), _stream(out)), 'sig_adsr')
     return out
 
@@ -509,24 +468,20 @@ def fused_osc_biquad(kind: str, btype: str, rate: int, position, block_frames: i
     rows, voices = out.shape
     if out.dtype != torch.float32 or rows != block_frames * nblocks:
         raise NativeError(f'fused out must be float32 ({block_frames * nblocks}, V), got {tuple(out.shape)} {out.dtype}')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
+    ptrs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain'))
+    entry, name = lib().sig_fused_osc_biquad, 'sig_fused_osc_biquad'
     if isinstance(position, torch.Tensor):
-        if position.dtype != torch.int64 or position.numel() != 1 or not position.is_cuda:
-            raise NativeError('device position must be a one-element int64 GPU tensor')
-        _check(lib().sig_fused_osc_biquad_devpos(OSC_KINDS[kind], FILT_TYPES[btype], rate, position.data_ptr(), block_frames,
-                                                 nblocks, context, voices, *ptrs, out.data_ptr(), out.stride(0),
-                                                 status.data_ptr() if status is not None else None, _stream(out)),
-               'sig_fused_osc_biquad_devpos')
-        return out
-    _check(lib().sig_fused_osc_biquad(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context,
-                                      voices, *ptrs, out.data_ptr(), out.stride(0),
-                                      status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_fused_osc_biquad')
+        entry, name, position = lib().sig_fused_osc_biquad_devpos, 'sig_fused_osc_biquad_devpos', _device_position(position)
+    _check(entry(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices, *ptrs,
+                 out.data_ptr(), out.stride(0), _ptr(status), _stream(out)), name)
     return out
+
+
+def _device_position(position: torch.Tensor) -> int:
+    """the pointer of a frame position the kernel reads on the device"""
+    if position.dtype != torch.int64 or position.numel() != 1 or not position.is_cuda:
+        raise NativeError('device position must be a one-element int64 GPU tensor')
+    return position.data_ptr()
 
 
 def biquad_coldstart_bus(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
@@ -540,35 +495,18 @@ def biquad_coldstart_bus(btype: str, rate: int, position: int, block_frames: int
     _audio(out, 'biquad bus out')
     rows, bus = out.shape
     voices = buf.shape[1]
-    if out.dtype != torch.float32 or buf.dtype != torch.float32 or rows != block_frames * nblocks or buf.shape[0] != history + rows:
-        raise NativeError(f'biquad bus shapes: in {tuple(buf.shape)} {buf.dtype} history {history} out {tuple(out.shape)} {out.dtype}')
+    if out.dtype != torch.float32:
+        raise NativeError(f'biquad bus out must be float32, got {out.dtype}')
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad bus')
     if cutoff.dtype != torch.float64 or cutoff.shape[1] not in (1, voices) or cutoff.shape[0] not in (1, nblocks) \
             or not cutoff.is_contiguous():
         raise NativeError(f'cutoff must be contiguous float64 (1|{nblocks}, 1|{voices}), got {tuple(cutoff.shape)} {cutoff.dtype}')
-    gp, gld = None, 0
-    if bus_gains is not None:
-        if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus, voices) or bus_gains.stride(1) != 1:
-            raise NativeError(f'bus gains must be float64 ({bus},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-        gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-    elif bus != 1:
-        raise NativeError('a bus without gains is mono')
-    ptrs = strides = None
-    if envelope is not None:
-        ptrs = (ctypes.c_void_p * 6)()
-        strides = (ctypes.c_int32 * 6)()
-        for i, name in enumerate(ADSR_PARAMS):
-            ptrs[i], strides[i] = _ctrl_row(envelope[name], name)
-            if envelope[name].shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {envelope[name].shape[1]} channels for {voices} voices')
-    need = lib().sig_fused_voice_bus_workspace(voices, rows, bus)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
-    in_ptr = buf.data_ptr() + history * buf.stride(0) * buf.element_size()
+    workspace = _bus_workspace(workspace, voices, rows, bus, out.device)
     _check(lib().sig_biquad_coldstart_bus(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
                                           cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0],
-                                          ptrs, strides, in_ptr, buf.stride(0), history, gp, gld, bus,
-                                          workspace.data_ptr(), out.data_ptr(), out.stride(0),
-                                          status.data_ptr() if status is not None else None, _stream(out)),
+                                          *_envelope(envelope, voices), in_ptr, buf.stride(0), history,
+                                          *_bus_gains(bus_gains, bus, voices), bus, workspace.data_ptr(),
+                                          out.data_ptr(), out.stride(0), _ptr(status), _stream(out)),
            'sig_biquad_coldstart_bus')
     return out
 
@@ -585,34 +523,17 @@ def latency_voice_bus(btype: str, rate: int, position, block_frames: int, contex
                       status: torch.Tensor | None = None) -> torch.Tensor:
     """out (block_frames, C) f32 <- one block of sum over voices of pan * [gain *] Filter(Sine), in one launch.
     `position`: an int, or a one-element int64 device tensor that the launch reads AND advances by block_frames."""
-    _gpu(hertz, phase, cutoff, gain, bus_gains, out, workspace, status)
+    _gpu(out)
     _audio(out, 'latency bus out')
     rows, bus = out.shape
     if out.dtype != torch.float32 or rows != block_frames:
         raise NativeError(f'latency bus out must be float32 ({block_frames}, C), got {tuple(out.shape)} {out.dtype}')
-    need = lib().sig_latency_voice_bus_workspace(voices, block_frames, bus)
-    if workspace.dtype != torch.float64 or workspace.numel() * 8 < need:
-        raise NativeError(f'latency workspace needs {need} bytes of float64 (latency_voice_bus_workspace)')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
-    gp, gld = None, 0
-    if bus_gains is not None:
-        if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus, voices) or bus_gains.stride(1) != 1:
-            raise NativeError(f'bus gains must be float64 ({bus},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-        gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-    elif bus != 1:
-        raise NativeError('a bus without gains is mono')
+    call = LatencyVoiceBusCall(btype, rate, block_frames, context, voices, hertz, phase, cutoff, gain, bus_gains, bus, workspace,
+                               status)
     pos_int, pos_dev = position, None
     if isinstance(position, torch.Tensor):
-        if position.dtype != torch.int64 or position.numel() != 1 or not position.is_cuda:
-            raise NativeError('device position must be a one-element int64 GPU tensor')
-        pos_int, pos_dev = 0, position.data_ptr()
-    _check(lib().sig_latency_voice_bus(FILT_TYPES[btype], rate, pos_int, pos_dev, block_frames, context, voices, *ptrs,
-                                       gp, gld, bus, workspace.data_ptr(), out.data_ptr(), out.stride(0),
-                                       status.data_ptr() if status is not None else None, _stream(out)),
+        pos_int, pos_dev = 0, _device_position(position)
+    _check(call._fn(*call._head, pos_int, pos_dev, *call._mid, out.data_ptr(), out.stride(0), call._status, _stream(out)),
            'sig_latency_voice_bus')
     return out
 
@@ -629,23 +550,13 @@ class LatencyVoiceBusCall:
         need = lib().sig_latency_voice_bus_workspace(voices, block_frames, bus_channels)
         if workspace.dtype != torch.float64 or workspace.numel() * 8 < need:
             raise NativeError(f'latency workspace needs {need} bytes of float64 (latency_voice_bus_workspace)')
-        ptrs = []
-        for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-            if row is not None and row.shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-            ptrs.extend(_ctrl_row(row, name))
-        gp, gld = None, 0
-        if bus_gains is not None:
-            if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus_channels, voices) or bus_gains.stride(1) != 1:
-                raise NativeError(f'bus gains must be float64 ({bus_channels},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-            gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-        elif bus_channels != 1:
-            raise NativeError('a bus without gains is mono')
+        ptrs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain'))
+        gp, gld = _bus_gains(bus_gains, bus_channels, voices)
         self._keep = (hertz, phase, cutoff, gain, bus_gains, workspace, status)
         self._fn = lib().sig_latency_voice_bus
         self._head = (FILT_TYPES[btype], rate)
         self._mid = (block_frames, context, voices, *ptrs, gp, gld, bus_channels, workspace.data_ptr())
-        self._status = status.data_ptr() if status is not None else None
+        self._status = _ptr(status)
         self.shape = (block_frames, bus_channels)
         self.device = workspace.device
 
@@ -678,34 +589,15 @@ class FusedVoiceBusCall:
                  consts: torch.Tensor):
         _gpu(hertz, phase, cutoff, gain, bus_gains, workspace, status, consts)
         rows = block_frames * nblocks
-        ptrs = []
-        for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-            if row is not None and row.shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-            ptrs.extend(_ctrl_row(row, name))
-        gp, gld = None, 0
-        if bus_gains is not None:
-            if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus_channels, voices) or bus_gains.stride(1) != 1:
-                raise NativeError(f'bus gains must be float64 ({bus_channels},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-            gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-        elif bus_channels != 1:
-            raise NativeError('a bus without gains is mono')
-        if workspace.dtype != torch.float64 or workspace.numel() * 8 < lib().sig_fused_voice_bus_workspace(voices, rows, bus_channels):
-            raise NativeError('fused bus workspace too small')
-        if consts.dtype != torch.float64 or consts.numel() * 8 < lib().sig_fused_voice_consts_size(voices):
-            raise NativeError('consts must be float64 of sig_fused_voice_consts_size(voices) bytes')
+        hp, hs, pp, ps, cp, cs, gp_, gs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain'))
+        gp, gld = _bus_gains(bus_gains, bus_channels, voices)
+        _bus_workspace(workspace, voices, rows, bus_channels)
         self._keep = (hertz, phase, cutoff, gain, bus_gains, workspace, status, consts)
-        self._head = (OSC_KINDS[kind], FILT_TYPES[btype], rate)
-        self._mid = (block_frames, nblocks, context, voices, *ptrs, gp, gld, bus_channels, workspace.data_ptr())
-        self._status = status.data_ptr() if status is not None else None
-        self._consts = consts.data_ptr()
-        self._prepared, self._walk = lib().sig_fused_voice_bus_prepared, lib().sig_fused_voice_bus_walk
         self.shape = (rows, bus_channels)
-        # ... and as one block for sig_fused_voice_bus_bound: six arguments per call instead of 26
-        (hp, hs), (pp, ps), (cp, cs), (gp_, gs) = [ptrs[2 * k: 2 * k + 2] for k in range(4)]
+        # the whole call as one block for sig_fused_voice_bus_bound: six arguments per call instead of 26
         self._block = FusedVoiceBusCallT(OSC_KINDS[kind], FILT_TYPES[btype], rate, block_frames, nblocks, context, voices, hs, ps, cs, gs,
-                                         bus_channels, hp, pp, cp, gp_, gp, gld, bus_channels, workspace.data_ptr(), self._status,
-                                         self._consts)
+                                         bus_channels, hp, pp, cp, gp_, gp, gld, bus_channels, workspace.data_ptr(), _ptr(status),
+                                         _consts(consts, voices))
         self._block_ref = ctypes.byref(self._block)
         self._bound = lib().sig_fused_voice_bus_bound
 
@@ -717,6 +609,13 @@ class FusedVoiceBusCall:
         if err:
             raise NativeError(f'sig_fused_voice_bus failed: hipError_t {err}')
         return out
+
+
+def _consts(consts: torch.Tensor, voices: int) -> int:
+    """the pointer of a caller-held buffer for the Sine closed form's per-voice constants"""
+    if consts.dtype != torch.float64 or consts.numel() * 8 < lib().sig_fused_voice_consts_size(voices):
+        raise NativeError('consts must be float64 of sig_fused_voice_consts_size(voices) bytes')
+    return consts.data_ptr()
 
 
 def fused_geometry(voices: int, block_frames: int, nblocks: int, context: int) -> tuple[int, int]:
@@ -750,99 +649,42 @@ def fused_rows(kind: str, btype: str, rate: int, position: int, block_frames: in
     `phase_hist` = the (1, .) row in front of the launch (the previous block's, whose samples are block 0's context)."""
     _gpu(hertz, phase, cutoff, gain, out, bus_gains, workspace, status, hertz_hist, phase_hist,
          *((pair[2], pair[3], pair[4]) if pair else ()))
-    fm = hertz_hist is not None or phase_hist is not None or hertz.shape[0] > 1 or (phase is not None and phase.shape[0] > 1)
-    if fm:
-        if pair is not None:
-            raise NativeError('block-rate FM and a second oscillator: no fused entry point')
-        hp, hs, hrows = _param_rows(hertz, 'hertz', voices, nblocks)
-        pp, ps, prows = _param_rows(phase, 'phase', voices, nblocks)
-
-        def hist(t, like, rows, what):
-            if t is None and rows == 1:
-                return None
-            if t is None or t.dtype != torch.float64 or tuple(t.shape) != (1, like.shape[1]) or not t.is_contiguous():
-                raise NativeError(f'{what}: the row in front of the launch is float64 (1, {like.shape[1]})')
-            return t.data_ptr()
-        hh, ph_ = hist(hertz_hist, hertz, hrows, 'hertz_hist'), hist(phase_hist, phase, prows, 'phase_hist') if phase is not None else None
-        cp, cs, crows = _param_rows(cutoff, 'cutoff', voices, nblocks)
-        gp, gs, grows = _param_rows(gain, 'gain', voices, nblocks)
-        st = status.data_ptr() if status is not None else None
-        _audio(out, 'fused rows out')
-        if out.dtype != torch.float32 or out.shape[0] != block_frames * nblocks:
-            raise NativeError(f'fused rows out must be float32 ({block_frames * nblocks}, .), got {tuple(out.shape)} {out.dtype}')
-        head = (OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                hp, hs, hrows, hh, pp, ps, prows, ph_, cp, cs, crows, gp, gs, grows)
-        if not bus:
-            if out.shape[1] != voices:
-                raise NativeError(f'fused rows out has {out.shape[1]} channels for {voices} voices')
-            _check(lib().sig_fused_osc_biquad_fm(*head, out.data_ptr(), out.stride(0), st, _stream(out)), 'sig_fused_osc_biquad_fm')
-            return out
-        C = out.shape[1]
-        bp, bld = None, 0
-        if bus_gains is not None:
-            if bus_gains.dtype != torch.float64 or bus_gains.shape != (C, voices) or bus_gains.stride(1) != 1:
-                raise NativeError(f'bus gains must be float64 ({C},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-            bp, bld = bus_gains.data_ptr(), bus_gains.stride(0)
-        elif C != 1:
-            raise NativeError('a bus without gains is mono')
-        need = lib().sig_fused_voice_bus_workspace(voices, out.shape[0], C)
-        if workspace is None or workspace.numel() * workspace.element_size() < need:
-            workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
-        _check(lib().sig_fused_voice_bus_fm(*head, bp, bld, C, workspace.data_ptr(), out.data_ptr(), out.stride(0), st, _stream(out)),
-               'sig_fused_voice_bus_fm')
-        return out
     _audio(out, 'fused rows out')
     rows = out.shape[0]
     if out.dtype != torch.float32 or rows != block_frames * nblocks:
         raise NativeError(f'fused rows out must be float32 ({block_frames * nblocks}, .), got {tuple(out.shape)} {out.dtype}')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
-    cp, cs, crows = _param_rows(cutoff, 'cutoff', voices, nblocks)
-    gp, gs, grows = _param_rows(gain, 'gain', voices, nblocks)
-    st = status.data_ptr() if status is not None else None
-    pargs = None
-    if pair is not None:
-        op, kind2, hertz2, phase2, mixrow = pair
-        pargs = []
-        for row, name in ((hertz2, 'hertz2'), (phase2, 'phase2'), (mixrow, 'mix')):
-            if row is not None and row.shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-            pargs.extend(_ctrl_row(row, name))
-        head = (OSC_KINDS[kind], OSC_KINDS[kind2], {'Mix': 1, 'RingMod': 2}[op], FILT_TYPES[btype])
-    if not bus:
-        if out.shape[1] != voices:
-            raise NativeError(f'fused rows out has {out.shape[1]} channels for {voices} voices')
-        if pargs is not None:
-            _check(lib().sig_fused_osc_pair_biquad(*head, rate, position, block_frames, nblocks, context, voices, *ptrs, *pargs,
-                                                   cp, cs, crows, gp, gs, grows, out.data_ptr(), out.stride(0), st, _stream(out)),
-                   'sig_fused_osc_pair_biquad')
-            return out
-        _check(lib().sig_fused_osc_biquad_rows(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context,
-                                               voices, *ptrs, cp, cs, crows, gp, gs, grows, out.data_ptr(), out.stride(0), st,
-                                               _stream(out)), 'sig_fused_osc_biquad_rows')
-        return out
-    C = out.shape[1]
-    bp, bld = None, 0
-    if bus_gains is not None:
-        if bus_gains.dtype != torch.float64 or bus_gains.shape != (C, voices) or bus_gains.stride(1) != 1:
-            raise NativeError(f'bus gains must be float64 ({C},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-        bp, bld = bus_gains.data_ptr(), bus_gains.stride(0)
-    elif C != 1:
-        raise NativeError('a bus without gains is mono')
-    need = lib().sig_fused_voice_bus_workspace(voices, rows, C)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
-    if pargs is not None:
-        _check(lib().sig_fused_voice_pair_bus(*head, rate, position, block_frames, nblocks, context, voices, *ptrs, *pargs,
-                                              cp, cs, crows, gp, gs, grows, bp, bld, C, workspace.data_ptr(), out.data_ptr(),
-                                              out.stride(0), st, _stream(out)), 'sig_fused_voice_pair_bus')
-        return out
-    _check(lib().sig_fused_voice_bus_rows(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                          *ptrs, cp, cs, crows, gp, gs, grows, bp, bld, C, workspace.data_ptr(), out.data_ptr(),
-                                          out.stride(0), st, _stream(out)), 'sig_fused_voice_bus_rows')
+    # the source -- how hertz and phase are marshalled -- decides which pair of entry points (voices out, bus out) runs
+    kinds = (OSC_KINDS[kind], FILT_TYPES[btype])
+    if hertz_hist is not None or phase_hist is not None or hertz.shape[0] > 1 or (phase is not None and phase.shape[0] > 1):
+        if pair is not None:
+            raise NativeError('block-rate FM and a second oscillator: no fused entry point')
+        names = ('sig_fused_osc_biquad_fm', 'sig_fused_voice_bus_fm')
+        source = []
+        for t, front, what in ((hertz, hertz_hist, 'hertz'), (phase, phase_hist, 'phase')):
+            ptr, stride, count = _param_rows(t, what, voices, nblocks)
+            if t is not None and not (front is None and count == 1):
+                if front is None or front.dtype != torch.float64 or tuple(front.shape) != (1, t.shape[1]) or not front.is_contiguous():
+                    raise NativeError(f'{what}_hist: the row in front of the launch is float64 (1, {t.shape[1]})')
+            source += [ptr, stride, count, _ptr(front) if t is not None else None]
+    else:
+        names = ('sig_fused_osc_biquad_rows', 'sig_fused_voice_bus_rows')
+        source = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'))
+        if pair is not None:
+            op, kind2, hertz2, phase2, mixrow = pair
+            names = ('sig_fused_osc_pair_biquad', 'sig_fused_voice_pair_bus')
+            kinds = (OSC_KINDS[kind], OSC_KINDS[kind2], {'Mix': 1, 'RingMod': 2}[op], FILT_TYPES[btype])
+            source += _voice_rows(voices, (hertz2, 'hertz2'), (phase2, 'phase2'), (mixrow, 'mix'))
+    sink = ()
+    if bus:
+        C = out.shape[1]
+        workspace = _bus_workspace(workspace, voices, rows, C, out.device)
+        sink = (*_bus_gains(bus_gains, C, voices), C, workspace.data_ptr())
+    elif out.shape[1] != voices:
+        raise NativeError(f'fused rows out has {out.shape[1]} channels for {voices} voices')
+    name = names[1 if bus else 0]
+    _check(getattr(lib(), name)(*kinds, rate, position, block_frames, nblocks, context, voices, *source,
+                                *_param_rows(cutoff, 'cutoff', voices, nblocks), *_param_rows(gain, 'gain', voices, nblocks),
+                                *sink, out.data_ptr(), out.stride(0), _ptr(status), _stream(out)), name)
     return out
 
 
@@ -858,33 +700,12 @@ def fused_cascade_bus(kind: str, btype1: str, btype2: str, rate: int, position: 
     rows, bus = out.shape
     if out.dtype != torch.float32 or rows != block_frames * nblocks:
         raise NativeError(f'fused cascade out must be float32 ({block_frames * nblocks}, C), got {tuple(out.shape)} {out.dtype}')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff1, 'cutoff1'), (cutoff2, 'cutoff2'), (gain, 'gain')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
-    eptrs = estrides = None
-    if envelope is not None:
-        eptrs = (ctypes.c_void_p * 6)()
-        estrides = (ctypes.c_int32 * 6)()
-        for i, name in enumerate(ADSR_PARAMS):
-            eptrs[i], estrides[i] = _ctrl_row(envelope[name], name)
-            if envelope[name].shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {envelope[name].shape[1]} channels for {voices} voices')
-    gp, gld = None, 0
-    if bus_gains is not None:
-        if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus, voices) or bus_gains.stride(1) != 1:
-            raise NativeError(f'bus gains must be float64 ({bus},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-        gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-    elif bus != 1:
-        raise NativeError('a bus without gains is mono')
-    need = lib().sig_fused_voice_bus_workspace(voices, rows, bus)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
+    ptrs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff1, 'cutoff1'), (cutoff2, 'cutoff2'), (gain, 'gain'))
+    workspace = _bus_workspace(workspace, voices, rows, bus, out.device)
     _check(lib().sig_fused_cascade_bus(OSC_KINDS[kind], FILT_TYPES[btype1], FILT_TYPES[btype2], rate, position,
-                                       first_history_start, block_frames, nblocks, context, voices, *ptrs, eptrs, estrides,
-                                       gp, gld, bus, workspace.data_ptr(), out.data_ptr(), out.stride(0),
-                                       status.data_ptr() if status is not None else None, _stream(out)),
+                                       first_history_start, block_frames, nblocks, context, voices, *ptrs,
+                                       *_envelope(envelope, voices), *_bus_gains(bus_gains, bus, voices), bus,
+                                       workspace.data_ptr(), out.data_ptr(), out.stride(0), _ptr(status), _stream(out)),
            'sig_fused_cascade_bus')
     return out
 
@@ -997,15 +818,10 @@ def fused_osc_biquad_mix(kind: str, btype: str, rate: int, position: int, block_
         raise NativeError(f'fused mix out must be float32 ({block_frames * nblocks}, 64*g), got {tuple(out.shape)} {out.dtype}')
     if matrix.dtype != torch.float32 or tuple(matrix.shape) != (64, 64) or not matrix.is_contiguous():
         raise NativeError(f'mix matrix must be contiguous float32 (64, 64), got {tuple(matrix.shape)} {matrix.dtype}')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
+    ptrs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain'))
     _check(lib().sig_fused_osc_biquad_mix(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context,
-                                          voices, *ptrs, matrix.data_ptr(), out.data_ptr(), out.stride(0),
-                                          status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_fused_osc_biquad_mix')
+                                          voices, *ptrs, matrix.data_ptr(), out.data_ptr(), out.stride(0), _ptr(status),
+                                          _stream(out)), 'sig_fused_osc_biquad_mix')
     return out
 
 
@@ -1030,38 +846,17 @@ def fused_voice_bus(kind: str, btype: str, rate: int, position: int, block_frame
     rows, bus = out.shape
     if out.dtype != torch.float32 or rows != block_frames * nblocks:
         raise NativeError(f'fused bus out must be float32 ({block_frames * nblocks}, C), got {tuple(out.shape)} {out.dtype}')
-    ptrs = []
-    for row, name in ((hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain')):
-        if row is not None and row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        ptrs.extend(_ctrl_row(row, name))
-    gp, gld = None, 0
-    if bus_gains is not None:
-        if bus_gains.dtype != torch.float64 or bus_gains.shape != (bus, voices) or bus_gains.stride(1) != 1:
-            raise NativeError(f'bus gains must be float64 ({bus},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-        gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-    need = lib().sig_fused_voice_bus_workspace(voices, rows, bus)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
+    ptrs = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (cutoff, 'cutoff'), (gain, 'gain'))
+    workspace = _bus_workspace(workspace, voices, rows, bus, out.device)
+    entry, name, tail = lib().sig_fused_voice_bus, 'sig_fused_voice_bus', ()
     if walk:
-        _check(lib().sig_fused_voice_bus_walk(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context,
-                                              voices, *ptrs, gp, gld, bus, workspace.data_ptr(), out.data_ptr(), out.stride(0),
-                                              status.data_ptr() if status is not None else None, _stream(out)),
-               'sig_fused_voice_bus_walk')
-        return out
-    if consts is not None:
-        if consts.dtype != torch.float64 or consts.numel() * 8 < lib().sig_fused_voice_consts_size(voices):
-            raise NativeError('consts must be float64 of sig_fused_voice_consts_size(voices) bytes')
-        _check(lib().sig_fused_voice_bus_prepared(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks,
-                                                  context, voices, *ptrs, gp, gld, bus, workspace.data_ptr(), out.data_ptr(),
-                                                  out.stride(0), status.data_ptr() if status is not None else None,
-                                                  _stream(out), consts.data_ptr(), 1 if consts_ready else 0),
-               'sig_fused_voice_bus_prepared')
-        return out
-    _check(lib().sig_fused_voice_bus(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context,
-                                     voices, *ptrs, gp, gld, bus, workspace.data_ptr(), out.data_ptr(), out.stride(0),
-                                     status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_fused_voice_bus')
+        entry, name = lib().sig_fused_voice_bus_walk, 'sig_fused_voice_bus_walk'
+    elif consts is not None:
+        entry, name = lib().sig_fused_voice_bus_prepared, 'sig_fused_voice_bus_prepared'
+        tail = (_consts(consts, voices), 1 if consts_ready else 0)
+    _check(entry(OSC_KINDS[kind], FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices, *ptrs,
+                 *_bus_gains(bus_gains, bus, voices), bus, workspace.data_ptr(), out.data_ptr(), out.stride(0), _ptr(status),
+                 _stream(out), *tail), name)
     return out
 
 
@@ -1069,23 +864,7 @@ def band_coldstart(btype: str, rate: int, position: int, block_frames: int, nblo
                    low: torch.Tensor, high: torch.Tensor, buf: torch.Tensor, history: int, out: torch.Tensor,
                    status: torch.Tensor | None = None) -> torch.Tensor:
     """BandPass ('bp') / BandStop ('bs'): two biquad sections; buffers as in `biquad_coldstart`."""
-    _gpu(low, high, buf, out, status)
-    _audio(buf, 'band in')
-    _audio(out, 'band out')
-    rows, voices = out.shape
-    if rows != block_frames * nblocks or buf.shape[0] != history + rows or buf.shape[1] != voices or buf.dtype != out.dtype:
-        raise NativeError(f'band shapes: in {tuple(buf.shape)} history {history} out {tuple(out.shape)}')
-    ptrs = []
-    for row, name in ((low, 'low'), (high, 'high')):
-        if row.shape[1] != voices and voices != 1:
-            raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
-        ptrs.extend(_ctrl_row(row, name))
-    in_ptr = buf.data_ptr() + history * buf.stride(0) * buf.element_size()
-    _check(lib().sig_band_coldstart(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices, *ptrs,
-                                    in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
-                                    status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_band_coldstart')
-    return out
+    return _band_coldstart(False, btype, rate, position, block_frames, nblocks, context, low, high, buf, history, out, status)
 
 
 def band_coldstart_blocks(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
@@ -1093,33 +872,37 @@ def band_coldstart_blocks(btype: str, rate: int, position: int, block_frames: in
                           status: torch.Tensor | None = None) -> torch.Tensor:
     """`band_coldstart` with per-block bands: low / high f64 (1|nblocks, V|1), row b (of a multi-row edge) is block b's.
     A single-row edge beside a multi-row one is repeated for every block."""
+    return _band_coldstart(True, btype, rate, position, block_frames, nblocks, context, low, high, buf, history, out, status)
+
+
+def _band_coldstart(per_block: bool, btype, rate, position, block_frames, nblocks, context, low, high, buf, history, out, status):
+    """sig_band_coldstart, or with `per_block` sig_band_coldstart_blocks: the two differ in their band edges' rows"""
     _gpu(low, high, buf, out, status)
     _audio(buf, 'band in')
     _audio(out, 'band out')
-    rows, voices = out.shape
-    if rows != block_frames * nblocks or buf.shape[0] != history + rows or buf.shape[1] != voices or buf.dtype != out.dtype:
-        raise NativeError(f'band shapes: in {tuple(buf.shape)} history {history} out {tuple(out.shape)}')
+    voices = out.shape[1]
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'band')
     blocks = max(low.shape[0], high.shape[0])
-    ptrs = []
+    edges = []
     for row, name in ((low, 'low'), (high, 'high')):
-        if row.dtype != torch.float64 or row.dim() != 2 or not row.is_contiguous():
-            raise NativeError(f'{name} must be a contiguous float64 2-D tensor')
-        if row.shape[0] not in (1, nblocks):
-            raise NativeError(f'{name} has {row.shape[0]} rows for {nblocks} blocks')
         if row.shape[1] != voices and voices != 1:
             raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
-        if row.shape[1] not in (1, voices):
-            raise NativeError(f'{name} has {row.shape[1]} channels for {voices} voices')
-        if row.shape[0] != blocks:
-            row = row.expand(blocks, row.shape[1]).contiguous()
-        ptrs.extend((row.data_ptr(), 0 if row.shape[1] == 1 else 1))
-        ptrs.append(row)                                                       # (kept alive until the call returns)
-    in_ptr = buf.data_ptr() + history * buf.stride(0) * buf.element_size()
-    _check(lib().sig_band_coldstart_blocks(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                           ptrs[0], ptrs[1], ptrs[3], ptrs[4], blocks, in_ptr, buf.stride(0), history,
-                                           out.data_ptr(), out.stride(0), _dt(out),
-                                           status.data_ptr() if status is not None else None, _stream(out)),
-           'sig_band_coldstart_blocks')
+        if per_block:
+            if row.dtype != torch.float64 or row.dim() != 2 or not row.is_contiguous():
+                raise NativeError(f'{name} must be a contiguous float64 2-D tensor')
+            if row.shape[0] not in (1, nblocks):
+                raise NativeError(f'{name} has {row.shape[0]} rows for {nblocks} blocks')
+            if row.shape[0] != blocks:
+                row = row.expand(blocks, row.shape[1]).contiguous()
+        edges.append((row, name))                                              # (an expanded row is kept alive until the call returns)
+    if per_block:
+        name, entry = 'sig_band_coldstart_blocks', lib().sig_band_coldstart_blocks
+        ptrs = _voice_rows(voices, *edges, form=lambda t, what: _ctrl_rows(t, what)[:2]) + [blocks]
+    else:
+        name, entry = 'sig_band_coldstart', lib().sig_band_coldstart
+        ptrs = _voice_rows(voices, *edges)
+    _check(entry(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices, *ptrs, in_ptr, buf.stride(0), history,
+                 out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), name)
     return out
 
 
@@ -1130,14 +913,8 @@ def adsr_apply(position: int, rate: int, rows: dict, x: torch.Tensor, out: torch
     _audio(out, 'adsr_apply out')
     if x.dtype != torch.float32 or out.dtype != torch.float32 or x.shape != out.shape:
         raise NativeError(f'adsr_apply is float32 (rows, V) in and out, got {tuple(x.shape)} {x.dtype} -> {tuple(out.shape)} {out.dtype}')
-    ptrs = (ctypes.c_void_p * 6)()
-    strides = (ctypes.c_int32 * 6)()
-    for i, name in enumerate(ADSR_PARAMS):
-        ptrs[i], strides[i] = _ctrl_row(rows[name], name)
-        if rows[name].shape[1] not in (1, out.shape[1]):
-            raise NativeError(f'{name} has {rows[name].shape[1]} channels for {out.shape[1]} voices')
-    _check(lib().sig_adsr_apply(position, rate, out.shape[0], out.shape[1], ptrs, strides, x.data_ptr(), x.stride(0),
-                                out.data_ptr(), out.stride(0), _stream(out)), 'sig_adsr_apply')
+    _check(lib().sig_adsr_apply(position, rate, out.shape[0], out.shape[1], *_envelope(rows, out.shape[1]), x.data_ptr(),
+                                x.stride(0), out.data_ptr(), out.stride(0), _stream(out)), 'sig_adsr_apply')
     return out
 
 
@@ -1148,6 +925,15 @@ def _vp_rows(t: torch.Tensor | None, what: str, voices: int, control_rows: int) 
             or t.shape[0] not in (1, control_rows)):
         raise NativeError(f'{what}: rows of a voice program are contiguous float64 (1|{control_rows}, 1|{voices}), got {tuple(t.shape)} {t.dtype}')
     return VpRows(t.data_ptr(), 0 if t.shape[1] == 1 else 1, t.shape[0])
+
+
+def _program_struct(code: list) -> VoiceProgramT:
+    """a sig_voice_program_t that holds the instructions given as (op name, kind, a, b, c) tuples"""
+    P = VoiceProgramT()
+    P.n_ins = len(code)
+    for k, (op, kind, a, b, c) in enumerate(code):
+        P.ins[k] = VpIns(VP_OPS[op], kind, a, b, c)
+    return P
 
 
 def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: int, depth: int, rate: int, position: int,
@@ -1168,10 +954,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
     if len(code) > VP_MAX_INS or len(oscs) > VP_MAX_OSCS or len(params) > VP_MAX_PARAMS or len(filters) > VP_MAX_FILTERS \
             or n_temps > VP_MAX_TEMPS or len(hist_positions) > VP_MAX_HIST:
         raise NativeError('voice program larger than the machine')
-    P = VoiceProgramT()
-    P.n_ins = len(code)
-    for k, (op, kind, a, b, c) in enumerate(code):
-        P.ins[k] = VpIns(VP_OPS[op], kind, a, b, c)
+    P = _program_struct(code)
     P.n_oscs = len(oscs)
     for k, (hz, ph) in enumerate(oscs):
         P.hertz[k] = _vp_rows(hz, 'hertz', voices, control_rows)
@@ -1187,32 +970,20 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
         P.filter_type[k] = FILT_TYPES[btype]
         P.filter_level[k] = level
     P.n_temps, P.depth = n_temps, depth
-    if adsr is not None:
-        for i, name in enumerate(ADSR_PARAMS):
-            P.adsr[i], P.adsr_stride[i] = _ctrl_row(adsr[name], name)
-            if adsr[name].shape[1] not in (1, voices):
-                raise NativeError(f'{name} has {adsr[name].shape[1]} channels for {voices} voices')
+    _envelope(adsr, voices, into=(P.adsr, P.adsr_stride))
     P.noise_seed[0], P.noise_seed[1] = noise_seeds
     hist = (ctypes.c_int64 * max(1, len(hist_positions)))(*hist_positions)
     C = 0
     gp, gld = None, 0
     if bus:
         C = out.shape[1]
-        if bus_gains is not None:
-            if bus_gains.dtype != torch.float64 or bus_gains.shape != (C, voices) or bus_gains.stride(1) != 1:
-                raise NativeError(f'bus gains must be float64 ({C},{voices}), got {tuple(bus_gains.shape)} {bus_gains.dtype}')
-            gp, gld = bus_gains.data_ptr(), bus_gains.stride(0)
-        elif C != 1:
-            raise NativeError('a bus without gains is mono')
-        need = lib().sig_fused_voice_bus_workspace(voices, rows, C)
-        if workspace is None or workspace.numel() * workspace.element_size() < need:
-            workspace = torch.empty(need // 8, dtype=torch.float64, device=out.device)
+        gp, gld = _bus_gains(bus_gains, C, voices)
+        workspace = _bus_workspace(workspace, voices, rows, C, out.device)
     elif out.shape[1] != voices:
         raise NativeError(f'voice program out has {out.shape[1]} channels for {voices} voices')
     _check(lib().sig_voice_program(ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows,
                                    len(hist_positions), hist, blocks_before, gp, gld, C,
-                                   workspace.data_ptr() if workspace is not None else None, out.data_ptr(), out.stride(0),
-                                   status.data_ptr() if status is not None else None, _stream(out)), 'sig_voice_program')
+                                   _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out)), 'sig_voice_program')
     return out
 
 
@@ -1236,10 +1007,7 @@ def voice_program_attach(code: list, n_oscs: int, n_params: int, n_filters: int,
     """hand the library a specialised build of voice_program.hip for exactly this program (signals_amd/specialise.py): later
     sig_voice_program calls with the same program, slot counts, voices per lane and sink launch it instead of the interpreter.
     Loads the image, runs its self-description kernel and synchronises: a set-up call, not a render call."""
-    P = VoiceProgramT()
-    P.n_ins = len(code)
-    for k, (op, kind, a, b, c) in enumerate(code):
-        P.ins[k] = VpIns(VP_OPS[op], kind, a, b, c)
+    P = _program_struct(code)
     P.n_oscs, P.n_params, P.n_filters, P.n_temps = n_oscs, n_params, n_filters, n_temps
     _check(lib().sig_voice_program_attach(ctypes.byref(P), voices_per_lane, bus_channels, image), 'sig_voice_program_attach')
 

@@ -270,9 +270,7 @@ class BatchRenderer:
         self._tails_rebuilt = False
         batch = _Batch(self, position, block_frames, nblocks, continuing)
         out = batch.buffer(self.node, self.channels, 0)
-        for node, buf in batch.impure_outputs():
-            keep = min(CONTEXT, buf.shape[0])
-            self._tails[node] = (position + block_frames * nblocks, buf[buf.shape[0] - keep:].clone())
+        self._save_tails(batch, position + block_frames * nblocks)
         self._stream_end = position + block_frames * nblocks
         self._prev_block_frames = block_frames
         self._stream_blocks += nblocks
@@ -300,6 +298,12 @@ class BatchRenderer:
             starts.insert(0, edge)
         return starts
 
+    def _save_tails(self, batch: '_Batch', end: int, replace: bool = True) -> None:
+        """keep the last min(100, rows) rows of every request-dependent node of a batch that ends at `end`"""
+        for node, buf in batch.impure_outputs():
+            if replace or node not in self._tails:
+                self._tails[node] = (end, buf[buf.shape[0] - min(CONTEXT, buf.shape[0]):].clone())
+
     def _rebuild_tails(self, position: int) -> None:
         """The previous batch ran (part of) the graph through the fused cascade, which leaves no tails, and this one needs
         the per-node schedule for it (a block size the kernel does not take, a node that gained a reader, `fuse_cascade`
@@ -315,10 +319,7 @@ class BatchRenderer:
         try:
             sub = _Batch(self, position - prev, prev, 1, False)
             sub.buffer(self.node, self.channels, 0)
-            for node, buf in sub.impure_outputs():
-                if node not in self._tails:
-                    keep = min(CONTEXT, buf.shape[0])
-                    self._tails[node] = (position, buf[buf.shape[0] - keep:].clone())
+            self._save_tails(sub, position, replace=False)
         finally:
             self.fuse_cascade, self._virtual_history, self._replay = keep_fuse, keep_virtual, keep_replay
 
@@ -339,6 +340,22 @@ class BatchRenderer:
         if self.timer is not None:
             return self.timer.launch(name, fn, **meta)
         return fn()
+
+    def _control_program(self, key, build: typing.Callable):
+        """the compiled control program kept under `key`, built again when the graph or a Fixed row behind it has changed"""
+        held = self._ctl_programs.get(key)
+        if held is None or held[0] != graph_clock.version or not held[1].current():
+            if len(self._ctl_programs) > 16:
+                self._ctl_programs.clear()
+            held = self._ctl_programs[key] = (graph_clock.version, build())
+        return held[1]
+
+    def _bus_workspace(self, voices: int, rows: int, bus_channels: int) -> torch.Tensor:
+        """the f64 scratch of the fused bus kernels, grown to what this launch needs"""
+        need = _native.lib().sig_fused_voice_bus_workspace(voices, rows, bus_channels) // 8
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=CTRL_DTYPE, device=runtime.device())
+        return self._workspace
 
     def _status_word(self, node: Emitter) -> torch.Tensor:
         word = self._status.get(node)
@@ -499,38 +516,56 @@ class _ControlProgram:
         self.ins.append(ins)
         return reg, cols
 
-    def _emit(self, src) -> tuple[int, int]:
+    def _emit(self, src, window: bool = False) -> tuple[int, int]:
+        """(register, columns) of a node's value at block rate; `window`: the node is part of a control filter's input and is
+        evaluated per window row (`reserved` = 1), its own control ports must then hold for every row (Fixed / unplugged).
+        A constant row is emitted at block rate in either place"""
         if src is None or not src.get_state().enabled:
-            key = None
-            if key not in self._reg:
-                self._reg[key] = self._row(self._zero)
-            return self._reg[key]
-        if src in self._reg:
-            return self._reg[src]
+            if None not in self._reg:
+                self._reg[None] = self._row(self._zero)
+            return self._reg[None]
+        window = window and not isinstance(src, fixed.Fixed)
+        regs = self._window if window else self._reg
+        if src in regs:
+            return regs[src]
+
+        def control(port):
+            if window and not _ctl_const(port):
+                raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input has a modulated {port.name}')
+            return self._emit(port.sig)
         if isinstance(src, fixed.Fixed):
             row = src.resident()
             self.fixed.append((src, row))
             got = self._row(row)
         elif isinstance(src, osc.Osc):
-            (a, ca), (b, cb) = self._emit(src.hertz.sig), self._emit(src.phase.sig)
-            got = self._push(_native.CtlIns(_native.CTL_OPS['Osc'], _native.OSC_KINDS[src.kind()], a, b, -1, 0, 0, 0, max(ca, cb), 0, None), max(ca, cb))
+            (a, ca), (b, cb) = control(src.hertz), control(src.phase)
+            got = self._push(_native.CtlIns(_native.CTL_OPS['Osc'], _native.OSC_KINDS[src.kind()], a, b, -1, 0, 0, 0, max(ca, cb),
+                                            int(window), None), max(ca, cb))
         elif isinstance(src, (fx.Gain, fx.Amp, fx.Mix, fx.RingMod)):
-            (a, ca), (b, cb) = self._emit(src.left.sig), self._emit(src.right.sig)
-            c, cc = self._emit(src.mix.sig) if isinstance(src, fx.Mix) else (-1, 1)
+            a, ca = self._emit(src.left.sig, window)
+            b, cb = control(src.right) if isinstance(src, (fx.Gain, fx.Amp)) else self._emit(src.right.sig, window)
+            c, cc = control(src.mix) if isinstance(src, fx.Mix) else (-1, 1)
             cols = broadcast_shape((1, ca), (1, cb), (1, cc))[1]
-            got = self._push(_native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, 0, None), cols)
+            got = self._push(_native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, int(window), None), cols)
         elif isinstance(src, noise.White):
-            got = self._push(self._noise(src, window=False), self._request_width(src))
+            got = self._push(self._noise(src, window), self._request_width(src))
+        elif window and isinstance(src, fx.CritFilter):
+            raise NotBatchable('a filter whose input contains a filter, in a control path')
         elif isinstance(src, fx.SingleCritFilter):
             got = self._filter(src)
         elif isinstance(src, fx.DoubleCritFilter):
             raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
+        elif isinstance(src, ext.PMOsc) and window:
+            raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
+                               f'window-rate program')
         elif isinstance(src, ext.PMOsc):
             raise NotBatchable(f'{src.cls_name()} in a control path: a phase-modulation oscillator has no block-rate program '
                                f'(its modulator is a frame-rate input)')
+        elif window:
+            raise NotBatchable(f'no window-rate program for {src.cls_name()} inside a control filter\'s input')
         else:
             raise NotBatchable(f'no block-rate program for {src.cls_name()}')
-        self._reg[src] = got
+        regs[src] = got
         return got
 
     def _request_width(self, src) -> int:
@@ -554,7 +589,7 @@ class _ControlProgram:
             raise NotBatchable(f'{src.cls_name()} in a control path over a one-row input')
         self._window = {}
         try:
-            a, ca = self._emit_window(inp)
+            a, ca = self._emit(inp, window=True)
             inside = set(self._window)
         finally:
             self._window = None
@@ -566,42 +601,6 @@ class _ControlProgram:
         status = None if self._status is None else self._status(src)
         return self._push(_native.CtlIns(_native.CTL_OPS['Filter'], _native.FILT_TYPES[str(src.type())], a, cut, -1, 0, 0, 0,
                                          width, 0, None if status is None else status.data_ptr()), width)
-
-    def _emit_window(self, src) -> tuple[int, int]:
-        """a node of a control filter's input: evaluated per window row (`reserved` = 1); its own control ports must hold for
-        every row (Fixed / unplugged)"""
-        if src is None or not src.get_state().enabled or isinstance(src, fixed.Fixed):
-            return self._emit(src)                         # a constant row: block rate
-        if src in self._window:
-            return self._window[src]
-        def const(port):
-            if not _ctl_const(port):
-                raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input has a modulated {port.name}')
-            return self._emit(port.sig)
-        if isinstance(src, osc.Osc):
-            (a, ca), (b, cb) = const(src.hertz), const(src.phase)
-            cols = max(ca, cb)
-            ins = _native.CtlIns(_native.CTL_OPS['Osc'], _native.OSC_KINDS[src.kind()], a, b, -1, 0, 0, 0, cols, 1, None)
-        elif isinstance(src, noise.White):
-            ins, cols = self._noise(src, window=True), self._request_width(src)
-        elif isinstance(src, (fx.Gain, fx.Amp)):
-            (a, ca), (b, cb) = self._emit_window(src.left.sig), const(src.right)
-            cols = broadcast_shape((1, ca), (1, cb))[1]
-            ins = _native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, -1, 0, 0, 0, cols, 1, None)
-        elif isinstance(src, (fx.Mix, fx.RingMod)):
-            (a, ca), (b, cb) = self._emit_window(src.left.sig), self._emit_window(src.right.sig)
-            c, cc = const(src.mix) if isinstance(src, fx.Mix) else (-1, 1)
-            cols = broadcast_shape((1, ca), (1, cb), (1, cc))[1]
-            ins = _native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, 1, None)
-        elif isinstance(src, fx.CritFilter):
-            raise NotBatchable('a filter whose input contains a filter, in a control path')
-        elif isinstance(src, ext.PMOsc):
-            raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
-                               f'window-rate program')
-        else:
-            raise NotBatchable(f'no window-rate program for {src.cls_name()} inside a control filter\'s input')
-        got = self._window[src] = self._push(ins, cols)
-        return got
 
     def current(self) -> bool:
         return all(f.resident() is t for f, t in self.fixed)
@@ -674,14 +673,9 @@ class _Batch:
         srcs = tuple(p.sig for p in ports)
         key = (tuple(id(x) for x in srcs), self.K, channels)
         try:
-            held = o._ctl_programs.get(key)
-            if held is None or held[0] != graph_clock.version or not held[1].current():
-                if len(o._ctl_programs) > 16:
-                    o._ctl_programs.clear()
-                held = o._ctl_programs[key] = (graph_clock.version, _ControlProgram(srcs, self.K, channels=channels,
-                                                                                   status=o._status_word))
-            self._check_windowed(held[1], [front_position] if front_position >= 0 else [])
-            return held[1].run(o, self.rate, self.pos, self.N, front_position)
+            program = o._control_program(key, lambda: _ControlProgram(srcs, self.K, channels=channels, status=o._status_word))
+            self._check_windowed(program, [front_position] if front_position >= 0 else [])
+            return program.run(o, self.rate, self.pos, self.N, front_position)
         except NotBatchable:
             rows = [self._control(p, p.name) for p in ports]
             if front_position < 0:
@@ -714,14 +708,10 @@ class _Batch:
             if not self._widths:
                 raise NotBatchable(f'{what}: {src.cls_name()} read where the request width is not known')
             width = self._widths[-1]
-            key = ('node', id(src), K, width)
-            held = o._ctl_programs.get(key)
-            if held is None or held[0] != graph_clock.version or not held[1].current():
-                if len(o._ctl_programs) > 16:
-                    o._ctl_programs.clear()
-                held = o._ctl_programs[key] = (graph_clock.version, _ControlProgram((src,), K, channels=width, status=o._status_word))
-            self._check_windowed(held[1], [])
-            result = held[1].run(o, self.rate, self.pos, self.N)[0]
+            program = o._control_program(('node', id(src), K, width),
+                                         lambda: _ControlProgram((src,), K, channels=width, status=o._status_word))
+            self._check_windowed(program, [])
+            result = program.run(o, self.rate, self.pos, self.N)[0]
         elif isinstance(src, (fx.Gain, fx.Amp, fx.Mix, fx.RingMod)):
             name = type(src).__name__
             a = self._control(src.left, 'left')
@@ -768,24 +758,12 @@ class _Batch:
         if not node.get_state().enabled and not isinstance(node, (ext.Tap, files.FileWriter)):
             return
         if isinstance(node, fx.CritFilter):
-            self._require(node.input.sig, channels, min(CONTEXT, self.pos))
+            hist = min(CONTEXT, self.pos)
         elif _modulated(node):
-            for port in _audio_ports(node):                       # own history comes from the tail / a fresh block
-                self._require(port.sig, channels, 0)
-        elif isinstance(node, (fx.Mix, fx.RingMod)):
-            self._require(node.left.sig, channels, hist)
-            self._require(node.right.sig, channels, hist)
-        elif isinstance(node, (fx.Gain, fx.Amp)):
-            self._require(node.left.sig, channels, hist)
-        elif isinstance(node, ext.PMOsc):
-            self._require(node.mod.sig, channels, hist)
-        elif isinstance(node, ext.SumBus):
-            self._require(node.input.sig, node.input.channels, hist)
-        elif isinstance(node, (ext.MixMatrix, ext.Tap, files.FileWriter)):
-            self._require(node.input.sig, channels, hist)
-        elif isinstance(node, shape.Merge):
-            self._require(node.left.sig, node.left.channels, hist)
-            self._require(node.right.sig, node.right.channels, hist)
+            hist = 0                                              # own history comes from the tail / a fresh block
+        own_width = isinstance(node, (ext.SumBus, shape.Merge))   # these ask with their ports' own widths
+        for port in _audio_ports(node):
+            self._require(port.sig, port.channels if own_width else channels, hist)
 
     # -------------------------------------------------------------- buffers
     def buffer(self, node: Emitter | None, channels: int, hist: int) -> torch.Tensor:
@@ -846,46 +824,29 @@ class _Batch:
         return value
 
     def _sched_osc(self, node, channels, hist, rows):
-        o = self.owner
-        hertz = self._control(node.hertz, 'hertz')
-        phase = self._control(node.phase, 'phase')
-        _, voices = broadcast_shape((1, 1), (1, hertz.shape[1]), (1, phase.shape[1]))
-        result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
-        if _modulated(node):
-            # hertz / phase are re-read every block: K parameter rows, N output rows each
-            main = result[hist:]
-            o._launch(f'osc_bank[{node.kind()},per-block]',
-                      lambda: _native.osc_bank(node.kind(), self.pos, self.rate, hertz, phase, main,
-                                               rows_per_param=self.N),
-                      units=main.shape[0] * voices)
-            self._own_history(node, voices, hist, result)
-        else:
-            start = self.pos - hist
-            o._launch(f'osc_bank[{node.kind()}]',
-                      lambda: _native.osc_bank(node.kind(), start, self.rate, hertz, phase, result),
-                      units=rows * voices)
-        return result
+        hertz, phase = self._control(node.hertz, 'hertz'), self._control(node.phase, 'phase')
+        return self._osc_launch(node, 'osc_bank', _native.osc_bank, (hertz, phase), hist, rows)
 
     def _sched_pm(self, node, channels, hist, rows):
         """a phase-modulation oscillator: one sig_osc_bank_pm launch over the modulator's rows"""
-        o = self.owner
         hertz, phase, index = (self._control(p, p.name) for p in (node.hertz, node.phase, node.index))
-        mod = _modulated(node)
-        x = self._operand(node.mod, channels, 0 if mod else hist)  # a modulated node's history comes from its tail
-        _, voices = broadcast_shape((1, 1), *((1, t.shape[1]) for t in (hertz, phase, index, x)))
+        x = self._operand(node.mod, channels, 0 if _modulated(node) else hist)   # a modulated node's history comes from its tail
+        return self._osc_launch(node, 'osc_bank_pm', _native.osc_bank_pm, (hertz, phase, index, x), hist, rows)
+
+    def _osc_launch(self, node, name, bank, operands, hist, rows):
+        """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
+        o, kind = self.owner, node.kind()
+        _, voices = broadcast_shape((1, 1), *((1, t.shape[1]) for t in operands))
         result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
-        if mod:
+        if _modulated(node):
+            # the parameters are re-read every block: K parameter rows, N output rows each
             main = result[hist:]
-            o._launch(f'osc_bank_pm[{node.kind()},per-block]',
-                      lambda: _native.osc_bank_pm(node.kind(), self.pos, self.rate, hertz, phase, index, x, main,
-                                                  rows_per_param=self.N),
-                      units=main.shape[0] * voices)
+            o._launch(f'{name}[{kind},per-block]',
+                      lambda: bank(kind, self.pos, self.rate, *operands, main, rows_per_param=self.N), units=main.shape[0] * voices)
             self._own_history(node, voices, hist, result)
         else:
             start = self.pos - hist
-            o._launch(f'osc_bank_pm[{node.kind()}]',
-                      lambda: _native.osc_bank_pm(node.kind(), start, self.rate, hertz, phase, index, x, result),
-                      units=rows * voices)
+            o._launch(f'{name}[{kind}]', lambda: bank(kind, start, self.rate, *operands, result), units=rows * voices)
         return result
 
     def _sched_noise(self, node, channels, hist, rows):
@@ -925,15 +886,29 @@ class _Batch:
             self._own_history(node, cols, hist, result)
         return result
 
+    @staticmethod
+    def _sole_envelope(node):
+        """a RingMod that is x * envelope, the envelope an enabled ADSR with block-invariant parameters that nothing else
+        reads: (the ADSR, x's port), else None"""
+        for env_port, x_port in ((node.right, node.left), (node.left, node.right)):
+            env = env_port.sig
+            if isinstance(env, ext.ADSR) and env.get_state().enabled and len(env.outputs_with_ports) == 1 and not _modulated(env):
+                return env, x_port
+        return None
+
+    def _envelope_rows(self, env) -> dict:
+        """the control rows of an envelope whose parameters hold for every block (NotBatchable otherwise)"""
+        return env.control_rows(lambda bound: self._control_const(bound, bound.name))
+
     def _enveloped_filter(self, node, channels):
         """RingMod(filter, ADSR) where nothing else reads the envelope or the filter and the filter's rows are not
         in the batch yet: (filter, ADSR control rows), else None"""
-        for env_port, x_port in ((node.right, node.left), (node.left, node.right)):
-            env, flt = env_port.sig, x_port.sig
-            if (isinstance(env, ext.ADSR) and env.get_state().enabled and len(env.outputs_with_ports) == 1
-                    and not _modulated(env) and isinstance(flt, fx.SingleCritFilter) and flt.get_state().enabled
+        found = self._sole_envelope(node)
+        if found is not None:
+            env, flt = found[0], found[1].sig
+            if (isinstance(flt, fx.SingleCritFilter) and flt.get_state().enabled
                     and len(flt.outputs_with_ports) == 1 and (flt, channels) not in self._memo):
-                ctl = env.control_rows(lambda bound: self._control_const(bound, bound.name))
+                ctl = self._envelope_rows(env)
                 voices = broadcast_shape((1, 1), *(r.shape for r in ctl.values()))[1]
                 if voices in (1, channels):
                     return flt, ctl
@@ -943,24 +918,23 @@ class _Batch:
         """RingMod(x, ADSR) with an envelope nobody else reads: the envelope multiplies x on the fly -- in the
         epilogue of the filter that produces x when nothing else reads that filter (sig_biquad_coldstart_env),
         else in one envelope * x pass (sig_adsr_apply)"""
-        for env_port, x_port in ((node.right, node.left), (node.left, node.right)):
-            env = env_port.sig
-            if (isinstance(env, ext.ADSR) and env.get_state().enabled and len(env.outputs_with_ports) == 1
-                    and not _modulated(env) and x_port.sig is not None and not isinstance(x_port.sig, ext.ADSR)):
-                ctl = env.control_rows(lambda bound: self._control_const(bound, bound.name))
-                voices = broadcast_shape((1, 1), *(r.shape for r in ctl.values()))[1]
-                flt = x_port.sig
-                if (isinstance(flt, fx.SingleCritFilter) and flt.get_state().enabled and len(flt.outputs_with_ports) == 1
-                        and voices in (1, channels) and (flt, channels) not in self._memo):
-                    return self._filter(flt, channels, hist, rows, envelope=ctl, owner_node=node)
-                x = self._operand(x_port, channels, hist)
-                if x.shape[0] == 1 or x.shape[1] != voices or x.dtype != AUDIO_DTYPE:
-                    return None
-                result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
-                start = self.pos - hist
-                return self.owner._launch('adsr_apply', lambda: _native.adsr_apply(start, self.rate, ctl, x, result),
-                                          units=rows * voices)
-        return None
+        found = self._sole_envelope(node)
+        if found is None or found[1].sig is None or isinstance(found[1].sig, ext.ADSR):
+            return None
+        env, x_port = found
+        ctl = self._envelope_rows(env)
+        voices = broadcast_shape((1, 1), *(r.shape for r in ctl.values()))[1]
+        flt = x_port.sig
+        if (isinstance(flt, fx.SingleCritFilter) and flt.get_state().enabled and len(flt.outputs_with_ports) == 1
+                and voices in (1, channels) and (flt, channels) not in self._memo):
+            return self._filter(flt, channels, hist, rows, envelope=ctl, owner_node=node)
+        x = self._operand(x_port, channels, hist)
+        if x.shape[0] == 1 or x.shape[1] != voices or x.dtype != AUDIO_DTYPE:
+            return None
+        result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
+        start = self.pos - hist
+        return self.owner._launch('adsr_apply', lambda: _native.adsr_apply(start, self.rate, ctl, x, result),
+                                  units=rows * voices)
 
     def _sched_bus(self, node, channels, hist, rows):
         o = self.owner
@@ -1051,14 +1025,10 @@ class _Batch:
         ctl = None
         f2 = top
         if sole(top, fx.RingMod) and not _modulated(top):
-            for env_port, x_port in ((top.right, top.left), (top.left, top.right)):
-                env = env_port.sig
-                if sole(env, ext.ADSR) and not _modulated(env) and isinstance(x_port.sig, fx.SingleCritFilter):
-                    ctl = env.control_rows(lambda bound: self._control_const(bound, bound.name))
-                    f2 = x_port.sig
-                    break
-            else:
+            found = self._sole_envelope(top)
+            if found is None or (found[0], voices) in self._memo or not isinstance(found[1].sig, fx.SingleCritFilter):
                 return None
+            ctl, f2 = self._envelope_rows(found[0]), found[1].sig
         if not sole(f2, fx.SingleCritFilter):
             return None
         f1 = f2.input.sig
@@ -1087,9 +1057,7 @@ class _Batch:
         else:
             history = self.pos - min(CONTEXT, self.pos)
         result = torch.empty((rows, C), dtype=AUDIO_DTYPE, device=runtime.device())
-        need = _native.lib().sig_fused_voice_bus_workspace(voices, rows, C) // 8
-        if o._workspace is None or o._workspace.numel() < need:
-            o._workspace = torch.empty(need, dtype=CTRL_DTYPE, device=runtime.device())
+        o._bus_workspace(voices, rows, C)
         status = o._status_word(f2)                                            # one word for the launch: both designs report here
         kind, t1, t2 = src.kind(), str(f1.type()), str(f2.type())
         o._virtual_history.add(node)
@@ -1122,9 +1090,7 @@ class _Batch:
         if window.dtype != AUDIO_DTYPE or window.shape[1] != voices:
             return None
         result = torch.empty((rows, node.channels), dtype=AUDIO_DTYPE, device=runtime.device())
-        need = _native.lib().sig_fused_voice_bus_workspace(voices, rows, node.channels) // 8
-        if o._workspace is None or o._workspace.numel() < need:
-            o._workspace = torch.empty(need, dtype=CTRL_DTYPE, device=runtime.device())
+        o._bus_workspace(voices, rows, node.channels)
         btype, status = str(flt.type()), o._status_word(flt)
         return o._launch(f'biquad_bus[{btype}{",env" if ctl else ""}]',
                          lambda: _native.biquad_coldstart_bus(btype, self.rate, self.pos, self.N, self.K, CONTEXT, cutoff,
@@ -1148,7 +1114,7 @@ class _Batch:
         return result
 
     def _sched_adsr(self, node, channels, hist, rows):
-        ctl = node.control_rows(lambda bound: self._control_const(bound, bound.name))
+        ctl = self._envelope_rows(node)
         _, voices = broadcast_shape((1, 1), *(r.shape for r in ctl.values()))
         result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
         start = self.pos - hist
@@ -1296,6 +1262,21 @@ class _Batch:
 
     def impure_outputs(self):
         return self._impure.items()
+
+
+def _deal_over_tiles(order: torch.Tensor, voices_per_lane: int) -> torch.Tensor:
+    """the voice permutation of a bus launch from the voices in order of their cutoff (`order`, an int64 index on any device):
+    the j-th group of 64 neighbours in cutoff goes to tile j % tiles, slot j // tiles of the voice tiles of 64 *
+    voices_per_lane, so every wave gets the same mix of slow- and fast-decaying slots (one wave per SIMD: the launch takes as
+    long as its slowest wave).  A ragged last tile stays lane-major"""
+    tile = 64 * voices_per_lane
+    tiles = order.shape[0] // tile
+    perm = order.clone()
+    if tiles:
+        q = torch.arange(tiles * tile, device=order.device)
+        group, lane = q // 64, q % 64
+        perm[((group % tiles) * 64 + lane) * voices_per_lane + group // tiles] = order[q]
+    return perm
 
 
 class _VoiceChain:
@@ -1475,16 +1456,7 @@ class _VoiceChain:
         cut = np.asarray(src._state.value, dtype=np.float64).reshape(-1)
         if cut.size != v or not np.isfinite(cut).all():
             return None
-        order = np.argsort(cut, kind='stable')
-        tile = 64 * voices_per_lane
-        tiles = v // tile
-        perm = order.copy()                                                  # a ragged last tile stays lane-major
-        q = np.arange(tiles * tile)
-        # the j-th group of 64 neighbours in cutoff goes to tile j % tiles, slot j // tiles: every wave gets the same mix
-        # of slow- and fast-decaying slots (one wave per SIMD: the launch takes as long as its slowest wave)
-        group, lane = q // 64, q % 64
-        perm[((group % tiles) * 64 + lane) * voices_per_lane + group // tiles] = order[q]
-        return torch.from_numpy(perm).to(runtime.device())
+        return _deal_over_tiles(torch.from_numpy(np.argsort(cut, kind='stable')), voices_per_lane).to(runtime.device())
 
     def live_key(self, bus_node=None):
         """identities of the resident control tensors (and the bus gains) as they are NOW -- `resident()` re-uploads an
@@ -1568,9 +1540,7 @@ class _VoiceChain:
         if pan is not None and pan.shape[1] != v:
             return None
         status = o._status_word(self.filt)
-        need = _native.lib().sig_fused_voice_bus_workspace(v, rows, bus_c) // 8
-        if o._workspace is None or o._workspace.numel() < need:
-            o._workspace = torch.empty(need, dtype=CTRL_DTYPE, device=dev)
+        o._bus_workspace(v, rows, bus_c)
         if self.general:
             if bus_c not in (1, 2):
                 return None
@@ -1594,13 +1564,7 @@ class _VoiceChain:
                     elif not swept:
                         index = self.cutoff_order(controls, vpl)
                     else:
-                        tile, tiles = 64 * vpl, v // (64 * vpl)
-                        order = torch.argsort(controls[2][0], stable=True)
-                        index = order.clone()                                    # (a ragged last tile stays lane-major)
-                        if tiles:
-                            q = torch.arange(tiles * tile, device=dev)
-                            group, lane = q // 64, q % 64
-                            index[((group % tiles) * 64 + lane) * vpl + group // tiles] = order[q]
+                        index = _deal_over_tiles(torch.argsort(controls[2][0], stable=True), vpl)
                     pick = lambda t: t if t is None or index is None or t.shape[1] != v else t.index_select(1, index).contiguous()
                     held = o._tremolo_order = (key, (controls[0], controls[1], controls[2], pan), index,
                                                [pick(controls[0]), pick(controls[1]), None if swept else pick(controls[2])], pick(pan))
@@ -1907,6 +1871,12 @@ class _VoiceProgram:
         self.code.append(('Const', 0, self._param(len(self.controls) - 1), 0, 0))
         return 0
 
+    def _osc_slot(self, n, below: int) -> int:
+        if len(self.oscs) >= _native.VP_MAX_OSCS:
+            raise _NoProgram('more oscillators than the machine has slots')
+        self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
+        return len(self.oscs) - 1
+
     def _emit(self, n, below: int) -> int:
         """code that leaves the node's sample in the accumulator; returns the filters in series up to and including it"""
         if isinstance(n, ext.Tap):
@@ -1929,17 +1899,11 @@ class _VoiceProgram:
             self.code.append(('Const', 0, self._param(len(self.controls) - 1), 0, 0))
             depth = 0
         elif isinstance(n, osc.Osc):
-            if len(self.oscs) >= _native.VP_MAX_OSCS:
-                raise _NoProgram('more oscillators than the machine has slots')
-            self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
-            self.code.append(('Osc', _native.OSC_KINDS[n.kind()], len(self.oscs) - 1, 0, 0))
+            self.code.append(('Osc', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, 0))
             depth = 0
         elif isinstance(n, ext.PMOsc):
             depth = self._emit(n.mod.sig, below)                               # the modulator's sample: in the accumulator
-            if len(self.oscs) >= _native.VP_MAX_OSCS:
-                raise _NoProgram('more oscillators than the machine has slots')
-            self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
-            self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], len(self.oscs) - 1, self._param(self._control(n.index, below)), 0))
+            self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), self._param(self._control(n.index, below)), 0))
         elif isinstance(n, noise.White):
             if len(self.seeds) >= 2 or n.channels != self.voices:
                 raise _NoProgram('White: two per program, as wide as the voices')
@@ -1976,27 +1940,19 @@ class _VoiceProgram:
                 self.temps_free.append(t)
                 del self.saved[n.right.sig]
             depth = max(left, right)
-        elif isinstance(n, fx.SingleCritFilter):
+        elif isinstance(n, fx.CritFilter):
             src = n.input.sig
             if src is None or not src.get_state().enabled:
                 raise _NoProgram('filter without an input')                    # (the per-node schedule raises the reference's error)
             depth = self._emit(src, below + 1) + 1
-            if len(self.filters) >= _native.VP_MAX_FILTERS:
+            band = isinstance(n, fx.DoubleCritFilter)                          # ONE cached node: both slots at its level
+            edges = (n.low, n.high) if band else (n.cutoff,)
+            if len(self.filters) + len(edges) > _native.VP_MAX_FILTERS:
                 raise _NoProgram('more filters than the machine has slots')
-            self.filters.append((self._control(n.cutoff, below), str(n.type()), depth, n))
-            self.code.append(('Filter', 0, len(self.filters) - 1, 0, 0))
-        elif isinstance(n, fx.DoubleCritFilter):
-            src = n.input.sig
-            if src is None or not src.get_state().enabled:
-                raise _NoProgram('filter without an input')
-            depth = self._emit(src, below + 1) + 1
-            if len(self.filters) + 2 > _native.VP_MAX_FILTERS:
-                raise _NoProgram('more filters than the machine has slots')
-            btype = str(n.type())                                              # ONE cached node: both slots at its level
-            self.filters.append((self._control(n.low, below), btype, depth, n))
-            self.filters.append((self._control(n.high, below), btype, depth, n))
-            self.code.append(('Band', 0, len(self.filters) - 2, 0, 0))
-            self.bands.append(n)
+            self.filters += [(self._control(p, below), str(n.type()), depth, n) for p in edges]
+            self.code.append(('Band' if band else 'Filter', 0, len(self.filters) - len(edges), 0, 0))
+            if band:
+                self.bands.append(n)
         else:
             raise _NoProgram(f'no voice-program instruction for {n.cls_name()}')
         self.depth_of[n] = depth
@@ -2036,14 +1992,8 @@ class _VoiceProgram:
                 groups.setdefault(bool(small and below >= 1), []).append(i)
         for inner, members in groups.items():
             srcs = tuple(self.controls[i][0].sig for i in members)
-            key = ('voice-program', tuple(id(x) for x in srcs), K, lead, small)
-            held = o._ctl_programs.get(key)
-            if held is None or held[0] != graph_clock.version or not held[1].current():
-                if len(o._ctl_programs) > 16:
-                    o._ctl_programs.clear()
-                held = o._ctl_programs[key] = (graph_clock.version, _ProgramRows(srcs, K, lead, small, channels=self.voices,
-                                                                                 status=o._status_word))
-            rows = held[1]
+            rows = o._control_program(('voice-program', tuple(id(x) for x in srcs), K, lead, small),
+                                      lambda: _ProgramRows(srcs, K, lead, small, channels=self.voices, status=o._status_word))
             if not small:
                 ahead = [front] + hist                                         # where the rows in front of the K blocks are read
                 b._check_windowed(rows.main, ahead)
@@ -2078,7 +2028,7 @@ class _VoiceProgram:
                 raise IndexError(f'index {tensors[cut].shape[1]} is out of bounds for axis 1 with size {tensors[cut].shape[1]}')   # fx.py:99
         adsr = None
         if self.adsr is not None:
-            adsr = self.adsr.control_rows(lambda bound: b._control_const(bound, bound.name))
+            adsr = b._envelope_rows(self.adsr)
             if any(r.shape[1] not in (1, v) for r in adsr.values()):
                 raise _NoProgram('envelope rows of another width than the voices')
         oscs = [(tensors[h], tensors[p] if p is not None else None) for h, p in self.oscs]
@@ -2086,9 +2036,7 @@ class _VoiceProgram:
         filters = [(tensors[c], t, level) for c, t, level, _ in self.filters]
         status = o._status_word(self.filters[0][3]) if self.filters else None
         if bus:
-            need = _native.lib().sig_fused_voice_bus_workspace(v, out.shape[0], out.shape[1]) // 8
-            if o._workspace is None or o._workspace.numel() < need:
-                o._workspace = torch.empty(need, dtype=CTRL_DTYPE, device=runtime.device())
+            o._bus_workspace(v, out.shape[0], out.shape[1])
         seeds = tuple(self.seeds + [0, 0])[:2]
         if self.depth:
             o._virtual_history.add(self.top)

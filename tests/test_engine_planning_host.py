@@ -95,3 +95,33 @@ def test_block_cache_matches_the_oracle_cache_on_random_request_sequences(reques
         want = ref.respond(position * 4, frames * 4, channels, 48000)
         assert tuple(got.shape) == want.shape and np.array_equal(got.numpy(), want)
     assert node.evals == ref.evals and len(node._block_cache) == len(ref._cache) <= 16
+
+
+@pytest.mark.parametrize('voices,voices_per_lane', ((1024, 8), (1024, 2), (1024, 1), (1000, 4), (192, 2), (100, 2), (64, 1), (7, 8)))
+def test_cutoff_order_permutation_is_the_two_expressions_it_replaced(voices, voices_per_lane):
+    """`_deal_over_tiles` against the two index expressions it replaced -- the numpy one of `_VoiceChain.cutoff_order` (host
+    cutoffs) and the torch one of the swept branch of `launch_bus` (device cutoffs) -- element for element: whole tiles, a
+    ragged last tile (1000 / 256, 100 / 128) and fewer voices than one tile (tiles == 0)"""
+    from signals_amd.engine import _deal_over_tiles
+    cut = np.random.default_rng(voices + voices_per_lane).uniform(200.0, 8000.0, voices)
+    cut[::7] = cut[3]                                              # ties: the stable sort decides
+    tile = 64 * voices_per_lane
+    tiles = voices // tile
+    # numpy, as `cutoff_order` had it
+    order = np.argsort(cut, kind='stable')
+    perm = order.copy()
+    q = np.arange(tiles * tile)
+    group, lane = q // 64, q % 64
+    if tiles:                                                      # (with no whole tile the assignment was an empty one)
+        perm[((group % tiles) * 64 + lane) * voices_per_lane + group // tiles] = order[q]
+    got = _deal_over_tiles(torch.from_numpy(np.argsort(cut, kind='stable')), voices_per_lane)
+    assert got.dtype == torch.int64 and np.array_equal(got.numpy(), perm)
+    # torch, as `launch_bus` had it
+    order_t = torch.argsort(torch.from_numpy(cut), stable=True)
+    index = order_t.clone()
+    if tiles:
+        q = torch.arange(tiles * tile)
+        group, lane = q // 64, q % 64
+        index[((group % tiles) * 64 + lane) * voices_per_lane + group // tiles] = order_t[q]
+    assert torch.equal(_deal_over_tiles(order_t, voices_per_lane), index)
+    assert sorted(got.tolist()) == list(range(voices))             # a permutation
