@@ -280,6 +280,45 @@ def adsr(position: int, frames: int, rate: int, attack, decay, sustain, release,
     return np.where(w < 0, held(t), hold_off * rel)
 
 
+NOISE_FRAME_STEP = 0x9E3779B97F4A7C15      # SplitMix64's increment: one step per frame
+NOISE_PAIR_STEP = 0xD1B54A32D192ED03       # one step per pair of channels
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    """SplitMix64's output function on uint64 arrays (numpy integer arithmetic wraps modulo 2^64)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def white_hash(seed: int, position: int, frames: int, pairs: int) -> np.ndarray:
+    """uint64 (frames, pairs): mix64(seed + frame * 0x9E3779B97F4A7C15 + pair * 0xD1B54A32D192ED03 mod 2^64) -- with seed 0
+    and pair 0 the frame-th output of SplitMix64 seeded with 0."""
+    if not 0 <= seed < 1 << 64:
+        raise ValueError('seed must fit an unsigned 64-bit word')
+    frame = np.array([((position + i) * NOISE_FRAME_STEP + seed) % (1 << 64) for i in range(frames)], dtype=np.uint64)
+    pair = np.array([(j * NOISE_PAIR_STEP) % (1 << 64) for j in range(pairs)], dtype=np.uint64)
+    return _mix64(frame[:, None] + pair[None, :])
+
+
+def white_bits(seed: int, position: int, frames: int, channels: int) -> np.ndarray:
+    """uint32 (frames, channels): channels 2m and 2m + 1 share the hash of pair m -- the even one takes its low word, the
+    odd one its high word."""
+    h = white_hash(seed, position, frames, (channels + 1) // 2)
+    words = np.empty((frames, 2 * h.shape[1]), dtype=np.uint32)
+    words[:, 0::2] = (h & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    words[:, 1::2] = (h >> np.uint64(32)).astype(np.uint32)
+    return words[:, :channels]
+
+
+def white(seed: int, position: int, frames: int, channels: int) -> np.ndarray:
+    """Build-defined (the reference draws np.random.rand from the global unseeded generator, noise.py:22-23: statistics
+    only).  Uniform on [0, 1), a function of (seed, frame, channel) alone: the top 24 bits of the channel's 32-bit word
+    (`white_bits`) times 2^-24 -- exact in float32, so the same value whichever type it is stored as.  This restatement is
+    the definition (include/signals_amd.h: sig_white_noise; signals_amd/csrc/sig_noise.h)."""
+    return (white_bits(seed, position, frames, channels) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
 def mix_matrix(x: np.ndarray, m: np.ndarray) -> np.ndarray:
     """Build-defined: out[n, 64g:64g+64] = x[n, 64g:64g+64] @ M, M (64,64).  Parity unpinned."""
     n, v = x.shape
@@ -442,6 +481,18 @@ class Adsr(Node):
 
     def eval(self, position, frames, channels, rate):
         return adsr(position, frames, rate, **self.rows)
+
+
+class White(Node):
+    """noise.py:13-23 with the build-defined generator: an ExplicitChannelsEmitter -- it answers `channels` columns whatever
+    the request's width -- behind a block cache like Osc."""
+
+    def __init__(self, seed: int = 0, channels: int = 1):
+        super().__init__()
+        self.seed, self.channels = seed, channels
+
+    def eval(self, position, frames, channels, rate):
+        return white(self.seed, position, frames, self.channels)
 
 
 class MixMatrix(Node):

@@ -28,7 +28,9 @@ class Noise(ExplicitChannelsEmitter, BlockCachingEmitter, abc.ABC):
 class White(Noise):
     @state
     class State(Noise.State):
-        seed: int = attr.ib(validator=attrs.validators.ge(0), default=0)
+        # a uint64 on every route (an argument, a struct field, an instruction's pointer field): larger values have no one meaning
+        seed: int = attr.ib(validator=[attrs.validators.ge(0), attrs.validators.le(2 ** 64 - 1)], default=0,
+                            on_setattr=attr.setters.validate)
 
     def _eval(self, request: Request) -> torch.Tensor:
         frames, channels = request.loc.shape
