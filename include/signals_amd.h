@@ -85,6 +85,24 @@ int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t r
                     const void* mod, int32_t mod_dtype, int64_t mod_ld, int32_t mod_stride,
                     void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Wavetable oscillator, chain/ext.py Wavetable: sig_osc_bank_mod's phase looked up in a table of W single-cycle waveforms of T
+ * points each, `table` float32 (T, W) row-major in device memory, T a power of two >= 2, W >= 1, T * W <= SIG_TABLE_MAX_POINTS:
+ *   t = (position + n * position_step) / rate * hertz[v] + phase[v]        (f64, that order)
+ *   m = np.mod(t, 1.0);  u = m * T;  i = floor(u);  f = u - i              (m == 1.0 for t in (-2^-54, 0): entry 0, f == 0)
+ *   w = clip(floor(select[v]), 0, W - 1)                                   (NaN -> 0; select NULL = unplugged = column 0)
+ *   out[n,v] = tbl[i & (T-1), w] + f * (tbl[(i+1) & (T-1), w] - tbl[i & (T-1), w])      tbl = (double) table, every operation rounded
+ * `select` rows like hertz / phase (per block with rows_per_param).  Position-pure.  The float64 value in front of the store is
+ * bit-exact against numpy.  A null table, T not a power of two, T * W over the cap or out_ld < voices: hipErrorInvalidValue,
+ * nothing launched; rows == 0: no launch. */
+enum { SIG_TABLE_MAX_POINTS = 16384 };
+int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                       int32_t voices, int32_t rows_per_param,
+                       const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                       const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                       const double* select, int32_t select_stride, int64_t select_row_stride,
+                       const float* table, int32_t table_points, int32_t table_waves,
+                       void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):
@@ -526,6 +544,12 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *   OSCPM  acc = wave_kind(n / rate * hertz[a] + phase[a] + params[b] * acc)     oscillator slot a, index = parameter slot b (a
  *          phase-modulation carrier: the modulator's code runs first and leaves its sample in the accumulator; a program with both
  *          BAND and OSCPM is refused, hipErrorInvalidValue: the interpreter is built with either, not both)
+ *   OSCTABLE acc = wavetable lookup (sig_osc_bank_table's expression) at n / rate * hertz[a] + phase[a] in table slot b of the
+ *          `tables` argument of sig_voice_program_ex, column = params[c] (select rows), c == -1: unplugged = column 0.  The tables
+ *          sit in LDS for the whole launch.  m = t - floor(t) is one v_fract_f64 here, like the other fused oscillators: it differs
+ *          from the definition only for t in (-2^-54, 0), where it reads the table's last segment at f = 1 - 2^-53 instead of entry 0
+ *          (the two agree to one ulp of a table step).  A program that combines OSCTABLE with BAND or OSCPM is refused,
+ *          hipErrorInvalidValue; so is one launched without its tables
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -546,9 +570,11 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * sig_fused_voice_bus_workspace(voices, rows, bus_channels) bytes.  f64 arithmetic, no float32 rounding between the nodes.
  * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF. */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
-       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12 };
+       SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
+       SIG_VP_OSCTABLE = 13 };
+enum { SIG_VP_MAX_TABLES = 2 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE: c may be -1 */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];
@@ -565,6 +591,16 @@ int sig_voice_program(const sig_voice_program_t* program, int32_t rate, int64_t 
                       int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
                       const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                       double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream);
+/* sig_voice_program with the wavetables of its OSCTABLE instructions: up to SIG_VP_MAX_TABLES tables, each float32 (points, waves)
+ * row-major in device memory under sig_osc_bank_table's rules, together at most SIG_TABLE_MAX_POINTS entries (they share the LDS of
+ * a workgroup).  `tables` (HOST memory) may be NULL for a program without the instruction: sig_voice_program is this call with NULL. */
+typedef struct { int32_t n_tables; struct { const float* ptr; int32_t points, waves; } table[SIG_VP_MAX_TABLES]; } sig_vp_tables_t;
+int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                         int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                         int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                         const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                         double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                         const sig_vp_tables_t* tables);
 /* Tuning / test hook: force the voices per lane (1, 2; 0 = heuristic; ignored where the program does not fit the variant) and
  * the blocks per lane (0 = heuristic) of sig_voice_program.  Process-wide. */
 int sig_voice_program_set_tuning(int32_t voices_per_lane, int32_t blocks_per_lane);

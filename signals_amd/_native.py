@@ -49,9 +49,11 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
+VP_MAX_TABLES = 2
+TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable (of a voice program's tables together)
 
 
 class VpIns(ctypes.Structure):
@@ -71,6 +73,15 @@ class VoiceProgramT(ctypes.Structure):
                 ('filter_level', ctypes.c_int32 * VP_MAX_FILTERS),
                 ('n_temps', ctypes.c_int32), ('depth', ctypes.c_int32),
                 ('adsr', ctypes.c_void_p * 6), ('adsr_stride', ctypes.c_int32 * 6), ('noise_seed', ctypes.c_uint64 * 2)]
+
+
+class VpTable(ctypes.Structure):
+    _fields_ = [('ptr', ctypes.c_void_p), ('points', ctypes.c_int32), ('waves', ctypes.c_int32)]
+
+
+class VpTablesT(ctypes.Structure):
+    """sig_vp_tables_t (host memory)"""
+    _fields_ = [('n_tables', ctypes.c_int32), ('table', VpTable * VP_MAX_TABLES)]
 
 
 class Operand(ctypes.Structure):
@@ -98,6 +109,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_mod': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, vp, i32, i64, vp],
         'sig_osc_bank_pm': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
                             vp, i32, i64, i32, vp, i32, i64, vp],
+        'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
         'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
@@ -138,6 +150,8 @@ def _argtypes() -> dict:
         'sig_control_program_attach': [p32, i32, ctypes.c_char_p, p32],
         'sig_control_program_attached': [i32] + program,
         'sig_voice_program': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out,
+        'sig_voice_program_ex': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out
+                                + [ctypes.POINTER(VpTablesT)],
         'sig_voice_program_set_tuning': [i32, i32],
         'sig_voice_program_geometry': [i32, i32, i32, i32, i32, i32, i32, i32, p32, p32],
         'sig_voice_program_args_size': [],
@@ -344,6 +358,31 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
     _check(lib().sig_osc_bank_pm(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
                                  *params[0:3], *params[4:7], *params[8:11], mp, mdt, mld, mcs,
                                  out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_pm')
+    return out
+
+
+def _table(table: torch.Tensor):
+    """(ptr, points, waves) of a wavetable: float32 (T, W) contiguous on the device, T a power of two >= 2, T * W within the cap"""
+    if table is None or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise NativeError('a wavetable is a contiguous float32 (points, waves) tensor')
+    points, waves = table.shape
+    if points < 2 or points & (points - 1) or waves < 1 or points * waves > TABLE_MAX_POINTS:
+        raise NativeError(f'wavetable {tuple(table.shape)}: points a power of two >= 2, points * waves <= {TABLE_MAX_POINTS}')
+    return table.data_ptr(), points, waves
+
+
+def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, select: torch.Tensor | None,
+                   table: torch.Tensor, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- wavetable oscillator (sig_osc_bank_table): the (T, W) float32 `table` read with linear interpolation at
+    np.mod(n / rate * hertz + phase, 1) * T, column clip(floor(select), 0, W - 1).  hertz / phase / select: (1|P, V|1) f64 like `osc_bank`."""
+    _gpu(hertz, phase, select, table, out)
+    _audio(out, 'osc out')
+    rows, voices = out.shape
+    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (select, 'select'), form=_ctrl_rows)
+    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'select'))
+    _check(lib().sig_osc_bank_table(position, step, rate, rows, voices, rows_per_param,
+                                    *params[0:3], *params[4:7], *params[8:11], *_table(table),
+                                    out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_table')
     return out
 
 
@@ -940,19 +979,19 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   block_frames: int, nblocks: int, context: int, voices: int, control_rows: int, hist_positions: list,
                   out: torch.Tensor, bus_gains: torch.Tensor | None = None, bus: bool = False,
                   adsr: dict | None = None, noise_seeds: tuple = (0, 0), workspace: torch.Tensor | None = None,
-                  status: torch.Tensor | None = None, blocks_before: int = 0) -> torch.Tensor:
-    """One launch for a whole per-voice graph (sig_voice_program).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
+                  status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None) -> torch.Tensor:
+    """One launch for a whole per-voice graph (sig_voice_program_ex; `tables`: the float32 (T, W) wavetables of its OscTable words).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
     'lp' | 'hp', level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
     tensors = [t for pair in oscs for t in pair] + list(params) + [f[0] for f in filters] + list((adsr or {}).values())
-    _gpu(out, bus_gains, workspace, status, *tensors)
+    _gpu(out, bus_gains, workspace, status, *tensors, *(tables or ()))
     _audio(out, 'voice program out')
     rows = block_frames * nblocks
     if out.dtype != torch.float32 or out.shape[0] != rows:
         raise NativeError(f'voice program out must be float32 ({rows}, .), got {tuple(out.shape)} {out.dtype}')
     if len(code) > VP_MAX_INS or len(oscs) > VP_MAX_OSCS or len(params) > VP_MAX_PARAMS or len(filters) > VP_MAX_FILTERS \
-            or n_temps > VP_MAX_TEMPS or len(hist_positions) > VP_MAX_HIST:
+            or n_temps > VP_MAX_TEMPS or len(hist_positions) > VP_MAX_HIST or len(tables or ()) > VP_MAX_TABLES:
         raise NativeError('voice program larger than the machine')
     P = _program_struct(code)
     P.n_oscs = len(oscs)
@@ -981,15 +1020,22 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
         workspace = _bus_workspace(workspace, voices, rows, C, out.device)
     elif out.shape[1] != voices:
         raise NativeError(f'voice program out has {out.shape[1]} channels for {voices} voices')
-    _check(lib().sig_voice_program(ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows,
-                                   len(hist_positions), hist, blocks_before, gp, gld, C,
-                                   _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out)), 'sig_voice_program')
+    held = None
+    if tables:
+        held = VpTablesT()
+        held.n_tables = len(tables)
+        for k, t in enumerate(tables):
+            held.table[k] = VpTable(*_table(t))
+    _check(lib().sig_voice_program_ex(ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows,
+                                      len(hist_positions), hist, blocks_before, gp, gld, C,
+                                      _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out),
+                                      ctypes.byref(held) if held is not None else None), 'sig_voice_program_ex')
     return out
 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | (c << 16) for op, kind, a, b, c in code]
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's c = -1: 15)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

@@ -159,6 +159,66 @@ class PMTriangle(PMOsc):
         return 'Triangle'
 
 
+def _validate_table(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and new_value.shape[0] >= 2 and new_value.shape[0] & (new_value.shape[0] - 1) == 0 and new_value.shape[1] >= 1
+          and new_value.shape[0] * new_value.shape[1] <= _native.TABLE_MAX_POINTS)
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a 2D real array (points, waves), points a power of two >= 2, points * waves <= '
+                            f'{_native.TABLE_MAX_POINTS}')
+
+
+class Wavetable(BlockCachingEmitter, ImplicitChannels):
+    """Wavetable oscillator: the state `table` holds W single-cycle waveforms of T points each as a (T, W) array (the
+    reference's (frames, channels) orientation), read with linear interpolation at the oscillator phase of chain/osc.py.
+    With tbl = float32(table) widened to float64, in float64 and every operation rounded:
+        t = frame_range / rate * hertz + phase;  m = np.mod(t, 1.0);  u = m * T;  i = floor(u);  f = u - i
+        w = clip(floor(select), 0, W - 1)                                  (per voice; NaN and unplugged: column 0)
+        out = tbl[i & (T-1), w] + f * (tbl[(i+1) & (T-1), w] - tbl[i & (T-1), w])
+    (kernel: sig_osc_bank_table; restated in numpy by tests/wavetable_reference.py).  Ports, all block-rate: hertz, phase,
+    select.  T is a power of two >= 2, T * W <= 16384; integer arrays (what a .sigs value arrives as) are converted; the device
+    copy is float32 and follows in-place edits of the array.  Position-pure: no carried phase.  Not an `osc.Osc`: that means a
+    closed-form leaf with two control ports to the engine's fused kernels.
+    Out of scope: the node inside a block-rate control path (the batched engine answers NotBatchable with the reason and the
+    graph keeps the eager path, which serves frames == 1 in float64); a phase-modulated wavetable; morphing between columns
+    (`fx.Mix` of two Wavetables does that); per-voice private tables; the closed-form and row-walker fused kernels, which keep
+    matching `osc.Osc` only."""
+    hertz: Receiver.BoundPort = port('hertz')
+    phase: Receiver.BoundPort = port('phase')
+    select: Receiver.BoundPort = port('select')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        table: np.ndarray = attr.ib(factory=lambda: np.array([[0.0], [1.0], [0.0], [-1.0]]), validator=_validate_table,
+                                    on_setattr=attr.setters.validate)
+
+    def __init__(self):
+        super().__init__()
+        self._resident = None
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR
+
+    def resident_table(self) -> torch.Tensor:
+        table = self._state.table
+        held = self._resident
+        if held is None or held[0] is not table or not held[1].matches(table):
+            host = np.ascontiguousarray(table, dtype=np.float32)
+            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
+        return held[2]
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        phase = as_control(self.phase.forward_at_block_rate(request))
+        hertz = as_control(self.hertz.forward_at_block_rate(request))
+        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
+        loc = request.loc
+        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, select.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
+        return _native.osc_bank_table(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
+
+
 def _validate_matrix(instance, attribute, new_value):
     if not (isinstance(new_value, np.ndarray) and new_value.shape == (64, 64)):
         raise BadStateValue(instance, attribute.name, new_value, 'must be a (64, 64) array')

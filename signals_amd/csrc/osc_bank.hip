@@ -237,7 +237,150 @@ int run_pm(int kind, const OscArgs& a, const PmArgs& m, void* out, int32_t out_d
     return (int)hipErrorInvalidValue;
 }
 
+// ---- wavetable: out = lerp of a (T, W) float32 table (W single-cycle waveforms of T points, T a power of two) at
+// m = np.mod(n / rate * hertz + phase, 1), column w = clip(floor(select), 0, W - 1) per voice (chain/ext.py Wavetable).
+// A 512-thread workgroup stages the whole table in LDS once -- column-major, T + 1 floats per column, the guard entry
+// tab[w][T] = tab[w][0] -- and then walks `groups` 16-row groups per wave of its 64 * VEC voices, so the staging (<= 64 KiB
+// read from L2) is amortised over up to 1 MiB of stores.  The guard makes the two lerp operands ONE paired read at a single
+// address (i & (T - 1), + 1: the last segment wraps without a second mask, and m == 1.0 lands on entry 0 with f == 0), and the
+// odd column stride T + 1 keeps equal indices of different columns on different banks.  Lanes, rows and stores as in
+// osc_bank_kernel.  64 KiB of table: two workgroups per CU = 16 waves, four per SIMD.
+// Arithmetic: the definition's, every operation rounded once in its order (t - floor(t) is np.mod(t, 1), sig_npmod_pow2;
+// m * T, floor, u - i are exact), so the float64 value in front of the store has numpy's bits.
+// Roofline: 4 B written per voice-sample (f32).
+constexpr int kTableWaves = 8;
+
+struct TableArgs {
+    const float* table; int T, W;                                  // (T, W) row-major, device memory
+    const double* select; int ss; int64_t srs;                     // (1|P, V|1) f64 like hertz / phase; NULL: unplugged = column 0
+    int groups;                                                    // 16-row groups per wave
+};
+
+template <int VEC, typename OUT>
+__global__ __launch_bounds__(64 * kTableWaves) void osc_bank_table_kernel(OscArgs a, TableArgs tb, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    extern __shared__ float tab[];                                 // [W][T + 1]
+    const int T = tb.T, W = tb.W, S = T + 1;
+    // coalesced read of row-major (T, W), element k = i * W + w to column w, row i (LDS stride S is odd); (i, w) advance by a
+    // workgroup's worth of elements per step, so the division is paid once per thread, not per element
+    constexpr int kStep = 64 * kTableWaves;
+    const int di = kStep / W, dw = kStep - di * W;
+    int si = (int)threadIdx.x / W, sw = (int)threadIdx.x - si * W;
+    for (int k = threadIdx.x; k < T * W; k += kStep) {
+        tab[sw * S + si] = tb.table[k];
+        si += di; sw += dw;
+        if (sw >= W) { sw -= W; ++si; }
+    }
+    for (int w = threadIdx.x; w < W; w += 64 * kTableWaves) tab[w * S + T] = tb.table[w];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int vt = blockIdx.x % voice_tiles;
+    const int64_t rt = blockIdx.x / voice_tiles;
+    const int v0 = (vt * SIG_WAVE + lane) * VEC;
+    const double scale = (double)T;
+    const int mask = T - 1;
+
+    double hz[VEC], ph[VEC];
+    int col[VEC];                                                  // the voice's column: its first float in `tab`
+    int64_t loaded = -1;                                           // parameter row currently in registers
+    for (int g = 0; g < tb.groups; ++g) {
+        const int64_t r0 = ((rt * tb.groups + g) * kTableWaves + wave) * kRowsPerWave;
+        if (r0 >= a.rows) break;                                   // wave-uniform
+        const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+        for (int j = 0; j < kRowsPerWave; ++j) {
+            const int64_t row = r0 + j;
+            if (row >= a.rows) break;                              // wave-uniform
+            const int64_t prow = a.rpp ? row / a.rpp : 0;          // wave-uniform
+            if (prow != loaded) {
+                loaded = prow;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const int v = v0 + i;
+                    hz[i] = (v < a.voices) ? a.hertz[prow * a.hrs + (int64_t)v * a.hs] : 0.0;
+                    ph[i] = (v < a.voices && a.phase) ? a.phase[prow * a.prs + (int64_t)v * a.ps] : 0.0;
+                    const double s = (v < a.voices && tb.select) ? floor(tb.select[prow * tb.srs + (int64_t)v * tb.ss]) : 0.0;
+                    const int w = (s >= 1.0) ? ((s >= (double)(W - 1)) ? W - 1 : (int)s) : 0;     // clip; NaN -> 0
+                    col[i] = w * S;
+                }
+            }
+            const double q = sig_readlane_f64(q_lane, j);
+            OUT y[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const double t = q * hz[i] + ph[i];                // two roundings, like numpy
+                const double u = sig_npmod_pow2<1>(t) * scale;     // in [0, T]
+                const double fl = floor(u);
+                const double f = u - fl;
+                const int at = col[i] + ((int)fl & mask);          // <= col + T - 1, so at + 1 reaches the guard at most
+                const double lo = (double)tab[at], hi = (double)tab[at + 1];
+                y[i] = (OUT)(lo + f * (hi - lo));
+            }
+            OUT* dst = out + row * ld + v0;
+            if (VEC == 4) {
+                if (v0 < a.voices) {                               // voices % 4 == 0 on this path
+                    typename sig_vec4<OUT>::type o;
+                    o.x = y[0]; o.y = y[1]; o.z = y[2]; o.w = y[3];
+                    *reinterpret_cast<typename sig_vec4<OUT>::type*>(dst) = o;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    if (v0 + i < a.voices) dst[i] = y[i];
+            }
+        }
+    }
+}
+
+template <typename OUT>
+int launch_table(const OscArgs& a, TableArgs tb, OUT* out, int64_t ld, hipStream_t stream)
+{
+    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
+                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
+    const int span = SIG_WAVE * (vec4 ? 4 : 1);
+    const int voice_tiles = (a.voices + span - 1) / span;
+    const int64_t rows_per_pass = (int64_t)kRowsPerWave * kTableWaves;
+    const int64_t passes = (a.rows + rows_per_pass - 1) / rows_per_pass;
+    // as many row groups per wave as still leave two workgroups for every CU of an MI355X (the staging is paid per workgroup)
+    tb.groups = 8;
+    while (tb.groups > 1 && ((passes + tb.groups - 1) / tb.groups) * voice_tiles < 512) tb.groups >>= 1;
+    const int64_t nwg = ((passes + tb.groups - 1) / tb.groups) * voice_tiles;
+    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)(tb.T + 1) * tb.W * sizeof(float);
+    if (vec4)
+        osc_bank_table_kernel<4, OUT><<<(unsigned)nwg, 64 * kTableWaves, lds, stream>>>(a, tb, out, ld, voice_tiles);
+    else
+        osc_bank_table_kernel<1, OUT><<<(unsigned)nwg, 64 * kTableWaves, lds, stream>>>(a, tb, out, ld, voice_tiles);
+    return sig_launch_status();
+}
+
 }  // namespace
+
+extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                                  int32_t voices, int32_t rows_per_param,
+                                  const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                                  const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                                  const double* select, int32_t select_stride, int64_t select_row_stride,
+                                  const float* table, int32_t table_points, int32_t table_waves,
+                                  void* out, int32_t out_dtype, int64_t out_ld, void* stream)
+{
+    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
+    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
+                  (select_stride == 0 || select_stride == 1));
+    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && select_row_stride >= 0);
+    SIG_CHECK_ARG(table != nullptr && table_points >= 2 && (table_points & (table_points - 1)) == 0 && table_waves >= 1 &&
+                  (int64_t)table_points * table_waves <= SIG_TABLE_MAX_POINTS);
+    SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
+    if (rows == 0 || voices == 0) return 0;
+    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
+                    phase, phase_stride, phase_row_stride, rows_per_param};
+    const TableArgs tb{table, table_points, table_waves, select, select_stride, select_row_stride, 1};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_dtype == SIG_F32) return launch_table<float>(a, tb, static_cast<float*>(out), out_ld, s);
+    return launch_table<double>(a, tb, static_cast<double*>(out), out_ld, s);
+}
 
 extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
                                int32_t voices, int32_t rows_per_param,

@@ -71,6 +71,11 @@ struct VpArgs {
     int* status;
 };
 
+// The wavetables of the OscTable instruction: (T, W) float32, staged in LDS.  A kernel parameter of its own that only the TAB
+// variant has, so that the argument block -- and with it the code -- of every other instantiation is what it was without the op.
+struct VpTables { const float* ptr[SIG_VP_MAX_TABLES]; int T[SIG_VP_MAX_TABLES], W[SIG_VP_MAX_TABLES]; };
+struct VpNoTables {};
+
 // f(integral_constant<int, i>) for a wave-uniform i < N: a scalar switch, so arrays indexed inside stay in registers
 template <int N, typename F>
 __device__ __forceinline__ void with_index(int i, F&& f) {
@@ -162,8 +167,11 @@ template <bool SMALL> struct VpLimits {
 // BAND: the Band instruction (band filters' per-voice middle taps and their design; a variant of its own, so that programs
 // without one keep the registers they had -- the band state and its inlined design cost the SMALL file ~200 B of scratch per lane)
 // PM: the OscPM instruction (phase-modulation carriers), a variant of its own for the same reason
-template <int VPT, bool SMALL, int C, bool BAND, bool PM>
-__device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave)
+// TAB: the OscTable instruction (wavetable oscillators, ext.py Wavetable), likewise; `tab`: the launch's tables in LDS, each
+// column-major with T + 1 floats per column (the guard entry [T] = [0], osc_bank.hip), table 1 behind table 0
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, typename TABLES>
+__device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
+                                        [[maybe_unused]] const float* tab)
 {
     constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
     constexpr bool BUS = C > 0;
@@ -473,6 +481,47 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #endif
             const int op = (int)(w & 31u), kind = (int)((w >> 5) & 7u), ia = (int)((w >> 8) & 15u), ib = (int)((w >> 12) & 15u),
                       ic = (int)((w >> 16) & 15u);
+            // OscTable is dispatched in front of the switch, and only in the TAB variant: a case of its own, even an empty one, changes
+            // the code of every other instantiation (the compare chain of the dispatch), and those are to stay what they were
+            if constexpr (TAB) {
+                if (op == SIG_VP_OSCTABLE) {                                   // the Osc handler's phase, looked up in table slot ib (ext.py Wavetable)
+                    // m = t - floor(t) as v_fract_f64: not the definition's 1.0 for t in (-2^-54, 0) but the largest double below
+                    // it, i.e. the last segment at f = 1 - T 2^-53 instead of entry 0 at f = 0 -- one rounding of a table step apart
+                    const int slot = ib & (SIG_VP_MAX_TABLES - 1);
+                    const int TT = tb.T[slot], W = tb.W[slot], S = TT + 1;
+                    const int first = slot ? (tb.T[0] + 1) * tb.W[0] : 0;
+                    int col[VPT];
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) col[i] = first;
+                    if (ic < NP) {                                             // (15: select unplugged, column 0)
+                        with_index<NP>(ic, [&](auto I) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) {
+                                const double s = floor(pr[decltype(I)::value][i]);
+                                col[i] = first + ((s >= 1.0) ? ((s >= (double)(W - 1)) ? W - 1 : (int)s) : 0) * S;   // clip; NaN -> 0
+                            }
+                        });
+                    }
+                    const double scale = (double)TT;
+                    const int mask = TT - 1;
+                    with_index<NO>(ia, [&](auto I) {
+                        constexpr int S_ = decltype(I)::value;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            const double qr = vp_pin(q[r]);
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) {
+                                const double u = __builtin_amdgcn_fract(qr * ohz[S_][i] + oph[S_][i]) * scale;
+                                const double fl = floor(u);
+                                const int at = col[i] + ((int)fl & mask);
+                                const double lo = (double)tab[at], hi = (double)tab[at + 1];
+                                acc[r][i] = lo + (u - fl) * (hi - lo);
+                            }
+                        }
+                    });
+                    continue;
+                }
+            }
             switch (op) {
                 case SIG_VP_OSC:
                     with_index<NO>(ia, [&](auto I) {
@@ -760,14 +809,36 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM>
-__device__ __forceinline__ void vp_kernel_body(const VpArgs& a)
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, typename TABLES>
+__device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
 {
     constexpr bool BUS = C > 0;
     __shared__ double lds[BUS ? 4 : 1][BUS ? sig_bus::kPairs * kTileStride : 1];
+    const float* tab = nullptr;
+    if constexpr (TAB) {                                                       // the tables into (dynamic) LDS, once per workgroup
+        extern __shared__ float vp_tab[];
+        int first = 0;
+#pragma unroll
+        for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) {
+            if (!tb.ptr[k]) break;                                             // (slots are filled from 0)
+            const int T = tb.T[k], W = tb.W[k], S = T + 1;
+            // element e = i * W + w of the row-major table goes to column w, row i; (i, w) advance by 256 elements without a division per element
+            const int di = 256 / W, dw = 256 - di * W;
+            int i = (int)threadIdx.x / W, w = (int)threadIdx.x - i * W;
+            for (int e = threadIdx.x; e < T * W; e += 256) {
+                vp_tab[first + w * S + i] = tb.ptr[k][e];
+                i += di; w += dw;
+                if (w >= W) { w -= W; ++i; }
+            }
+            for (int c = threadIdx.x; c < W; c += 256) vp_tab[first + c * S + T] = tb.ptr[k][c];
+            first += S * W;
+        }
+        __syncthreads();
+        tab = vp_tab;
+    }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM>(a, lds[BUS ? wave : 0], lane, wave);
+    vp_wave<VPT, SMALL, C, BAND, PM, TAB>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -779,7 +850,14 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a)
 // constant -- the dispatch loop unrolls and every switch folds.  Attached to the library with sig_voice_program_attach.
 }  // namespace
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
+#ifndef SIG_VP_S_TAB
+#define SIG_VP_S_TAB 0                     // 1: the program has an OscTable word, the kernel takes the tables as a second parameter
+#endif
+#if SIG_VP_S_TAB
+void sig_vp_specialised(VpArgs a, VpTables tb)
+#else
 void sig_vp_specialised(VpArgs a)
+#endif
 {
     constexpr bool kBand = [] {
         constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
@@ -793,7 +871,18 @@ void sig_vp_specialised(VpArgs a)
         for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) pm |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCPM;
         return pm;
     }();
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm>(a);
+    constexpr bool kTab = [] {
+        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
+        bool tab = false;
+        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) tab |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCTABLE;
+        return tab;
+    }();
+    static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable word is built with -DSIG_VP_S_TAB=1, any other without");
+#if SIG_VP_S_TAB
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true>(a, tb);
+#else
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false>(a, VpNoTables{});
+#endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
 extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
@@ -806,7 +895,13 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND, PM>(a);
+    vp_kernel_body<VPT, SMALL, C, BAND, PM, false>(a, VpNoTables{});
+}
+// the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
+{
+    vp_kernel_body<VPT, SMALL, C, false, false, true>(a, tb);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -822,9 +917,10 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCPM && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15))
+        const int c = (x.op == SIG_VP_OSCTABLE && x.c == -1) ? 15 : x.c;       // (no select: a slot number no register file has)
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCTABLE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
             return false;
-        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)x.c << 16);
+        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
     }
     return true;
 }
@@ -839,7 +935,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -879,10 +975,23 @@ int vp_launch_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
     return sig_launch_status();
 }
 
+template <int VPT, bool SMALL>
+int vp_launch_table_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nwg, size_t lds, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_table_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, tb); break;
+        case 1: voice_program_table_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, tb); break;
+        case 2: voice_program_table_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, tb); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
 template <int VPT>
-int vp_launch_file(const VpArgs& a, bool small_file, bool band, bool pm, int C, unsigned nwg, hipStream_t s) {
-    if (pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);   // (never with a band: refused)
-    if (band) return small_file ? vp_launch_sink<VPT, true, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, true, false>(a, C, nwg, s);
+int vp_launch_file(const VpArgs& a, const VpTables& tb, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
+    // (a table never with a band or a PM carrier, a PM carrier never with a band: refused)
+    if (n.table) return small_file ? vp_launch_table_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_table_sink<VPT, false>(a, tb, C, nwg, lds, s);
+    if (n.pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);
+    if (n.band) return small_file ? vp_launch_sink<VPT, true, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, true, false>(a, C, nwg, s);
     return small_file ? vp_launch_sink<VPT, true, false, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, false>(a, C, nwg, s);
 }
 
@@ -965,6 +1074,18 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
                                  const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                                  double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream)
 {
+    return sig_voice_program_ex(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks,
+                                hist_positions, blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld,
+                                status, stream, nullptr);
+}
+
+extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                    int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                    int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                    const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                    double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                                    const sig_vp_tables_t* tables)
+{
     SIG_CHECK_ARG(program && rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
     SIG_CHECK_ARG(out && (bus_channels == 0 || bus_channels == 1 || bus_channels == 2));
     SIG_CHECK_ARG(bus_channels == 0 ? out_ld >= voices : (out_ld >= bus_channels && workspace != nullptr));
@@ -985,13 +1106,26 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false};
+    // the wavetables: powers of two, together inside the cap (one workgroup's LDS holds them all)
+    const int n_tables = tables ? tables->n_tables : 0;
+    SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
+    size_t table_lds = 0;
+    for (int k = 0, points = 0; k < n_tables; ++k) {
+        const auto& t = tables->table[k];
+        SIG_CHECK_ARG(t.ptr != nullptr && t.points >= 2 && (t.points & (t.points - 1)) == 0 && t.waves >= 1 &&
+                      (int64_t)t.points * t.waves <= SIG_TABLE_MAX_POINTS - points);
+        points += t.points * t.waves;
+        table_lds += (size_t)(t.points + 1) * t.waves * sizeof(float);
+    }
     bool has_adsr = false;
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCPM && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && x.c >= 0 && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCTABLE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+                      x.c >= (x.op == SIG_VP_OSCTABLE ? -1 : 0) && x.c <= 15);
         switch (x.op) {
+            case SIG_VP_OSCTABLE: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params); break;
             case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
@@ -1006,8 +1140,12 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
         if (x.op == SIG_VP_ADSR) has_adsr = true;
         if (x.op == SIG_VP_BAND) need.band = true;
         if (x.op == SIG_VP_OSCPM) need.pm = true;
+        if (x.op == SIG_VP_OSCTABLE) need.table = true;
     }
-    SIG_CHECK_ARG(!(need.band && need.pm));                                    // (no interpreter variant with both; the engine keeps such a graph per node)
+    SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no interpreter variant with two of them; the engine keeps such a graph per node)
+    VpTables tb{};
+    for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
+    if (!need.table) table_lds = 0;
     SIG_CHECK_ARG(vp_encode(P, a.code));
     a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
     for (int k = 0; k < P.n_oscs; ++k) {
@@ -1077,12 +1215,12 @@ extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rat
     hipStream_t s = static_cast<hipStream_t>(stream);
     int err;
     if (hipFunction_t fn = vp_find_special(a, P, vpt, bus_channels)) {         // this very program, built as straight-line code
-        void* params[] = {&a};
-        err = (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, 0, s, params, nullptr);
+        void* params[] = {&a, &tb};                                           // (an image built for a table program takes both, any other the first)
+        err = (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, small_file, need.band, need.pm, bus_channels, (unsigned)nwg, s);
-    else err = vp_launch_file<1>(a, small_file, need.band, need.pm, bus_channels, (unsigned)nwg, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, small_file, need, bus_channels, (unsigned)nwg, table_lds, s);
+    else err = vp_launch_file<1>(a, tb, small_file, need, bus_channels, (unsigned)nwg, table_lds, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);

@@ -370,12 +370,19 @@ def _ctl_const(port: Receiver.BoundPort) -> bool:
     return src is None or not src.get_state().enabled or isinstance(src, fixed.Fixed)
 
 
+def _ctl_unplugged(port: Receiver.BoundPort) -> bool:
+    """a control port that reads zeros((1, 1)): nothing plugged, or a disabled source"""
+    return port.sig is None or not port.sig.get_state().enabled
+
+
 def _control_ports(node: Emitter) -> list:
     """ports a node reads with forward_at_block_rate"""
     if isinstance(node, osc.Osc):
         return [node.hertz, node.phase]
     if isinstance(node, ext.PMOsc):
         return [node.hertz, node.phase, node.index]
+    if isinstance(node, ext.Wavetable):
+        return [node.hertz, node.phase, node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
@@ -555,6 +562,9 @@ class _ControlProgram:
             got = self._filter(src)
         elif isinstance(src, fx.DoubleCritFilter):
             raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
+        elif isinstance(src, ext.Wavetable):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a wavetable oscillator has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.PMOsc) and window:
             raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
                                f'window-rate program')
@@ -726,6 +736,9 @@ class _Batch:
         elif isinstance(src, ext.PMOsc):
             raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a phase-modulation oscillator has no block-rate '
                                f'schedule (its modulator is a frame-rate input)')
+        elif isinstance(src, ext.Wavetable):
+            raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a wavetable oscillator has no block-rate schedule '
+                               f'(the eager node serves one-frame requests)')
         else:
             raise NotBatchable(f'{what}: no block-rate schedule for {src.cls_name()}')
         self._ctl_memo[src] = result
@@ -833,9 +846,18 @@ class _Batch:
         x = self._operand(node.mod, channels, 0 if _modulated(node) else hist)   # a modulated node's history comes from its tail
         return self._osc_launch(node, 'osc_bank_pm', _native.osc_bank_pm, (hertz, phase, index, x), hist, rows)
 
-    def _osc_launch(self, node, name, bank, operands, hist, rows):
+    def _sched_table(self, node, channels, hist, rows):
+        """a wavetable oscillator: one sig_osc_bank_table launch, per-block hertz / phase / select rows when one is modulated"""
+        hertz, phase, select = (self._control(p, p.name) for p in (node.hertz, node.phase, node.select))
+        table = node.resident_table()
+
+        def bank(kind, position, rate, hertz, phase, select, out, **kw):
+            return _native.osc_bank_table(position, rate, hertz, phase, select, table, out, **kw)
+        return self._osc_launch(node, 'osc_bank_table', bank, (hertz, phase, select), hist, rows, kind='Table')
+
+    def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
         """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
-        o, kind = self.owner, node.kind()
+        o, kind = self.owner, kind or node.kind()
         _, voices = broadcast_shape((1, 1), *((1, t.shape[1]) for t in operands))
         result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
         if _modulated(node):
@@ -1167,6 +1189,7 @@ class _Batch:
         (fixed.Fixed, _sched_fixed),
         (osc.Osc, _sched_osc),
         (ext.PMOsc, _sched_pm),
+        (ext.Wavetable, _sched_table),
         (noise.White, _sched_noise),
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
@@ -1786,7 +1809,7 @@ class _ProgramRows:
 
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
-    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), in any arrangement in which every voice is computed from its own
+    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
@@ -1794,7 +1817,7 @@ class _VoiceProgram:
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
     KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
-                    ext.PMOsc)
+                    ext.PMOsc, ext.Wavetable)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
@@ -1806,6 +1829,7 @@ class _VoiceProgram:
         self.controls: list = []                 # (port | None, constant tensor | None, filters between the node and the sink)
         self.adsr = None
         self.seeds: list = []
+        self.tables: list = []                   # the Wavetable nodes whose tables the launch stages, one slot per distinct state array
         self.temps_used, self.temps_free, self.n_temps = set(), [], 0
         self.saved: dict = {}                    # node -> [temporary, readers left]
         self.depth_of: dict = {}
@@ -1820,6 +1844,8 @@ class _VoiceProgram:
             raise _NoProgram('program too long')
         if self.bands and any(op == 'OscPM' for op, *_ in self.code):
             raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
+        if self.tables and (self.bands or any(op == 'OscPM' for op, *_ in self.code)):
+            raise _NoProgram('a wavetable oscillator with a band filter or a phase-modulation oscillator: no interpreter variant has both')
 
     # ---- pass 1: readers of every node inside the graph
     def _count(self, n):
@@ -1877,6 +1903,17 @@ class _VoiceProgram:
         self.oscs.append((self._control(n.hertz, below), self._control(n.phase, below, optional=True)))
         return len(self.oscs) - 1
 
+    def _table_slot(self, n) -> int:
+        """the slot of this node's table: nodes that share one state array share a slot; together inside the LDS cap"""
+        table = n.get_state().table
+        for k, other in enumerate(self.tables):
+            if other.get_state().table is table:
+                return k
+        if len(self.tables) >= _native.VP_MAX_TABLES or sum(t.get_state().table.size for t in self.tables) + table.size > _native.TABLE_MAX_POINTS:
+            raise _NoProgram('more wavetables than the launch holds')
+        self.tables.append(n)
+        return len(self.tables) - 1
+
     def _emit(self, n, below: int) -> int:
         """code that leaves the node's sample in the accumulator; returns the filters in series up to and including it"""
         if isinstance(n, ext.Tap):
@@ -1904,6 +1941,10 @@ class _VoiceProgram:
         elif isinstance(n, ext.PMOsc):
             depth = self._emit(n.mod.sig, below)                               # the modulator's sample: in the accumulator
             self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), self._param(self._control(n.index, below)), 0))
+        elif isinstance(n, ext.Wavetable):
+            select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
+            self.code.append(('OscTable', 0, self._osc_slot(n, below), self._table_slot(n), select))
+            depth = 0
         elif isinstance(n, noise.White):
             if len(self.seeds) >= 2 or n.channels != self.voices:
                 raise _NoProgram('White: two per program, as wide as the voices')
@@ -2057,7 +2098,8 @@ class _VoiceProgram:
         return o._launch(label, lambda: _native.voice_program(self.code, oscs, params, filters, self.n_temps, self.depth, b.rate, b.pos,
                                                               b.N, b.K, CONTEXT, v, control_rows, hist, out, bus_gains=bus_gains, bus=bus,
                                                               adsr=adsr, noise_seeds=seeds, workspace=o._workspace if bus else None,
-                                                              status=status, blocks_before=before),
+                                                              status=status, blocks_before=before,
+                                                              tables=[n.resident_table() for n in self.tables]),
                          units=out.shape[0] * v)
 
     @classmethod
@@ -2086,7 +2128,9 @@ class _VoiceProgram:
         under the same rule (tools/time_band.py); graphs whose bands all hold still keep the per-node schedule
         they had before the program knew band filters, unless that schedule cannot batch them (short blocks behind a filter).
         Phase-modulation carriers (OscPM) take the program under the same rule: a two-operator voice under a bus runs at 0.54-0.55 T
-        interpreted against 0.22 T per node, 0.40-0.42 against 0.16-0.17 T behind a LowPass (tools/time_pm.py)."""
+        interpreted against 0.22 T per node, 0.40-0.42 against 0.16-0.17 T behind a LowPass (tools/time_pm.py).
+        Wavetable oscillators (OscTable) take the program under the same rule: 0.76 T interpreted against 0.32 T per node under a bus,
+        0.55 against 0.21 T behind a LowPass (tools/time_wavetable.py)."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
