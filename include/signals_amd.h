@@ -103,6 +103,23 @@ int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, in
                        const float* table, int32_t table_points, int32_t table_waves,
                        void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Table-lookup waveshaper, chain/ext.py Shaper (build-defined: the reference has no memoryless non-linearity but Amp).  `table`
+ * float32 (T, W) row-major in device memory: W transfer curves of T points each, spanning input -1 .. +1; T >= 2 (any integer: 2^k + 1
+ * points put a knot at x = 0), W >= 1, T * W <= SIG_TABLE_MAX_POINTS.  For every row n and voice v, in f64, every operation rounded:
+ *   c = clip(in[n,v], -1, 1)                                               (+-inf clip; NaN stays NaN)
+ *   u = (c + 1.0) * ((T - 1) * 0.5);  i = min(floor(u), T - 2);  f = u - i (f in [0, 1]: in = +1 reads the last segment at f = 1)
+ *   w = clip(floor(select[v]), 0, W - 1)                                   (NaN -> 0; select NULL = unplugged = column 0)
+ *   out[n,v] = tbl[i, w] + f * (tbl[i+1, w] - tbl[i, w])                   tbl = (double) table; NaN where in is NaN
+ * `in`: float32 or float64 (rows | 1, voices | 1): in_ld == 0 one row for all, in_stride == 0 one column broadcast over the voices.
+ * `select`: f64 (1 | P, voices | 1), output row n reads select row n / rows_per_select (0: one row for the whole launch).
+ * The float64 value in front of the store is bit-exact against numpy.  A null pointer, T < 2, T * W over the cap, out_ld < voices or
+ * a stride other than 0 / 1: hipErrorInvalidValue, nothing launched; rows == 0: no launch. */
+int sig_shaper_table(int64_t rows, int32_t voices,
+                     const void* in, int32_t in_dtype, int64_t in_ld, int32_t in_stride,
+                     const double* select, int32_t select_stride, int64_t select_row_stride, int32_t rows_per_select,
+                     const float* table, int32_t table_points, int32_t table_waves,
+                     void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):
@@ -550,6 +567,9 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *          from the definition only for t in (-2^-54, 0), where it reads the table's last segment at f = 1 - 2^-53 instead of entry 0
  *          (the two agree to one ulp of a table step).  A program that combines OSCTABLE with BAND or OSCPM is refused,
  *          hipErrorInvalidValue; so is one launched without its tables
+ *   SHAPE  acc = waveshaper lookup (sig_shaper_table's expression) of the accumulator in table slot b of the `tables` argument,
+ *          column = params[c] (select rows), c == -1: unplugged = column 0.  Refused with BAND or OSCPM and without its tables, like
+ *          OSCTABLE.  A slot that only SHAPE words read may have any T >= 2; a slot an OSCTABLE word reads is a power of two
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -571,10 +591,10 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF. */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
-       SIG_VP_OSCTABLE = 13 };
+       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14 };
 enum { SIG_VP_MAX_TABLES = 2 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE: c may be -1 */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE: c may be -1 */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];
@@ -591,8 +611,9 @@ int sig_voice_program(const sig_voice_program_t* program, int32_t rate, int64_t 
                       int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
                       const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                       double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream);
-/* sig_voice_program with the wavetables of its OSCTABLE instructions: up to SIG_VP_MAX_TABLES tables, each float32 (points, waves)
- * row-major in device memory under sig_osc_bank_table's rules, together at most SIG_TABLE_MAX_POINTS entries (they share the LDS of
+/* sig_voice_program with the tables of its OSCTABLE and SHAPE instructions: up to SIG_VP_MAX_TABLES tables, each float32 (points, waves)
+ * row-major in device memory under sig_osc_bank_table's rules (points a power of two) where an OSCTABLE word reads it, under
+ * sig_shaper_table's (points >= 2) where only SHAPE words do, together at most SIG_TABLE_MAX_POINTS entries (they share the LDS of
  * a workgroup).  `tables` (HOST memory) may be NULL for a program without the instruction: sig_voice_program is this call with NULL. */
 typedef struct { int32_t n_tables; struct { const float* ptr; int32_t points, waves; } table[SIG_VP_MAX_TABLES]; } sig_vp_tables_t;
 int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,

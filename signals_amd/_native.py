@@ -49,11 +49,12 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12, 'OscTable': 13}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 VP_MAX_TABLES = 2
-TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable (of a voice program's tables together)
+VP_TABLE_OPS = ('OscTable', 'Shape')        # the instructions of the table variant (SIG_VP_S_TAB): table slot b, select = parameter slot c | -1
+TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
 
 
 class VpIns(ctypes.Structure):
@@ -110,6 +111,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_pm': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
                             vp, i32, i64, i32, vp, i32, i64, vp],
         'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
+        'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
         'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
@@ -361,13 +363,14 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
     return out
 
 
-def _table(table: torch.Tensor):
-    """(ptr, points, waves) of a wavetable: float32 (T, W) contiguous on the device, T a power of two >= 2, T * W within the cap"""
+def _table(table: torch.Tensor, pow2: bool = True):
+    """(ptr, points, waves) of a wavetable: float32 (T, W) contiguous on the device, T a power of two >= 2, T * W within the cap;
+    `pow2` False: a shaper's table, any T >= 2"""
     if table is None or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
         raise NativeError('a wavetable is a contiguous float32 (points, waves) tensor')
     points, waves = table.shape
-    if points < 2 or points & (points - 1) or waves < 1 or points * waves > TABLE_MAX_POINTS:
-        raise NativeError(f'wavetable {tuple(table.shape)}: points a power of two >= 2, points * waves <= {TABLE_MAX_POINTS}')
+    if points < 2 or (pow2 and points & (points - 1)) or waves < 1 or points * waves > TABLE_MAX_POINTS:
+        raise NativeError(f'table {tuple(table.shape)}: points {"a power of two " if pow2 else ""}>= 2, points * waves <= {TABLE_MAX_POINTS}')
     return table.data_ptr(), points, waves
 
 
@@ -383,6 +386,25 @@ def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.T
     _check(lib().sig_osc_bank_table(position, step, rate, rows, voices, rows_per_param,
                                     *params[0:3], *params[4:7], *params[8:11], *_table(table),
                                     out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_table')
+    return out
+
+
+def shaper_table(x: torch.Tensor, select: torch.Tensor | None, table: torch.Tensor, out: torch.Tensor,
+                 rows_per_select: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- waveshaper (sig_shaper_table): the (T, W) float32 `table` of transfer curves over -1 .. +1 read with linear
+    interpolation at (clip(x, -1, 1) + 1) * (T - 1) / 2, column clip(floor(select), 0, W - 1).  x: float32 | float64 (rows|1, V|1);
+    select: (1|P, V|1) f64, output row r reads row r // rows_per_select."""
+    _gpu(x, select, table, out)
+    _audio(out, 'shaper out')
+    _audio(x, 'shaper in')
+    rows, voices = out.shape
+    if x.shape[0] not in (1, rows) or x.shape[1] not in (1, voices):
+        raise NativeError(f'shaper input {tuple(x.shape)} does not broadcast to {(rows, voices)}')
+    sp, ss, srs, srows = _voice_rows(voices, (select, 'select'), form=_ctrl_rows)
+    rows_per_select = _parameter_rows(rows, rows_per_select, (srows, 'select'))
+    _check(lib().sig_shaper_table(rows, voices, x.data_ptr(), _dt(x), 0 if x.shape[0] == 1 else x.stride(0), 0 if x.shape[1] == 1 else 1,
+                                  sp, ss, srs, rows_per_select, *_table(table, pow2=False),
+                                  out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_shaper_table')
     return out
 
 
@@ -980,7 +1002,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   out: torch.Tensor, bus_gains: torch.Tensor | None = None, bus: bool = False,
                   adsr: dict | None = None, noise_seeds: tuple = (0, 0), workspace: torch.Tensor | None = None,
                   status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None) -> torch.Tensor:
-    """One launch for a whole per-voice graph (sig_voice_program_ex; `tables`: the float32 (T, W) wavetables of its OscTable words).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
+    """One launch for a whole per-voice graph (sig_voice_program_ex; `tables`: the float32 (T, W) tables of its OscTable and Shape words).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
     'lp' | 'hp', level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
@@ -1024,8 +1046,9 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
     if tables:
         held = VpTablesT()
         held.n_tables = len(tables)
+        wrapped = {b for op, _, _, b, _ in code if op == 'OscTable'}            # slots an oscillator reads: powers of two
         for k, t in enumerate(tables):
-            held.table[k] = VpTable(*_table(t))
+            held.table[k] = VpTable(*_table(t, pow2=k in wrapped))
     _check(lib().sig_voice_program_ex(ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows,
                                       len(hist_positions), hist, blocks_before, gp, gld, C,
                                       _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out),
@@ -1035,7 +1058,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's c = -1: 15)
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's and Shape's c = -1: 15)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

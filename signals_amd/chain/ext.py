@@ -219,6 +219,67 @@ class Wavetable(BlockCachingEmitter, ImplicitChannels):
         return _native.osc_bank_table(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
 
 
+def _validate_curves(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and new_value.shape[0] >= 2 and new_value.shape[1] >= 1
+          and new_value.shape[0] * new_value.shape[1] <= _native.TABLE_MAX_POINTS)
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a 2D real array (points, curves), points >= 2, points * curves <= {_native.TABLE_MAX_POINTS}')
+
+
+class Shaper(BlockCachingEmitter, ImplicitChannels):
+    """Table-lookup waveshaper, a memoryless non-linearity (saturation, overdrive, wavefolding, Chebyshev shaping, soft clipping):
+    the state `table` holds W transfer curves of T points each as a (T, W) array, spanning input -1 .. +1, read with linear
+    interpolation at the input's VALUE.  With tbl = float32(table) widened to float64, in float64 and every operation rounded:
+        c = clip(x, -1, 1)                                                 (+-inf clip; NaN stays NaN)
+        h = (T - 1) * 0.5;  u = (c + 1.0) * h                              (in [0, T - 1])
+        i = min(floor(u), T - 2);  f = u - i                               (f in [0, 1]: x = +1 reads the last segment at f = 1)
+        w = clip(floor(select), 0, W - 1)                                  (per voice; NaN and unplugged: column 0)
+        out = tbl[i, w] + f * (tbl[i+1, w] - tbl[i, w])                    (NaN where x is NaN)
+    (kernel: sig_shaper_table; restated in numpy by tests/shaper_reference.py).  Ports: `input` at frame rate, `select` at block
+    rate.  T >= 2, any integer (2^k + 1 points put a knot at x = 0), T * W <= 16384; integer arrays (what a .sigs value arrives
+    as) are converted; the device copy is float32 and follows in-place edits of the array.  The default table [[-1], [1]] is the
+    identity on [-1, 1]: a hard clip.  Position-pure when its input is, no context rows.  The map is continuous and piecewise
+    linear, Lipschitz with L = max_i |tbl[i+1, w] - tbl[i, w]| * (T - 1) / 2.
+    Out of scope: the node inside a block-rate control path (the batched engine answers NotBatchable with the reason and the
+    graph keeps the eager path, which serves frames == 1 in float64); a combination with a band filter or a phase-modulation
+    oscillator in one voice program (such a graph stays one kernel per node); oversampling and anti-aliasing of the shaper;
+    morphing between columns; a frame-rate `select`; the closed-form, row-walker and cascade fused kernels."""
+    input: Receiver.BoundPort = port('input')
+    select: Receiver.BoundPort = port('select')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        table: np.ndarray = attr.ib(factory=lambda: np.array([[-1.0], [1.0]]), validator=_validate_curves,
+                                    on_setattr=attr.setters.validate)
+
+    def __init__(self):
+        super().__init__()
+        self._resident = None
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.EFFECT
+
+    def resident_table(self) -> torch.Tensor:
+        table = self._state.table
+        held = self._resident
+        if held is None or held[0] is not table or not held[1].matches(table):
+            host = np.ascontiguousarray(table, dtype=np.float32)
+            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
+        return held[2]
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
+        x = self.input.forward(request)
+        if x.dtype not in (torch.float32, torch.float64) or (x.shape[1] > 1 and x.stride(1) != 1):
+            x = x.to(result_dtype(x.shape[0])).contiguous()
+        frames, voices = broadcast_shape(x.shape, select.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=select.device)
+        return _native.shaper_table(x, select, self.resident_table(), out)
+
+
 def _validate_matrix(instance, attribute, new_value):
     if not (isinstance(new_value, np.ndarray) and new_value.shape == (64, 64)):
         raise BadStateValue(instance, attribute.name, new_value, 'must be a (64, 64) array')

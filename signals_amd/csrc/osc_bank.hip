@@ -9,6 +9,7 @@
 //
 // Roofline: 4 B written per voice-sample (f32), no reads beyond 2 x 8 B per voice per wave.
 #include "sig_osc.h"
+#include "sig_table.h"
 
 namespace {
 
@@ -240,7 +241,7 @@ int run_pm(int kind, const OscArgs& a, const PmArgs& m, void* out, int32_t out_d
 // ---- wavetable: out = lerp of a (T, W) float32 table (W single-cycle waveforms of T points, T a power of two) at
 // m = np.mod(n / rate * hertz + phase, 1), column w = clip(floor(select), 0, W - 1) per voice (chain/ext.py Wavetable).
 // A 512-thread workgroup stages the whole table in LDS once -- column-major, T + 1 floats per column, the guard entry
-// tab[w][T] = tab[w][0] -- and then walks `groups` 16-row groups per wave of its 64 * VEC voices, so the staging (<= 64 KiB
+// tab[w][T] = tab[w][0] (sig_table.h, shared with the waveshaper) -- and then walks `groups` 16-row groups per wave of its 64 * VEC voices, so the staging (<= 64 KiB
 // read from L2) is amortised over up to 1 MiB of stores.  The guard makes the two lerp operands ONE paired read at a single
 // address (i & (T - 1), + 1: the last segment wraps without a second mask, and m == 1.0 lands on entry 0 with f == 0), and the
 // odd column stride T + 1 keeps equal indices of different columns on different banks.  Lanes, rows and stores as in
@@ -259,19 +260,9 @@ struct TableArgs {
 template <int VEC, typename OUT>
 __global__ __launch_bounds__(64 * kTableWaves) void osc_bank_table_kernel(OscArgs a, TableArgs tb, OUT* __restrict__ out, int64_t ld, int voice_tiles)
 {
-    extern __shared__ float tab[];                                 // [W][T + 1]
+    extern __shared__ float tab[];                                 // [W][T + 1], sig_table.h
     const int T = tb.T, W = tb.W, S = T + 1;
-    // coalesced read of row-major (T, W), element k = i * W + w to column w, row i (LDS stride S is odd); (i, w) advance by a
-    // workgroup's worth of elements per step, so the division is paid once per thread, not per element
-    constexpr int kStep = 64 * kTableWaves;
-    const int di = kStep / W, dw = kStep - di * W;
-    int si = (int)threadIdx.x / W, sw = (int)threadIdx.x - si * W;
-    for (int k = threadIdx.x; k < T * W; k += kStep) {
-        tab[sw * S + si] = tb.table[k];
-        si += di; sw += dw;
-        if (sw >= W) { sw -= W; ++si; }
-    }
-    for (int w = threadIdx.x; w < W; w += 64 * kTableWaves) tab[w * S + T] = tb.table[w];
+    sig_table::stage<64 * kTableWaves>(tab, tb.table, T, W);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -347,7 +338,7 @@ int launch_table(const OscArgs& a, TableArgs tb, OUT* out, int64_t ld, hipStream
     while (tb.groups > 1 && ((passes + tb.groups - 1) / tb.groups) * voice_tiles < 512) tb.groups >>= 1;
     const int64_t nwg = ((passes + tb.groups - 1) / tb.groups) * voice_tiles;
     if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    const size_t lds = (size_t)(tb.T + 1) * tb.W * sizeof(float);
+    const size_t lds = sig_table::lds_bytes(tb.T, tb.W);
     if (vec4)
         osc_bank_table_kernel<4, OUT><<<(unsigned)nwg, 64 * kTableWaves, lds, stream>>>(a, tb, out, ld, voice_tiles);
     else

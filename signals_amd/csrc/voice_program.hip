@@ -40,6 +40,7 @@
 #include "sig_biquad.h"
 #include "sig_bus_tile.h"
 #include "sig_osc.h"
+#include "sig_table.h"
 
 namespace {
 
@@ -167,9 +168,11 @@ template <bool SMALL> struct VpLimits {
 // BAND: the Band instruction (band filters' per-voice middle taps and their design; a variant of its own, so that programs
 // without one keep the registers they had -- the band state and its inlined design cost the SMALL file ~200 B of scratch per lane)
 // PM: the OscPM instruction (phase-modulation carriers), a variant of its own for the same reason
-// TAB: the OscTable instruction (wavetable oscillators, ext.py Wavetable), likewise; `tab`: the launch's tables in LDS, each
-// column-major with T + 1 floats per column (the guard entry [T] = [0], osc_bank.hip), table 1 behind table 0
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, typename TABLES>
+// TAB: the OscTable and Shape instructions (wavetable oscillators and waveshapers, ext.py Wavetable / Shaper), likewise; `tab`: the launch's tables in LDS, each
+// column-major with T + 1 floats per column (the guard entry [T] = [0], sig_table.h), table 1 behind table 0
+// SHP: the Shape instruction on top of TAB, a variant of its own once more: with the handler in the one TAB variant the SMALL
+// table kernels went from 260-312 to 412-472 B of scratch per lane, which wavetable-only programs would have paid
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, typename TABLES>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
                                         [[maybe_unused]] const float* tab)
 {
@@ -484,24 +487,48 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
             // OscTable is dispatched in front of the switch, and only in the TAB variant: a case of its own, even an empty one, changes
             // the code of every other instantiation (the compare chain of the dispatch), and those are to stay what they were
             if constexpr (TAB) {
-                if (op == SIG_VP_OSCTABLE) {                                   // the Osc handler's phase, looked up in table slot ib (ext.py Wavetable)
-                    // m = t - floor(t) as v_fract_f64: not the definition's 1.0 for t in (-2^-54, 0) but the largest double below
-                    // it, i.e. the last segment at f = 1 - T 2^-53 instead of entry 0 at f = 0 -- one rounding of a table step apart
+                // the column of table slot ib that parameter slot ic selects, per voice: its first float in `tab`
+                auto columns = [&](int (&col)[VPT], int& TT) {
                     const int slot = ib & (SIG_VP_MAX_TABLES - 1);
-                    const int TT = tb.T[slot], W = tb.W[slot], S = TT + 1;
+                    TT = tb.T[slot];
+                    const int W = tb.W[slot], S = TT + 1;
                     const int first = slot ? (tb.T[0] + 1) * tb.W[0] : 0;
-                    int col[VPT];
 #pragma unroll
                     for (int i = 0; i < VPT; ++i) col[i] = first;
                     if (ic < NP) {                                             // (15: select unplugged, column 0)
                         with_index<NP>(ic, [&](auto I) {
 #pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                const double s = floor(pr[decltype(I)::value][i]);
-                                col[i] = first + ((s >= 1.0) ? ((s >= (double)(W - 1)) ? W - 1 : (int)s) : 0) * S;   // clip; NaN -> 0
-                            }
+                            for (int i = 0; i < VPT; ++i) col[i] = first + sig_table::column(pr[decltype(I)::value][i], W) * S;
                         });
                     }
+                };
+                if constexpr (SHP) {
+                    if (op == SIG_VP_SHAPE) {                                  // the accumulator through a transfer curve (ext.py Shaper, shaper.hip)
+                        int col[VPT], TT;
+                        columns(col, TT);
+                        const double half = (double)(TT - 1) * 0.5;
+                        const int last = TT - 2;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) {
+                                const double x = acc[r][i];
+                                const double c = (x < -1.0) ? -1.0 : ((x > 1.0) ? 1.0 : x);     // np.clip: NaN stays NaN
+                                const double u = (c + 1.0) * half;
+                                const int k = (u >= 0.0) ? min((int)floor(u), last) : 0;         // (NaN: entry 0, u - k carries it)
+                                const int at = col[i] + k;                     // at + 1 <= the column's entry T - 1
+                                const double lo = (double)tab[at], hi = (double)tab[at + 1];
+                                acc[r][i] = lo + (u - (double)k) * (hi - lo);
+                            }
+                        }
+                        continue;
+                    }
+                }
+                if (op == SIG_VP_OSCTABLE) {                                   // the Osc handler's phase, looked up in table slot ib (ext.py Wavetable)
+                    // m = t - floor(t) as v_fract_f64: not the definition's 1.0 for t in (-2^-54, 0) but the largest double below
+                    // it, i.e. the last segment at f = 1 - T 2^-53 instead of entry 0 at f = 0 -- one rounding of a table step apart
+                    int col[VPT], TT;
+                    columns(col, TT);
                     const double scale = (double)TT;
                     const int mask = TT - 1;
                     with_index<NO>(ia, [&](auto I) {
@@ -809,7 +836,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, typename TABLES>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, typename TABLES>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
 {
     constexpr bool BUS = C > 0;
@@ -821,24 +848,15 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
 #pragma unroll
         for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) {
             if (!tb.ptr[k]) break;                                             // (slots are filled from 0)
-            const int T = tb.T[k], W = tb.W[k], S = T + 1;
-            // element e = i * W + w of the row-major table goes to column w, row i; (i, w) advance by 256 elements without a division per element
-            const int di = 256 / W, dw = 256 - di * W;
-            int i = (int)threadIdx.x / W, w = (int)threadIdx.x - i * W;
-            for (int e = threadIdx.x; e < T * W; e += 256) {
-                vp_tab[first + w * S + i] = tb.ptr[k][e];
-                i += di; w += dw;
-                if (w >= W) { w -= W; ++i; }
-            }
-            for (int c = threadIdx.x; c < W; c += 256) vp_tab[first + c * S + T] = tb.ptr[k][c];
-            first += S * W;
+            sig_table::stage<256>(vp_tab + first, tb.ptr[k], tb.T[k], tb.W[k]);
+            first += (tb.T[k] + 1) * tb.W[k];
         }
         __syncthreads();
         tab = vp_tab;
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM, TAB>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
+    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -851,7 +869,7 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
 }  // namespace
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
 #ifndef SIG_VP_S_TAB
-#define SIG_VP_S_TAB 0                     // 1: the program has an OscTable word, the kernel takes the tables as a second parameter
+#define SIG_VP_S_TAB 0                     // 1: the program has an OscTable or a Shape word, the kernel takes the tables as a second parameter
 #endif
 #if SIG_VP_S_TAB
 void sig_vp_specialised(VpArgs a, VpTables tb)
@@ -874,14 +892,20 @@ void sig_vp_specialised(VpArgs a)
     constexpr bool kTab = [] {
         constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
         bool tab = false;
-        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) tab |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCTABLE;
+        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) tab |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCTABLE || (c[k] & 31u) == (uint32_t)SIG_VP_SHAPE;
         return tab;
     }();
-    static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable word is built with -DSIG_VP_S_TAB=1, any other without");
+    constexpr bool kShape = [] {
+        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
+        bool shape = false;
+        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) shape |= (c[k] & 31u) == (uint32_t)SIG_VP_SHAPE;
+        return shape;
+    }();
+    static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
 #if SIG_VP_S_TAB
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true>(a, tb);
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape>(a, tb);
 #else
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false>(a, VpNoTables{});
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false>(a, VpNoTables{});
 #endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
@@ -895,13 +919,19 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND, PM, false>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false>(a, VpNoTables{});
 }
 // the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, false>(a, tb);
+}
+// the TAB variant with the Shape instruction (programs with a waveshaper, with or without a wavetable oscillator)
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_shape_kernel(VpArgs a, VpTables tb)
+{
+    vp_kernel_body<VPT, SMALL, C, false, false, true, true>(a, tb);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -917,8 +947,8 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        const int c = (x.op == SIG_VP_OSCTABLE && x.c == -1) ? 15 : x.c;       // (no select: a slot number no register file has)
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCTABLE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
+        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) && x.c == -1) ? 15 : x.c;       // (no select: a slot number no register file has)
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_SHAPE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
     }
@@ -935,7 +965,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -986,9 +1016,21 @@ int vp_launch_table_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nw
     return sig_launch_status();
 }
 
+template <int VPT, bool SMALL>
+int vp_launch_shape_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nwg, size_t lds, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_shape_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, tb); break;
+        case 1: voice_program_shape_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, tb); break;
+        case 2: voice_program_shape_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, tb); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
 template <int VPT>
 int vp_launch_file(const VpArgs& a, const VpTables& tb, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
     // (a table never with a band or a PM carrier, a PM carrier never with a band: refused)
+    if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
     if (n.table) return small_file ? vp_launch_table_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_table_sink<VPT, false>(a, tb, C, nwg, lds, s);
     if (n.pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);
     if (n.band) return small_file ? vp_launch_sink<VPT, true, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, true, false>(a, C, nwg, s);
@@ -1106,14 +1148,14 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false};
-    // the wavetables: powers of two, together inside the cap (one workgroup's LDS holds them all)
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false};
+    // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
     const int n_tables = tables ? tables->n_tables : 0;
     SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
     size_t table_lds = 0;
     for (int k = 0, points = 0; k < n_tables; ++k) {
         const auto& t = tables->table[k];
-        SIG_CHECK_ARG(t.ptr != nullptr && t.points >= 2 && (t.points & (t.points - 1)) == 0 && t.waves >= 1 &&
+        SIG_CHECK_ARG(t.ptr != nullptr && t.points >= 2 && t.waves >= 1 &&
                       (int64_t)t.points * t.waves <= SIG_TABLE_MAX_POINTS - points);
         points += t.points * t.waves;
         table_lds += (size_t)(t.points + 1) * t.waves * sizeof(float);
@@ -1122,10 +1164,14 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCTABLE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
-                      x.c >= (x.op == SIG_VP_OSCTABLE ? -1 : 0) && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_SHAPE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) ? -1 : 0) && x.c <= 15);
         switch (x.op) {
-            case SIG_VP_OSCTABLE: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params); break;
+            case SIG_VP_OSCTABLE:
+                SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
+                SIG_CHECK_ARG((tables->table[x.b].points & (tables->table[x.b].points - 1)) == 0);     // the oscillator wraps with a mask
+                break;
+            case SIG_VP_SHAPE: SIG_CHECK_ARG(x.b < n_tables && x.c < P.n_params); break;
             case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
@@ -1140,7 +1186,8 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (x.op == SIG_VP_ADSR) has_adsr = true;
         if (x.op == SIG_VP_BAND) need.band = true;
         if (x.op == SIG_VP_OSCPM) need.pm = true;
-        if (x.op == SIG_VP_OSCTABLE) need.table = true;
+        if (x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) need.table = true;
+        if (x.op == SIG_VP_SHAPE) need.shape = true;
     }
     SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no interpreter variant with two of them; the engine keeps such a graph per node)
     VpTables tb{};

@@ -383,6 +383,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.hertz, node.phase, node.index]
     if isinstance(node, ext.Wavetable):
         return [node.hertz, node.phase, node.select]
+    if isinstance(node, ext.Shaper):
+        return [node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
@@ -402,7 +404,7 @@ def _audio_ports(node: Emitter) -> list:
         return [node.left, node.right]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.left]
-    if isinstance(node, (fx.CritFilter, ext.SumBus, ext.MixMatrix, ext.Tap, files.FileWriter)):
+    if isinstance(node, (fx.CritFilter, ext.SumBus, ext.MixMatrix, ext.Tap, ext.Shaper, files.FileWriter)):
         return [node.input]
     if isinstance(node, shape.Merge):
         return [node.left, node.right]
@@ -564,6 +566,9 @@ class _ControlProgram:
             raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
         elif isinstance(src, ext.Wavetable):
             raise NotBatchable(f'{src.cls_name()} in a control path: a wavetable oscillator has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.Shaper):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a waveshaper has no block-rate program '
                                f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.PMOsc) and window:
             raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
@@ -739,6 +744,9 @@ class _Batch:
         elif isinstance(src, ext.Wavetable):
             raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a wavetable oscillator has no block-rate schedule '
                                f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.Shaper):
+            raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a waveshaper has no block-rate schedule '
+                               f'(the eager node serves one-frame requests)')
         else:
             raise NotBatchable(f'{what}: no block-rate schedule for {src.cls_name()}')
         self._ctl_memo[src] = result
@@ -854,6 +862,26 @@ class _Batch:
         def bank(kind, position, rate, hertz, phase, select, out, **kw):
             return _native.osc_bank_table(position, rate, hertz, phase, select, table, out, **kw)
         return self._osc_launch(node, 'osc_bank_table', bank, (hertz, phase, select), hist, rows, kind='Table')
+
+    def _sched_shaper(self, node, channels, hist, rows):
+        """a waveshaper: one sig_shaper_table launch over its input's rows (history rows included when a filter reads it), scheduled
+        like an element-wise node; per-block select rows when that port is modulated"""
+        o, dev = self.owner, runtime.device()
+        mod = _modulated(node)
+        x = self._operand(node.input, channels, 0 if mod else hist)           # a modulated node's history comes from its tail
+        select = self._control(node.select, 'select')
+        table = node.resident_table()
+        cols = broadcast_shape((1, x.shape[1]), (1, select.shape[1]))[1]
+        if x.shape[0] == 1 and not mod:
+            result = torch.empty((1, cols), dtype=CTRL_DTYPE, device=dev)      # a one-row reply in, a one-row reply out
+            return o._launch('shaper_table[Shaper]', lambda: _native.shaper_table(x, select, table, result), units=cols)
+        result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=dev)
+        main = result[hist:] if mod else result
+        o._launch(f'shaper_table[Shaper{",per-block" if mod else ""}]',
+                  lambda: _native.shaper_table(x, select, table, main, rows_per_select=self.N if mod else 0), units=main.shape[0] * cols)
+        if mod:
+            self._own_history(node, cols, hist, result)
+        return result
 
     def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
         """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
@@ -1193,6 +1221,7 @@ class _Batch:
         (noise.White, _sched_noise),
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
+        (ext.Shaper, _sched_shaper),
         (ext.SumBus, _sched_bus),
         (ext.Tap, _sched_tap),
         (files.FileWriter, _sched_file_writer),
@@ -1809,7 +1838,7 @@ class _ProgramRows:
 
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
-    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), in any arrangement in which every voice is computed from its own
+    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), waveshapers (ext.Shaper), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
@@ -1817,7 +1846,7 @@ class _VoiceProgram:
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
     KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
-                    ext.PMOsc, ext.Wavetable)
+                    ext.PMOsc, ext.Wavetable, ext.Shaper)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
@@ -1829,7 +1858,7 @@ class _VoiceProgram:
         self.controls: list = []                 # (port | None, constant tensor | None, filters between the node and the sink)
         self.adsr = None
         self.seeds: list = []
-        self.tables: list = []                   # the Wavetable nodes whose tables the launch stages, one slot per distinct state array
+        self.tables: list = []                   # the Wavetable / Shaper nodes whose tables the launch stages, one slot per distinct state array
         self.temps_used, self.temps_free, self.n_temps = set(), [], 0
         self.saved: dict = {}                    # node -> [temporary, readers left]
         self.depth_of: dict = {}
@@ -1845,7 +1874,7 @@ class _VoiceProgram:
         if self.bands and any(op == 'OscPM' for op, *_ in self.code):
             raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
         if self.tables and (self.bands or any(op == 'OscPM' for op, *_ in self.code)):
-            raise _NoProgram('a wavetable oscillator with a band filter or a phase-modulation oscillator: no interpreter variant has both')
+            raise _NoProgram('a wavetable oscillator or a waveshaper with a band filter or a phase-modulation oscillator: no interpreter variant has both')
 
     # ---- pass 1: readers of every node inside the graph
     def _count(self, n):
@@ -1910,7 +1939,7 @@ class _VoiceProgram:
             if other.get_state().table is table:
                 return k
         if len(self.tables) >= _native.VP_MAX_TABLES or sum(t.get_state().table.size for t in self.tables) + table.size > _native.TABLE_MAX_POINTS:
-            raise _NoProgram('more wavetables than the launch holds')
+            raise _NoProgram('more tables than the launch holds')
         self.tables.append(n)
         return len(self.tables) - 1
 
@@ -1945,6 +1974,10 @@ class _VoiceProgram:
             select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
             self.code.append(('OscTable', 0, self._osc_slot(n, below), self._table_slot(n), select))
             depth = 0
+        elif isinstance(n, ext.Shaper):
+            depth = self._emit(n.input.sig, below)                             # the input's sample: in the accumulator
+            select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
+            self.code.append(('Shape', 0, 0, self._table_slot(n), select))
         elif isinstance(n, noise.White):
             if len(self.seeds) >= 2 or n.channels != self.voices:
                 raise _NoProgram('White: two per program, as wide as the voices')
@@ -2130,7 +2163,9 @@ class _VoiceProgram:
         Phase-modulation carriers (OscPM) take the program under the same rule: a two-operator voice under a bus runs at 0.54-0.55 T
         interpreted against 0.22 T per node, 0.40-0.42 against 0.16-0.17 T behind a LowPass (tools/time_pm.py).
         Wavetable oscillators (OscTable) take the program under the same rule: 0.76 T interpreted against 0.32 T per node under a bus,
-        0.55 against 0.21 T behind a LowPass (tools/time_wavetable.py)."""
+        0.55 against 0.21 T behind a LowPass (tools/time_wavetable.py).
+        Waveshapers (Shape) likewise: 0.56 T interpreted against 0.22 T per node under a bus, 0.43 against 0.16 T with a LowPass in
+        front of the shaper (tools/time_shaper.py)."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
