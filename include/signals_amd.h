@@ -511,7 +511,7 @@ int sig_latency_voice_bus(int filt_type, int32_t rate, int64_t position, int64_t
                           double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream);
 
 /* Introspection: the launch geometry the two fused entry points use for this problem size -- voices per lane
- * (1, 2 or 4) and consecutive blocks per lane (the span walker, fused_voice.hip).  For measurement tools (the
+ * (1, 2 or 4) and consecutive blocks per lane (the span walker, sig_fused_walk.h).  For measurement tools (the
  * f64 operation count per voice-sample depends on the span) and tests; no device work. */
 int sig_fused_geometry(int32_t voices, int32_t block_frames, int32_t nblocks, int32_t context,
                        int32_t* voices_per_lane, int32_t* blocks_per_lane);

@@ -147,14 +147,14 @@ int launch(Args a, const sig_env::AdsrRows& env, float* out, int64_t out_ld, hip
 {
     const bool vec = (a.voices % 4 == 0) && (a.in_ld % 4 == 0) && (reinterpret_cast<uintptr_t>(a.in) % 16 == 0);
     const int vpt = vec ? 4 : 1;
-    a.voice_tiles = (a.voices + SIG_WAVE * vpt - 1) / (SIG_WAVE * vpt);
-    const int64_t nwg = ((int64_t)a.voice_tiles * a.K + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    a.voice_tiles = sig_voice_tiles(a.voices, vpt);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, 1), nwg)) return (int)hipErrorInvalidValue;
     // rows of loads in flight per lane: 16 for the HBM-bound plain form; the envelope form (f64-issue-bound, one wave
     // per SIMD because of its cold stage-derivation code) measured the same with 8 and with 2 voices per lane
     constexpr int kRing = ENV ? 8 : 16;
-    if (vec) biquad_bus_kernel<4, kRing, ENV, C><<<(unsigned)nwg, 256, 0, stream>>>(a, env);
-    else     biquad_bus_kernel<1, 16, ENV, C><<<(unsigned)nwg, 256, 0, stream>>>(a, env);
+    if (vec) biquad_bus_kernel<4, kRing, ENV, C><<<nwg, 256, 0, stream>>>(a, env);
+    else     biquad_bus_kernel<1, 16, ENV, C><<<nwg, 256, 0, stream>>>(a, env);
     const int err = sig_launch_status();
     if (err) return err;
     return sig_bus::launch_partials<C>(a.partials, a.voice_tiles, a.rows, out, out_ld, stream);

@@ -12,8 +12,7 @@ for f in *.hip; do
   o="${f%.hip}.o"
   stale=0
   [ -f "$o" ] || stale=1
-  extra=""; [ "$f" = fused_voice_b.hip ] && extra=fused_voice.hip      # (it is that file, compiled for the other waveforms)
-  for dep in "$f" $extra sig_common.h sig_osc.h sig_biquad.h sig_noise.h sig_adsr.h sig_bus_tile.h sig_mix_tile.h sig_steady.h sig_table.h ../../include/signals_amd.h; do
+  for dep in "$f" *.h ../../include/signals_amd.h; do      # (every header: none can be forgotten)
     [ "$stale" = 1 ] || { [ "$dep" -nt "$o" ] && stale=1; } || true
   done
   if [ "$stale" = 1 ]; then

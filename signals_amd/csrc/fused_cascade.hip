@@ -23,7 +23,7 @@
 // position - N_previous on a continuing stream, position - min(100, position) on a fresh graph (the reference then
 // renders [p - 100, p) as a block of its own), position itself at frame 0 (no history).
 //
-// Arithmetic as in fused_voice.hip: exact per-row phase t = n / rate * hertz + phase (n / rate for 64 rows at a time, one
+// Arithmetic as in sig_fused_walk.h: exact per-row phase t = n / rate * hertz + phase (n / rate for 64 rows at a time, one
 // row per lane, broadcast by v_readlane), b0-normalised DF2T (4 operations per filter row, both b0 folded into the output
 // weight), envelope as the voice's current linear stage (sig_adsr.h: Segment) folded with the bus weight into one fma
 // per (voice, channel, row), bus sums folded across lanes by sig_bus::FoldedGroup.  The inner filter's output reaches
@@ -288,7 +288,7 @@ int g_force_vpt = 0, g_force_span = 0;         // tuning / test hook (sig_fused_
 int g_tile_sum_kernel = 0;                     // 1 (blocks_per_lane given as its negative): voice tiles added by partials_kernel
 
 void cascade_geometry(int voices, int nblocks, int& vpt, int& span) {
-    auto waves = [&](int v, int s) { return (int64_t)((voices + SIG_WAVE * v - 1) / (SIG_WAVE * v)) * ((nblocks + s - 1) / s); };
+    auto waves = [&](int v, int s) { return sig_span_waves(sig_voice_tiles(voices, v), nblocks, s); };
     double best_cost = 0.0;
     int64_t best_waves = -1;
     vpt = 1; span = 1;
@@ -310,14 +310,14 @@ int launch(CascadeArgs a, const sig_env::AdsrRows& env, float* out, int64_t out_
 {
     int vpt;
     cascade_geometry(a.voices, a.K, vpt, a.span);
-    a.voice_tiles = (a.voices + SIG_WAVE * vpt - 1) / (SIG_WAVE * vpt);
-    const int64_t nwg = ((int64_t)a.voice_tiles * ((a.K + a.span - 1) / a.span) + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    a.voice_tiles = sig_voice_tiles(a.voices, vpt);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, a.span), nwg)) return (int)hipErrorInvalidValue;
     if (sig_bus::tiles_sum_in_workgroup(a.voice_tiles) && !g_tile_sum_kernel) { a.out = out; a.out_ld = out_ld; }
     switch (vpt) {
-        case 1: fused_cascade_kernel<KIND, 1, ENV, C><<<(unsigned)nwg, 256, 0, stream>>>(a, env); break;
-        case 2: fused_cascade_kernel<KIND, 2, ENV, C><<<(unsigned)nwg, 256, 0, stream>>>(a, env); break;
-        default: fused_cascade_kernel<KIND, 4, ENV, C><<<(unsigned)nwg, 256, 0, stream>>>(a, env); break;
+        case 1: fused_cascade_kernel<KIND, 1, ENV, C><<<nwg, 256, 0, stream>>>(a, env); break;
+        case 2: fused_cascade_kernel<KIND, 2, ENV, C><<<nwg, 256, 0, stream>>>(a, env); break;
+        default: fused_cascade_kernel<KIND, 4, ENV, C><<<nwg, 256, 0, stream>>>(a, env); break;
     }
     const int err = sig_launch_status();
     if (err || a.out) return err;                                              // (the kernel added the voice tiles itself)

@@ -155,15 +155,15 @@ int launch_steady_mix(const FusedArgs& a_, bool gain, hipStream_t stream)
         a.span = 1;
         while (a.span < 8 && (int64_t)a.voice_tiles * ((a.K + 2 * a.span - 1) / (2 * a.span)) >= 2048) a.span *= 2;
     }
-    const int64_t nwg = ((int64_t)a.voice_tiles * ((a.K + a.span - 1) / a.span) + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, a.span), nwg)) return (int)hipErrorInvalidValue;
     const bool f32 = a.steady == 3;                                            // sig_fused_set_tuning(closed_form = 3)
     if (gain) {
-        if (f32) fused_steady_mix_kernel<true, true><<<(unsigned)nwg, 256, 0, stream>>>(a);
-        else fused_steady_mix_kernel<true, false><<<(unsigned)nwg, 256, 0, stream>>>(a);
+        if (f32) fused_steady_mix_kernel<true, true><<<nwg, 256, 0, stream>>>(a);
+        else fused_steady_mix_kernel<true, false><<<nwg, 256, 0, stream>>>(a);
     } else {
-        if (f32) fused_steady_mix_kernel<false, true><<<(unsigned)nwg, 256, 0, stream>>>(a);
-        else fused_steady_mix_kernel<false, false><<<(unsigned)nwg, 256, 0, stream>>>(a);
+        if (f32) fused_steady_mix_kernel<false, true><<<nwg, 256, 0, stream>>>(a);
+        else fused_steady_mix_kernel<false, false><<<nwg, 256, 0, stream>>>(a);
     }
     return sig_launch_status();
 }

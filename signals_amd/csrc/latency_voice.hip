@@ -1,8 +1,8 @@
 // Latency mode of the C2 graph (Sine -> LowPass|HighPass -> [x gain] -> [pan] -> bus) for ONE block per launch: a
 // real-time sink pulls 256 frames of 1024 voices at a time, which is far too little work to hide a chain of
-// launches behind (fused_voice.hip's scan kernel + sum_bus + position advance: ~25 us per block through a hipGraph).
+// launches behind (the scan kernel of sig_fused_scan.h + sum_bus + position advance: ~25 us per block through a hipGraph).
 // Here the whole block is one launch with rows x voices parallelism:
-//   * closed form of fused_voice.hip ("steady" kernel): y_n = yss_n + yh_n, steady-state sinusoid + homogeneous
+//   * closed form of sig_fused_steady.h ("steady" kernel): y_n = yss_n + yh_n, steady-state sinusoid + homogeneous
 //     solution of the cold start at r0 = p - c.  Both can be seeded at ANY row: yss from the phase of that row
 //     (sin by the f64 polynomial), yh = [A^(n - r0) (-sss_{r0-1})]_0 with A^k by squaring.  So a lane takes one voice
 //     and one chunk of kRows rows: ~600 f64 operations of set-up, then 7 per row.  voices/64 x N/kRows waves.
@@ -38,7 +38,7 @@ __device__ __forceinline__ M2 m2_mul(const M2& x, const M2& y) {
     return {fma(x.a, y.a, x.b * y.c), fma(x.a, y.b, x.b * y.d), fma(x.c, y.a, x.d * y.c), fma(x.c, y.b, x.d * y.d)};
 }
 
-// sin(2 pi f) in f64 (~1 ulp), any |f| < 2^50 (fused_voice.hip)
+// sin(2 pi f) in f64 (~1 ulp), any |f| < 2^50 (sig_steady.h)
 __device__ __forceinline__ double sin2pi(double f) {
     const double u = fma(f, 2.0, sig_osc::kRoundMagic);
     const double k = u - sig_osc::kRoundMagic;

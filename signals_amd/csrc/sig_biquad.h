@@ -1,4 +1,4 @@
-// Butterworth biquad design shared by biquad.hip and fused_voice.hip.
+// Butterworth biquad design shared by biquad.hip and the fused kernels (sig_fused_*.h).
 #pragma once
 #include "sig_common.h"
 

@@ -1,4 +1,4 @@
-// Cross-lane bus sums for kernels whose lanes are voices (fused_voice.hip, biquad_bus.hip).
+// Cross-lane bus sums for kernels whose lanes are voices (sig_fused_walk.h, sig_fused_steady.h, biquad_bus.hip).
 //   partial[tile][row][c] = sum over the wave's voices of weight[c][v] * y[row][v]
 // A row's sum is a cross-lane sum; doing it per row with a butterfly would cost as much as the recurrences
 // themselves, so rows are staged kPairs/C at a time in a wave-private LDS tile [pair = row*C + c][lane] (row stride
@@ -56,7 +56,7 @@ struct Tile {
     }
 };
 
-// the software-pipelined form of the f64-issue-bound fused kernels (fused_voice.hip): rows are staged either one at a
+// the software-pipelined form of the f64-issue-bound fused kernels (sig_fused_walk.h, sig_fused_steady.h): rows are staged either one at a
 // time (`put`, flushing when the tile is full) or in statically unrolled groups of R (`put_at` + `issue` / `finish`):
 // the wave's LDS operations execute in order, so the 16 reads of a flush may be issued right after the group's last
 // write and consumed a whole group of rows later, which hides their latency.

@@ -13,6 +13,29 @@
 
 static inline int sig_launch_status() { return (int)hipGetLastError(); }
 
+// Launch geometry of the kernels whose waves own 64 * vpt consecutive voices and walk `span` consecutive blocks:
+// voice tiles, waves, and workgroups of four waves (false: more than a grid dimension holds)
+static inline int sig_voice_tiles(int voices, int vpt) { return (voices + SIG_WAVE * vpt - 1) / (SIG_WAVE * vpt); }
+static inline int64_t sig_span_waves(int voice_tiles, int64_t blocks, int span) { return (int64_t)voice_tiles * ((blocks + span - 1) / span); }
+static inline bool sig_workgroups(int64_t waves, unsigned& nwg) {
+    const int64_t n = (waves + 3) / 4;
+    if (n > 0x7fffffffLL) return false;
+    nwg = (unsigned)n;
+    return true;
+}
+
+// one store of a lane's VPT consecutive float32 samples
+namespace sig_vec {
+template <int VPT> struct OutVec;
+template <> struct OutVec<1> { using type = float; };
+template <> struct OutVec<2> { using type = float2; };
+template <> struct OutVec<4> { using type = float4; };
+
+__device__ __forceinline__ void put(float& v, const float (&y)[1]) { v = y[0]; }
+__device__ __forceinline__ void put(float2& v, const float (&y)[2]) { v = make_float2(y[0], y[1]); }
+__device__ __forceinline__ void put(float4& v, const float (&y)[4]) { v = make_float4(y[0], y[1], y[2], y[3]); }
+}  // namespace sig_vec
+
 template <typename T> struct sig_vec4;
 template <> struct sig_vec4<float> { using type = float4; };
 template <> struct sig_vec4<double> { using type = double4; };

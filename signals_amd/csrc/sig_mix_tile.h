@@ -1,4 +1,4 @@
-// The MixMatrix contraction of the fused kernels (fused_voice.hip, BASELINE config 5): 32 staged rows x 64 voices times
+// The MixMatrix contraction of the fused kernels (sig_fused_walk.h, fused_mix.hip; BASELINE config 5): 32 staged rows x 64 voices times
 // the 64 x 64 matrix on the matrix cores, float32 in, float32 out.
 //
 // A float32 is the exact sum of three bfloat16 (8 + 8 + 8 significand bits): x = x0 + x1 + x2, m = m0 + m1 + m2, so

@@ -1,4 +1,4 @@
-// Oscillator waveforms shared by osc_bank.hip and fused_voice.hip: `t` (cycles, f64) -> sample.
+// Oscillator waveforms shared by osc_bank.hip and the fused kernels (sig_fused_*.h): `t` (cycles, f64) -> sample.
 // Reference: src/signals/chain/osc.py:40-62.  See osc_bank.hip for the precision notes.
 #pragma once
 #include "sig_common.h"

@@ -1,6 +1,6 @@
-// Pieces shared by the fused kernels' translation units (fused_voice.hip, fused_mix.hip): the launch arguments, and the
+// Pieces shared by the fused kernels' translation units (fused_voice.hip, fused_voice_b.hip, fused_mix.hip): the launch arguments, and the
 // per-voice constants of the closed form (a sinusoid through an LTI filter: steady state + homogeneous part, see
-// fused_voice.hip "closed form").
+// sig_fused_steady.h).
 #pragma once
 #include "sig_biquad.h"
 #include "sig_osc.h"
@@ -40,7 +40,7 @@ struct BusArgs {
     float* out = nullptr; int64_t out_ld = 0;   // set: the kernel adds the voice tiles itself (sig_bus::sum_tiles_in_workgroup), no partials_kernel launch
 };
 
-// Tuning / test hooks of the fused entry points (fused_voice.hip): one instance, read by both of its translation units
+// Tuning / test hooks of the fused entry points (defined in fused_voice.hip): one instance, read by every translation unit of the family
 struct Tuning { int vpt = 0, span = 0, steady = -1, scan = -1, tile_sum_kernel = 0, mix_f32 = 0; };     // 0 / -1 = the launch heuristics decide
 Tuning& tuning();
 // fused_voice_b.hip: the walkers of Square / Sawtooth / Triangle, called by fused_voice.hip's dispatchers

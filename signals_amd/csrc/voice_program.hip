@@ -1,6 +1,6 @@
 // A whole frame-rate voice graph in ONE launch, gfx950: the general form of the fused voice kernels.
 //
-// The fused kernels of fused_voice.hip / fused_cascade.hip each cover one graph shape (Filter(Osc), Filter(Filter(Osc)) ...).
+// The fused kernels of sig_fused_*.h / fused_cascade.hip each cover one graph shape (Filter(Osc), Filter(Filter(Osc)) ...).
 // Everything else -- an Amp or a Mix behind a filter, RingMod of two filtered voices, three filters in series, block-rate
 // FM together with a second oscillator, blocks shorter than the filter context -- ran one kernel per node (24+ B per
 // voice-sample through HBM) or, for short blocks, the eager pull path (~150 us per block).  Here the per-voice graph is
@@ -39,6 +39,7 @@
 #include "sig_adsr.h"
 #include "sig_biquad.h"
 #include "sig_bus_tile.h"
+#include "sig_noise.h"
 #include "sig_osc.h"
 #include "sig_table.h"
 
@@ -103,12 +104,6 @@ __device__ __forceinline__ double vp_pin(double x) {
     return x;
 }
 
-__device__ __forceinline__ uint64_t vp_mix64(uint64_t z) {                     // noise.hip
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 // sig_biquad.h's design_butter2 with a light tangent: libm's tan() carries a Payne-Hanek reduction for huge arguments whose
 // temporaries set the register budget of the whole kernel (+110 VGPRs, measured), and the argument here is pi Wn / 2 with
 // Wn in (0, 1): tan = sin / cos from the odd polynomial of sig_osc.h on [0, pi/2], cos(x) = sin(pi/2 - x) with pi/2 as hi + lo.
@@ -136,14 +131,6 @@ __device__ __forceinline__ bool vp_design(int type, double cutoff, double rate, 
 }
 
 __device__ __noinline__ double vp_amp(double x, double e) { return copysign(pow(x, e), x); }   // fx.py:60 (kept out of line: pow is long)
-
-template <int VPT> struct VpOut;
-template <> struct VpOut<1> { using type = float; };
-template <> struct VpOut<2> { using type = float2; };
-template <> struct VpOut<4> { using type = float4; };
-__device__ __forceinline__ void vp_put(float& v, const float (&y)[1]) { v = y[0]; }
-__device__ __forceinline__ void vp_put(float2& v, const float (&y)[2]) { v = make_float2(y[0], y[1]); }
-__device__ __forceinline__ void vp_put(float4& v, const float (&y)[4]) { v = make_float4(y[0], y[1], y[2], y[3]); }
 
 // Register-file sizes per variant (the host picks the smallest variant a program fits).  SMALL: two filter slots, three
 // oscillator slots, four parameter registers, one temporary (a temporary is a whole row group: 8 rows x 2 voices = 32 VGPRs), no Amp / ADSR / White -- the common synthesiser voice; its
@@ -182,7 +169,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     using L = VpLimits<SMALL>;
     constexpr int NF = L::NF, NO = L::NO, NP = L::NP, NT = L::NT;
     constexpr bool EXT = L::EXT;
-    using Vec = typename VpOut<VPT>::type;
+    using Vec = typename sig_vec::OutVec<VPT>::type;
     const int64_t item = (int64_t)blockIdx.x * 4 + wave;
     const int vt = (int)(item % a.voice_tiles);
     const int64_t b_first = (item / a.voice_tiles) * a.span;
@@ -748,13 +735,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #pragma unroll
                             for (int r = 0; r < R; ++r)
 #pragma unroll
-                                for (int i = 0; i < VPT; ++i) {
-                                    const int ch = v0 + i;
-                                    const uint64_t h = vp_mix64(a.seeds[ia & 1] + (uint64_t)(n + r) * 0x9E3779B97F4A7C15ULL +
-                                                                (uint64_t)(ch >> 1) * 0xD1B54A32D192ED03ULL);
-                                    const uint32_t k = ((ch & 1) ? (uint32_t)(h >> 32) : (uint32_t)h) >> 8;
-                                    acc[r][i] = (double)((float)k * 5.9604644775390625e-8f);
-                                }
+                                for (int i = 0; i < VPT; ++i) acc[r][i] = (double)sig_noise::noise_value(a.seeds[ia & 1], n + r, v0 + i);
                         }
                     }
                     break;
@@ -800,7 +781,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #pragma unroll
                         for (int i = 0; i < VPT; ++i) y32[i] = (float)acc[r][i];
                         if (live0) {
-                            Vec o; vp_put(o, y32);
+                            Vec o; sig_vec::put(o, y32);
                             *reinterpret_cast<Vec*>(dst + (n + r - a.position) * a.out_ld) = o;
                         }
                     }
@@ -866,6 +847,13 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
 // A SPECIALISED build of this file (signals_amd/specialise.py: hipcc --genco with the program, the exact register file, the
 // voices per lane and the sink as macros): one kernel, the same source as the interpreter with the program a compile-time
 // constant -- the dispatch loop unrolls and every switch folds.  Attached to the library with sig_voice_program_attach.
+// does the program this file is specialised for have an instruction with this opcode?
+constexpr bool vp_static_has(int op) {
+    constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
+    for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k)
+        if ((c[k] & 31u) == (uint32_t)op) return true;
+    return false;
+}
 }  // namespace
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
 #ifndef SIG_VP_S_TAB
@@ -877,30 +865,8 @@ void sig_vp_specialised(VpArgs a, VpTables tb)
 void sig_vp_specialised(VpArgs a)
 #endif
 {
-    constexpr bool kBand = [] {
-        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
-        bool band = false;
-        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) band |= (c[k] & 31u) == (uint32_t)SIG_VP_BAND;
-        return band;
-    }();
-    constexpr bool kPm = [] {
-        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
-        bool pm = false;
-        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) pm |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCPM;
-        return pm;
-    }();
-    constexpr bool kTab = [] {
-        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
-        bool tab = false;
-        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) tab |= (c[k] & 31u) == (uint32_t)SIG_VP_OSCTABLE || (c[k] & 31u) == (uint32_t)SIG_VP_SHAPE;
-        return tab;
-    }();
-    constexpr bool kShape = [] {
-        constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
-        bool shape = false;
-        for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) shape |= (c[k] & 31u) == (uint32_t)SIG_VP_SHAPE;
-        return shape;
-    }();
+    constexpr bool kBand = vp_static_has(SIG_VP_BAND), kPm = vp_static_has(SIG_VP_OSCPM), kShape = vp_static_has(SIG_VP_SHAPE);
+    constexpr bool kTab = vp_static_has(SIG_VP_OSCTABLE) || kShape;
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
 #if SIG_VP_S_TAB
     vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape>(a, tb);
@@ -979,7 +945,7 @@ bool fits_small(const VpNeeds& n) {
 // keeps a lone wave per SIMD busy, and the bus flush and the row's n / rate are paid per lane -- taken when the store is
 // 16-byte aligned (or there is a bus) and the launch still has a wave for every SIMD
 void vp_geometry(const VpArgs& a, int store_aligned, bool four, int& vpt, int& span) {
-    auto waves = [&](int v, int s) { return (int64_t)((a.voices + SIG_WAVE * v - 1) / (SIG_WAVE * v)) * ((a.K + s - 1) / s); };
+    auto waves = [&](int v, int s) { return sig_span_waves(sig_voice_tiles(a.voices, v), a.K, s); };
     const bool bus = a.partials != nullptr;
     vpt = ((bus || store_aligned >= 2) && waves(2, 1) >= 1024) ? 2 : 1;
     const bool can4 = four && (bus || store_aligned >= 4);
@@ -1255,19 +1221,19 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     int vpt = 1;
     vp_geometry(a, aligned, vp_find_special(a, P, 4, bus_channels) != nullptr, vpt, a.span);
     const bool small_file = fits_small(need);
-    a.voice_tiles = (voices + SIG_WAVE * vpt - 1) / (SIG_WAVE * vpt);
-    const int64_t nwg = ((int64_t)a.voice_tiles * ((a.K + a.span - 1) / a.span) + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    a.voice_tiles = sig_voice_tiles(voices, vpt);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, a.span), nwg)) return (int)hipErrorInvalidValue;
     if (bus_channels > 0 && sig_bus::tiles_sum_in_workgroup(a.voice_tiles)) { a.bus_out = out; a.bus_out_ld = out_ld; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     int err;
     if (hipFunction_t fn = vp_find_special(a, P, vpt, bus_channels)) {         // this very program, built as straight-line code
         void* params[] = {&a, &tb};                                           // (an image built for a table program takes both, any other the first)
-        err = (int)hipModuleLaunchKernel(fn, (unsigned)nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
+        err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, small_file, need, bus_channels, (unsigned)nwg, table_lds, s);
-    else err = vp_launch_file<1>(a, tb, small_file, need, bus_channels, (unsigned)nwg, table_lds, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, small_file, need, bus_channels, nwg, table_lds, s);
+    else err = vp_launch_file<1>(a, tb, small_file, need, bus_channels, nwg, table_lds, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);

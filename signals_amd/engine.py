@@ -60,7 +60,7 @@ from signals_amd.chain import (
 from signals_amd.chain import ext, files, fixed, fx, noise, osc, shape
 
 CONTEXT = 100
-SCAN_MAX_CHAINS = 16384      # signals_amd/csrc/fused_voice.hip: kScanMaxChains
+SCAN_MAX_CHAINS = 16384      # signals_amd/csrc/sig_fused_scan.h: kScanMaxChains
 SCAN_MAX_ROWS = 512          # kScanMaxL * 64
 
 
@@ -1490,7 +1490,7 @@ class _VoiceChain:
         """(controls, pan) with the voices re-ordered for the bus launch: groups of 64 neighbours in cutoff, dealt round
         robin over the voice tiles of 64 * voices_per_lane, slot-major (slot i of every lane of a wave = one group).  The bus is a sum
         over voices, so any order renders the same bus up to the rounding of the sum; this one lets the Sine closed
-        form drop the decayed homogeneous part of whole voice slots (fused_voice.hip: fused_steady_bus_kernel).
+        form drop the decayed homogeneous part of whole voice slots (sig_fused_steady.h: fused_steady_bus_kernel).
         Built once per parameter upload (it is kept with the closed form's constants)."""
         index = self.cutoff_order(ctl, voices_per_lane)
         if index is None:

@@ -1,7 +1,8 @@
 #!/bin/bash
 # tuning builds of ONE kernel file: [FILE=fused_voice.hip] tools/build_variant.sh <name> [-D...]  ->  scratch/variants/lib_<name>.so
 # (same ABI, loaded with SIG_LIB_PATH; for fused_voice.hip -DSIG_TUNE_SINE_ONLY restricts the template instantiations
-# to what tools/tune_kernels.py launches so a variant builds in seconds)
+# to what tools/tune_kernels.py launches -- that unit alone, Sine kernels, stereo bus -- so a variant builds in seconds;
+# the kernels themselves are in sig_fused_walk.h / sig_fused_steady.h / sig_fused_scan.h)
 set -euo pipefail
 cd "$(dirname "$0")/../signals_amd/csrc"
 name=$1; shift
