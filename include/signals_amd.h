@@ -36,13 +36,16 @@ enum { SIG_F32 = 0, SIG_F64 = 1 };
 enum { SIG_OSC_SINE = 0, SIG_OSC_SQUARE = 1, SIG_OSC_SAWTOOTH = 2, SIG_OSC_TRIANGLE = 3 };
 
 /* critical-frequency filter types: fx.py:68-72 (only lp/hp are live in the reference, fx.py:142-151) */
-enum { SIG_FILT_LOWPASS = 0, SIG_FILT_HIGHPASS = 1, SIG_FILT_BANDPASS = 2, SIG_FILT_BANDSTOP = 3 };
+enum { SIG_FILT_LOWPASS = 0, SIG_FILT_HIGHPASS = 1, SIG_FILT_BANDPASS = 2, SIG_FILT_BANDSTOP = 3,
+       /* filter slots of a voice program that a FILTERQ word runs: the resonant low-pass / high-pass of chain/ext.py */
+       SIG_FILT_RES_LOWPASS = 4, SIG_FILT_RES_HIGHPASS = 5 };
 
 /* element-wise effects: fx.py:35-60 */
 enum { SIG_EW_GAIN = 0, SIG_EW_MIX = 1, SIG_EW_RINGMOD = 2, SIG_EW_AMP = 3 };
 
 /* bits OR-ed into the optional device status word by kernels (never cleared by them) */
-enum { SIG_STATUS_BAD_CUTOFF = 1 };  /* Wn <= 0 or >= 1: scipy raises ValueError (fx.py:99-102) */
+enum { SIG_STATUS_BAD_CUTOFF = 1,     /* Wn <= 0 or >= 1: scipy raises ValueError (fx.py:99-102) */
+       SIG_STATUS_BAD_RESONANCE = 2 };  /* a resonant filter's q that is not finite and > 0 (build-defined, chain/ext.py ResonantFilter) */
 
 int sig_abi_version(void);
 
@@ -137,6 +140,25 @@ int sig_biquad_coldstart(int type, int32_t rate, int64_t position,
                          const void* in, int64_t in_ld, int64_t in_history,
                          void* out, int64_t out_ld, int32_t dtype,
                          int32_t* status, void* stream);
+
+/* sig_biquad_coldstart with a resonance control: the resonant 2-pole low-pass / high-pass of chain/ext.py ResonantLowPass /
+ * ResonantHighPass (build-defined: every filter of the reference is a Butterworth at q = 1/sqrt2).  Per voice and block, in f64:
+ *   wn = clip(cutoff / (rate / 2), 0, 1);  k = tan(pi wn / 2);  d = 1 / q;  nrm = 1 / (1 + d k + k k)
+ *   lp: b = (k k, 2 k k, k k) nrm      hp: b = (1, -2, 1) nrm      a = (1, 2 (k k - 1) nrm, (1 - d k + k k) nrm)
+ * -- the bilinear transform with prewarping, the RBJ cookbook's low-pass / high-pass with alpha = sin(w0) / (2 q) -- then the same
+ * cold-start recurrence, buffers and block semantics as sig_biquad_coldstart (the same kernel source).
+ * resonance: f64 (resonance_blocks, voices | 1) contiguous rows of q, resonance_blocks in {1, nblocks} like cutoff_blocks (either
+ * control may be per block on its own: a swept cutoff, a swept q), resonance_stride 0 / 1; NULL: unplugged = 1/sqrt2, the damping is
+ * sqrt2 itself and the call computes what sig_biquad_coldstart computes.  A q that is 0, negative, NaN or +-inf gives NaN rows for
+ * that voice (in that block) and sets SIG_STATUS_BAD_RESONANCE, next to SIG_STATUS_BAD_CUTOFF for the cutoff; voices past `voices`
+ * (padding lanes) never set either.  type: SIG_FILT_LOWPASS | SIG_FILT_HIGHPASS.  Argument errors: hipErrorInvalidValue, nothing launched. */
+int sig_biquad_coldstart_q(int type, int32_t rate, int64_t position,
+                           int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                           const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
+                           const double* resonance, int32_t resonance_stride, int32_t resonance_blocks,
+                           const void* in, int64_t in_ld, int64_t in_history,
+                           void* out, int64_t out_ld, int32_t dtype,
+                           int32_t* status, void* stream);
 
 /* sig_biquad_coldstart whose stored rows are multiplied by a per-voice ADSR envelope evaluated at the row's
  * time (f32 buffers): RingMod(Filter(x), ADSR) -- fx.py:43-46 over fx.py:85-121 and the envelope of sig_adsr --
@@ -570,6 +592,11 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *   SHAPE  acc = waveshaper lookup (sig_shaper_table's expression) of the accumulator in table slot b of the `tables` argument,
  *          column = params[c] (select rows), c == -1: unplugged = column 0.  Refused with BAND or OSCPM and without its tables, like
  *          OSCTABLE.  A slot that only SHAPE words read may have any T >= 2; a slot an OSCTABLE word reads is a power of two
+ *   FILTERQ acc = resonant filter slot a applied to acc (sig_biquad_coldstart_q's design, the FILTER word's recurrence): the slot's
+ *          filter_type is SIG_FILT_RES_LOWPASS | SIG_FILT_RES_HIGHPASS, its cutoff rows as for FILTER, q = params[c] read per block
+ *          with the cutoff (the rows of the block the design is for), c == -1: unplugged = 1/sqrt2.  One FILTERQ word per slot;
+ *          FILTER words run in the same program (ResonantHighPass -> LowPass is one program).  Refused together with BAND, OSCPM,
+ *          OSCTABLE or SHAPE, hipErrorInvalidValue: the interpreter variant with the resonant design has none of them
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -588,13 +615,14 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * series there).  bus_channels 0: out (nblocks * block_frames, voices) float32; 1 | 2: out (.., bus_channels) = sum over voices of
  * bus_gains[c, v] * sample (bus_gains NULL: mono sum), float64 accumulation in a fixed order; workspace of
  * sig_fused_voice_bus_workspace(voices, rows, bus_channels) bytes.  f64 arithmetic, no float32 rounding between the nodes.
- * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF. */
+ * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF; a FILTERQ slot's q that is not finite and
+ * > 0 likewise and sets SIG_STATUS_BAD_RESONANCE (never for a voice past `voices`). */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
-       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14 };
+       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15 };
 enum { SIG_VP_MAX_TABLES = 2 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE: c may be -1 */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ: c may be -1 */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];

@@ -17,9 +17,10 @@ LIB_PATH = pathlib.Path(os.environ.get('SIG_LIB_PATH') or pathlib.Path(__file__)
 
 F32, F64 = 0, 1
 OSC_KINDS = {'Sine': 0, 'Square': 1, 'Sawtooth': 2, 'Triangle': 3}
-FILT_TYPES = {'lp': 0, 'hp': 1, 'bp': 2, 'bs': 3}
+FILT_TYPES = {'lp': 0, 'hp': 1, 'bp': 2, 'bs': 3, 'rlp': 4, 'rhp': 5}     # rlp / rhp: a voice program's resonant slots (SIG_FILT_RES_*)
 EW_OPS = {'Gain': 0, 'Mix': 1, 'RingMod': 2, 'Amp': 3}
 STATUS_BAD_CUTOFF = 1
+STATUS_BAD_RESONANCE = 2
 ABI_VERSION = 7
 SINE_FAST_MAX_CYCLES = 2.0 ** 26     # sig_osc.h kSineFastMaxT: |t| up to which the fused Sine kernels advance the phase incrementally
 
@@ -49,11 +50,12 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 VP_MAX_TABLES = 2
 VP_TABLE_OPS = ('OscTable', 'Shape')        # the instructions of the table variant (SIG_VP_S_TAB): table slot b, select = parameter slot c | -1
+VP_RES_OPS = ('FilterQ',)                   # the instruction of the resonant variant (SIG_VP_S_RES): filter slot a, q = parameter slot c | -1
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
 
 
@@ -113,6 +115,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
+        'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
         'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
         'sig_band_coldstart': cold + [dp, i32, dp, i32] + window + [vp, i64, i32, vp, vp],
@@ -438,6 +441,36 @@ def biquad_coldstart(btype: str, rate: int, position: int, block_frames: int, nb
         return out
     _check(lib().sig_biquad_coldstart(*head, in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
                                       _ptr(status), _stream(out)), 'sig_biquad_coldstart')
+    return out
+
+
+def _block_rows(t: torch.Tensor, what: str, nblocks: int, voices: int, broadcast: bool = False):
+    """(ptr, stride, blocks) of a cold-start filter's control rows: contiguous f64 (1 | nblocks, 1 | voices); narrower than the
+    voices: the reference's IndexError (it indexes crit[0, i] for every channel i, fx.py:99) unless `broadcast` (one column for all)"""
+    if t.dtype != torch.float64 or t.dim() != 2 or not t.is_contiguous():
+        raise NativeError(f'{what} must be a contiguous float64 2-D tensor')
+    if t.shape[0] not in (1, nblocks) or t.shape[1] not in (1, voices):
+        raise NativeError(f'{what} shape {tuple(t.shape)} vs blocks {nblocks} voices {voices}')
+    if t.shape[1] != voices and voices != 1 and not broadcast:
+        raise IndexError(f'index {t.shape[1]} is out of bounds for axis 1 with size {t.shape[1]}')
+    return t.data_ptr(), 0 if t.shape[1] == 1 else 1, t.shape[0]
+
+
+def biquad_coldstart_q(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
+                       cutoff: torch.Tensor, resonance: torch.Tensor | None, buf: torch.Tensor, history: int, out: torch.Tensor,
+                       status: torch.Tensor | None = None) -> torch.Tensor:
+    """`biquad_coldstart` with a resonance row (sig_biquad_coldstart_q: the resonant low-pass / high-pass of chain/ext.py).
+    cutoff: f64 (1|nblocks, V); resonance: f64 (1|nblocks, V|1), a one-column row holds for every voice (the nodes refuse a narrow
+    one before they get here); each per block on its own; resonance None: unplugged = 1/sqrt2 (the Butterworth design)."""
+    _gpu(cutoff, resonance, buf, out, status)
+    _audio(buf, 'biquad in')
+    _audio(out, 'biquad out')
+    voices = out.shape[1]
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
+    q = (None, 0, 1) if resonance is None else _block_rows(resonance, 'resonance', nblocks, voices, broadcast=True)
+    _check(lib().sig_biquad_coldstart_q(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
+                                        *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, in_ptr, buf.stride(0), history,
+                                        out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), 'sig_biquad_coldstart_q')
     return out
 
 
@@ -1004,7 +1037,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None) -> torch.Tensor:
     """One launch for a whole per-voice graph (sig_voice_program_ex; `tables`: the float32 (T, W) tables of its OscTable and Shape words).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
-    'lp' | 'hp', level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
+    'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
     tensors = [t for pair in oscs for t in pair] + list(params) + [f[0] for f in filters] + list((adsr or {}).values())
     _gpu(out, bus_gains, workspace, status, *tensors, *(tables or ()))
@@ -1058,7 +1091,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's and Shape's c = -1: 15)
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's and FilterQ's c = -1: 15)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

@@ -7,6 +7,7 @@ with a Butterworth biquad designed per channel in the kernel.
 """
 import abc
 import enum
+import typing
 
 import torch
 
@@ -105,7 +106,10 @@ class CritFilter(Effect, abc.ABC):
     def context_frames(self) -> int:
         return 100
 
-    def _filter(self, request: Request, crit_1: torch.Tensor, crit_2: torch.Tensor = None) -> torch.Tensor:
+    def _filter(self, request: Request, crit_1: torch.Tensor, crit_2: torch.Tensor = None,
+                resonant: bool = False, resonance: typing.Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`resonant` (chain/ext.py ResonantFilter, single-cutoff types only): the resonant design with `resonance`, a one-row q
+        tensor, or None for an unplugged port (1/sqrt2); otherwise a Butterworth filter of the reference"""
         assert Shape.of_array(crit_1).frames == 1
         if crit_2 is not None:
             assert Shape.of_array(crit_2).frames == 1
@@ -142,6 +146,16 @@ class CritFilter(Effect, abc.ABC):
             return _native.band_coldstart(str(self.type()), request.loc.rate, request.loc.position, shape.frames, 1,
                                           context_frames, cutoff, high, buf, history, result,
                                           status=self._status.tensor)
+        if resonant:
+            if resonance is not None:
+                assert Shape.of_array(resonance).frames == 1
+                if resonance.shape[1] < shape.channels:
+                    raise IndexError(f'index {resonance.shape[1]} is out of bounds for axis 1 with size {resonance.shape[1]}')
+                resonance = resonance[:, :shape.channels]
+                if not resonance.is_contiguous():
+                    resonance = resonance.contiguous()
+            return _native.biquad_coldstart_q(str(self.type()), request.loc.rate, request.loc.position, shape.frames, 1,
+                                              context_frames, cutoff, resonance, buf, history, result, status=self._status.tensor)
         return _native.biquad_coldstart(str(self.type()), request.loc.rate, request.loc.position,
                                         shape.frames, 1, context_frames, cutoff, buf, history, result,
                                         status=self._status.tensor)

@@ -11,6 +11,7 @@
 // Algorithmic traffic: 4 B read + 4 B written per voice-sample; the (N+c)/N context re-read is the
 // previous block's tail and is served by L2/Infinity Cache when the neighbouring wave ran recently.
 #include <cstdlib>
+#include <type_traits>
 
 #include "sig_adsr.h"
 #include "sig_biquad.h"
@@ -43,12 +44,16 @@ __device__ __forceinline__ void pack(double4& v, const double (&y)[4]) { v = mak
 // ENV: multiply the stored rows by a per-voice ADSR envelope evaluated at the row's time (the
 // RingMod(Filter, ADSR) pair of BASELINE config 3 without a separate pass; sig_adsr.h).  n/rate is computed for
 // 64 rows at a time, one row per lane, and broadcast with v_readlane, like in the oscillator kernels.
-template <typename T, int VPT, int kRing, bool ENV>   // kRing = rows of loads in flight per lane
-__global__ __launch_bounds__(256) void biquad_coldstart_kernel(
+// RES: the resonance rows of sig_biquad_coldstart_q (ResRows), or NoRes: the Butterworth design, and nothing of the other in the code
+struct NoRes {};
+struct ResRows { const double* ptr; int rs, blocks; };    // (blocks, voices | 1) f64 rows of q; ptr null: unplugged = 1/sqrt2
+
+template <typename T, int VPT, int kRing, bool ENV, typename RES>   // kRing = rows of loads in flight per lane
+__device__ __forceinline__ void biquad_coldstart_body(
     int type, double rate, int64_t position, int N, int K, int ctx, int voices,
     const double* __restrict__ cutoff, int cs, int cutoff_blocks,
     const T* __restrict__ in, int64_t in_ld, T* __restrict__ out, int64_t out_ld,
-    int voice_tiles, int* __restrict__ status, sig_env::AdsrRows env)
+    int voice_tiles, int* __restrict__ status, const sig_env::AdsrRows& env, [[maybe_unused]] const RES& res)
 {
     using Vec = typename RowVec<T, VPT>::type;
     const int lane = threadIdx.x & 63;
@@ -65,15 +70,28 @@ __global__ __launch_bounds__(256) void biquad_coldstart_kernel(
 
     Biquad q[VPT];
     double z0[VPT], z1[VPT];
-    bool ok = true;
+    if constexpr (std::is_same<RES, NoRes>::value) {
+        bool ok = true;
 #pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-        const int v = (vc + i < voices) ? vc + i : vc;
-        const double hz = cutoff[(cutoff_blocks > 1 ? b * (int64_t)(cs ? voices : 1) : 0) + (int64_t)v * cs];
-        ok &= design_butter2(type, hz, rate, q[i]);
-        z0[i] = 0.0; z1[i] = 0.0;
+        for (int i = 0; i < VPT; ++i) {
+            const int v = (vc + i < voices) ? vc + i : vc;
+            const double hz = cutoff[(cutoff_blocks > 1 ? b * (int64_t)(cs ? voices : 1) : 0) + (int64_t)v * cs];
+            ok &= design_butter2(type, hz, rate, q[i]);
+            z0[i] = 0.0; z1[i] = 0.0;
+        }
+        if (!ok && live && status) atomicOr(status, SIG_STATUS_BAD_CUTOFF);
+    } else {
+        int bad = 0;                                                           // SIG_STATUS_BAD_CUTOFF | SIG_STATUS_BAD_RESONANCE
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+            const int v = (vc + i < voices) ? vc + i : vc;
+            const double hz = cutoff[(cutoff_blocks > 1 ? b * (int64_t)(cs ? voices : 1) : 0) + (int64_t)v * cs];
+            const double* r = res.ptr ? res.ptr + (res.blocks > 1 ? b * (int64_t)(res.rs ? voices : 1) : 0) + (int64_t)v * res.rs : nullptr;
+            bad |= sig_biquad::design_resonant2(type, hz, r, rate, q[i]);
+            z0[i] = 0.0; z1[i] = 0.0;
+        }
+        if (bad && live && status) atomicOr(status, bad);                      // (a dead lane shadows voice 0, which a live lane reports)
     }
-    if (!ok && live && status) atomicOr(status, SIG_STATUS_BAD_CUTOFF);
     sig_env::Voice ev[ENV ? VPT : 1];
     double q_lane = 0.0;
     if (ENV) {
@@ -124,6 +142,30 @@ __global__ __launch_bounds__(256) void biquad_coldstart_kernel(
             }
         }
     }
+}
+
+template <typename T, int VPT, int kRing, bool ENV>
+__global__ __launch_bounds__(256) void biquad_coldstart_kernel(
+    int type, double rate, int64_t position, int N, int K, int ctx, int voices,
+    const double* __restrict__ cutoff, int cs, int cutoff_blocks,
+    const T* __restrict__ in, int64_t in_ld, T* __restrict__ out, int64_t out_ld,
+    int voice_tiles, int* __restrict__ status, sig_env::AdsrRows env)
+{
+    biquad_coldstart_body<T, VPT, kRing, ENV>(type, rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld,
+                                              voice_tiles, status, env, NoRes{});
+}
+
+// the same body with the resonant design (sig_biquad_coldstart_q): a kernel of its own, so that the one above keeps its arguments
+// and its code
+template <typename T, int VPT, int kRing>
+__global__ __launch_bounds__(256) void biquad_coldstart_q_kernel(
+    int type, double rate, int64_t position, int N, int K, int ctx, int voices,
+    const double* __restrict__ cutoff, int cs, int cutoff_blocks, ResRows res,
+    const T* __restrict__ in, int64_t in_ld, T* __restrict__ out, int64_t out_ld,
+    int voice_tiles, int* __restrict__ status)
+{
+    biquad_coldstart_body<T, VPT, kRing, false>(type, rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld,
+                                                voice_tiles, status, sig_env::AdsrRows{}, res);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -245,7 +287,7 @@ template <typename T, bool ENV>
 int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K, int32_t ctx, int32_t voices,
                   const double* cutoff, int32_t cs, int32_t cutoff_blocks,
                   const T* in, int64_t in_ld, T* out, int64_t out_ld, int32_t* status, hipStream_t stream,
-                  const sig_env::AdsrRows& env)
+                  const sig_env::AdsrRows& env, const ResRows* res = nullptr)
 {
     auto ok = [&](int vpt) {
         return (voices % vpt == 0) && (in_ld % vpt == 0) && (out_ld % vpt == 0) &&
@@ -266,7 +308,7 @@ int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K
         int span = (int)(((int64_t)tiles * K) / 1024);
         if (span > 4) span = 4;
         if (walk_env >= 0) span = walk_env;                                    // tuning: 0/1 disables
-        if (span >= 2 && N > ctx && cutoff_blocks == 1 && variant == 0) {
+        if (span >= 2 && N > ctx && cutoff_blocks == 1 && variant == 0 && !res) {   // (the resonant entry: the plain kernel only)
             const int64_t items = (int64_t)tiles * ((K + span - 1) / span);
             const int64_t nwg = (items + 3) / 4;
             if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
@@ -301,8 +343,17 @@ int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K
     const int64_t items = (int64_t)voice_tiles * K;
     const int64_t nwg = (items + 3) / 4;
     if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-#define SIG_BQ(V, R) biquad_coldstart_kernel<T, V, R, ENV><<<(unsigned)nwg, 256, 0, stream>>>( \
-        type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld, voice_tiles, status, env)
+#define SIG_BQ(V, R) do { \
+        if constexpr (!ENV) { \
+            if (res) { \
+                biquad_coldstart_q_kernel<T, V, R><<<(unsigned)nwg, 256, 0, stream>>>( \
+                    type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, *res, in, in_ld, out, out_ld, voice_tiles, status); \
+                break; \
+            } \
+        } \
+        biquad_coldstart_kernel<T, V, R, ENV><<<(unsigned)nwg, 256, 0, stream>>>( \
+            type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld, voice_tiles, status, env); \
+    } while (0)
     switch (vpt * 100 + ring) {
         case 108: SIG_BQ(1, 8); break;
         case 116: SIG_BQ(1, 16); break;
@@ -326,9 +377,10 @@ namespace {
 int run_biquad(int type, int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context,
                int32_t voices, const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
                const void* in, int64_t in_ld, int64_t in_history, void* out, int64_t out_ld, int32_t dtype,
-               int32_t* status, void* stream, const sig_env::AdsrRows* env)
+               int32_t* status, void* stream, const sig_env::AdsrRows* env, const ResRows* res = nullptr)
 {
     SIG_CHECK_ARG(type == SIG_FILT_LOWPASS || type == SIG_FILT_HIGHPASS);
+    SIG_CHECK_ARG(!res || (!env && (res->rs == 0 || res->rs == 1) && (res->blocks == 1 || res->blocks == nblocks)));
     SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
     SIG_CHECK_ARG(cutoff != nullptr && in != nullptr && out != nullptr);
     SIG_CHECK_ARG(cutoff_stride == 0 || cutoff_stride == 1);
@@ -349,12 +401,12 @@ int run_biquad(int type, int32_t rate, int64_t position, int32_t block_frames, i
         return env ? launch_biquad<float, true>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, *env)
                    : launch_biquad<float, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
-                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, none);
+                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, none, res);
     }
     if (dtype == SIG_F64 && !env)
         return launch_biquad<double, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
                                             cutoff_stride, cutoff_blocks, static_cast<const double*>(in), in_ld,
-                                            static_cast<double*>(out), out_ld, status, s, none);
+                                            static_cast<double*>(out), out_ld, status, s, none, res);
     return (int)hipErrorInvalidValue;
 }
 
@@ -382,4 +434,17 @@ extern "C" int sig_biquad_coldstart_env(int type, int32_t rate, int64_t position
     SIG_CHECK_ARG(sig_env::load_rows(adsr_params, adsr_strides, env));
     return run_biquad(type, rate, position, block_frames, nblocks, context, voices, cutoff, cutoff_stride, cutoff_blocks,
                       in, in_ld, in_history, out, out_ld, SIG_F32, status, stream, &env);
+}
+
+extern "C" int sig_biquad_coldstart_q(int type, int32_t rate, int64_t position,
+                                      int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                                      const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
+                                      const double* resonance, int32_t resonance_stride, int32_t resonance_blocks,
+                                      const void* in, int64_t in_ld, int64_t in_history,
+                                      void* out, int64_t out_ld, int32_t dtype,
+                                      int32_t* status, void* stream)
+{
+    const ResRows res{resonance, resonance_stride, resonance_blocks};          // (a null row: unplugged, its stride and count still checked)
+    return run_biquad(type, rate, position, block_frames, nblocks, context, voices, cutoff, cutoff_stride, cutoff_blocks,
+                      in, in_ld, in_history, out, out_ld, dtype, status, stream, nullptr, &res);
 }

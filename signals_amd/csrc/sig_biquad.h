@@ -27,6 +27,32 @@ __device__ __forceinline__ bool design_butter2(int type, double cutoff, double r
     return !bad;
 }
 
+// Resonant 2-pole low-pass / high-pass (chain/ext.py ResonantLowPass / ResonantHighPass): design_butter2's bilinear transform with
+// the damping 1/q in place of sqrt2 -- the RBJ cookbook's low-pass / high-pass (alpha = sin(w0) / (2 q)) in another form, the
+// Butterworth response at q = 1/sqrt2.  `resonance` null: unplugged, the damping is sqrt2 itself (design_butter2's bits).
+// Returns 0 or the status bits of what was refused (the coefficients are then NaN): SIG_STATUS_BAD_CUTOFF as design_butter2,
+// SIG_STATUS_BAD_RESONANCE for a q that is not finite and > 0.
+__device__ __forceinline__ int design_resonant2(int type, double cutoff, const double* resonance, double rate, Biquad& q) {
+    double wn = cutoff / (rate * 0.5);
+    wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
+    int bad = !(wn > 0.0 && wn < 1.0) ? SIG_STATUS_BAD_CUTOFF : 0;
+    double d = kSqrt2;
+    if (resonance) {
+        const double r = *resonance;
+        if (!(r > 0.0 && r < __builtin_inf())) bad |= SIG_STATUS_BAD_RESONANCE;     // 0, negative, NaN, +-inf
+        d = 1.0 / r;
+    }
+    const double k = tan(kPi * wn / 2.0);
+    const double k2 = k * k;
+    const double nrm = 1.0 / (1.0 + d * k + k2);
+    if (type == SIG_FILT_LOWPASS) { q.b0 = k2 * nrm; q.b1 = 2.0 * k2 * nrm; q.b2 = q.b0; }
+    else                          { q.b0 = nrm;      q.b1 = -2.0 * nrm;     q.b2 = nrm;  }
+    q.a1 = 2.0 * (k2 - 1.0) * nrm;
+    q.a2 = (1.0 - d * k + k2) * nrm;
+    if (bad) { q.b0 = q.b1 = q.b2 = q.a1 = q.a2 = __builtin_nan(""); }
+    return bad;
+}
+
 // ---- 4th-order band filters: butter(2, [lo, hi], 'bp'|'bs', output='sos') = two sections --------------
 // Restatement of scipy's chain (buttap -> lp2bp_zpk / lp2bs_zpk -> bilinear_zpk -> zpk2sos, pairing
 // 'nearest'), fs = 2:  w = 4 tan(pi Wn / 2), bw = w2 - w1, wo = sqrt(w1 w2); prototype pole p = (-1+j)/sqrt2

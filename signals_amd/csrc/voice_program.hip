@@ -130,6 +130,26 @@ __device__ __forceinline__ bool vp_design(int type, double cutoff, double rate, 
     return !bad;
 }
 
+// vp_design with the damping as an argument: the resonant low-pass / high-pass of chain/ext.py (sig_biquad.h design_resonant2 with the
+// light tangent), d = 1 / q -- one divide more per voice and block -- or sqrt2 for a Butterworth slot of the same program, which
+// then gets vp_design's bits.  `lowpass`: the slot's response; `q_ok`: the resonance was finite and > 0 (or unplugged).  Returns 0 or
+// the status bits of what was refused.
+__device__ __forceinline__ int vp_design_res(bool lowpass, double cutoff, double d, bool q_ok, double rate, Biquad& q) {
+    double wn = cutoff / (rate * 0.5);
+    wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
+    const int bad = (!(wn > 0.0 && wn < 1.0) ? SIG_STATUS_BAD_CUTOFF : 0) | (q_ok ? 0 : SIG_STATUS_BAD_RESONANCE);
+    const double x = sig_biquad::kPi * wn / 2.0;
+    const double k = VpTan{}(x);
+    const double k2 = k * k;
+    const double nrm = 1.0 / (1.0 + d * k + k2);
+    q.b0 = lowpass ? k2 * nrm : nrm;
+    q.a1 = 2.0 * (k2 - 1.0) * nrm;
+    q.a2 = (1.0 - d * k + k2) * nrm;
+    if (bad) { q.b0 = q.a1 = q.a2 = __builtin_nan(""); }
+    q.b1 = q.b2 = 0.0;
+    return bad;
+}
+
 __device__ __noinline__ double vp_amp(double x, double e) { return copysign(pow(x, e), x); }   // fx.py:60 (kept out of line: pow is long)
 
 // Register-file sizes per variant (the host picks the smallest variant a program fits).  SMALL: two filter slots, three
@@ -159,7 +179,10 @@ template <bool SMALL> struct VpLimits {
 // column-major with T + 1 floats per column (the guard entry [T] = [0], sig_table.h), table 1 behind table 0
 // SHP: the Shape instruction on top of TAB, a variant of its own once more: with the handler in the one TAB variant the SMALL
 // table kernels went from 260-312 to 412-472 B of scratch per lane, which wavetable-only programs would have paid
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, typename TABLES>
+// RES: the FilterQ instruction (resonant low-pass / high-pass, ext.py ResonantFilter): slots of type SIG_FILT_RES_* whose design reads
+// a second block-rate control, q, from the parameter rows the word names; a variant of its own (never with BAND, PM or TAB), so that
+// programs without the word keep their registers and scratch.  Filter words run in it too
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, typename TABLES>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
                                         [[maybe_unused]] const float* tab)
 {
@@ -204,7 +227,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     for (int f = 0; f < NF; ++f) {
         const bool band = f < a.n_filters && (a.ftype[f] == SIG_FILT_BANDPASS || a.ftype[f] == SIG_FILT_BANDSTOP);
         bfirst[f] = BAND && band && f + 1 < NF && !(f > 0 && bfirst[f > 0 ? f - 1 : 0]);
-        s2[f] = (f < a.n_filters && a.ftype[f] == SIG_FILT_HIGHPASS) ? -2.0 : 2.0;
+        s2[f] = (f < a.n_filters && (a.ftype[f] == SIG_FILT_HIGHPASS || (RES && a.ftype[f] == SIG_FILT_RES_HIGHPASS))) ? -2.0 : 2.0;
 #pragma unroll
         for (int i = 0; i < VPT; ++i) { z0[f][i] = z1[f][i] = w0[f][i] = w1[f][i] = 0.0; na1[f][i] = na2[f][i] = fb0[f][i] = xa1[f][i] = xa2[f][i] = 0.0; }
     }
@@ -220,6 +243,21 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
         for (int r = 0; r < RG; ++r) acc[r][i] = 0.0;
 #pragma unroll
         for (int ch = 0; ch < CC; ++ch) wt[ch][i] = BUS ? ((v0 + i < a.voices) ? (a.pan ? a.pan[ch * a.pan_ld + voice(i)] : 1.0) : 0.0) : 1.0;
+    }
+
+    // RES: the parameter slot that holds filter slot f's q rows (-1: a Butterworth slot, or q unplugged), from the FilterQ words
+    [[maybe_unused]] int qreg[NF];
+    if constexpr (RES) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) qreg[f] = -1;
+        for (int k = 0; k < a.n_ins; ++k) {
+            const uint32_t w = a.code[k];                                      // (wave-uniform: the argument block)
+            if ((w & 31u) != (uint32_t)SIG_VP_FILTERQ) continue;
+            const int slot = (int)((w >> 8) & 15u), reg = (int)((w >> 16) & 15u);
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+                if (f == slot) qreg[f] = (reg < a.n_params) ? reg : -1;        // (15: unplugged)
+        }
     }
 
     // ---- per-block state: parameter registers, oscillator rows, filter designs
@@ -269,7 +307,34 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                 }
                 if (!ok && a.status) atomicOr(a.status, SIG_STATUS_BAD_CUTOFF);
             }
-            const bool single = f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
+            if constexpr (RES) {                                               // every slot of this variant: vp_design_res, a Butterworth slot at d = sqrt2
+                const bool resonant = f < a.n_filters && (a.ftype[f] == SIG_FILT_RES_LOWPASS || a.ftype[f] == SIG_FILT_RES_HIGHPASS);
+                const bool plain = f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
+                const bool swept_q = resonant && qreg[f] >= 0 && a.params[qreg[f] >= 0 ? qreg[f] : 0].rows > 1;
+                if ((resonant || plain) && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1 || swept_q)) {
+                    const bool lowpass = a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_RES_LOWPASS;
+                    int bad = 0;
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        double d = sig_biquad::kSqrt2;
+                        bool q_ok = true;
+                        if (resonant && qreg[f] >= 0) {
+                            const double r = row_at(a.params[qreg[f]], cri, voice(i));
+                            q_ok = r > 0.0 && r < __builtin_inf();             // 0, negative, NaN, +-inf: refused
+                            d = 1.0 / r;
+                        }
+                        Biquad q;
+                        const int got = vp_design_res(lowpass, row_at(a.cutoff[f], cri, voice(i)), d, q_ok, a.rate, q);
+                        bad |= (v0 + i < a.voices) ? got : 0;                  // a dead (padding) lane never reports
+                        if (NEXT) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
+                        else { na1[f][i] = -q.a1; na2[f][i] = -q.a2; fb0[f][i] = q.b0; }
+                        if (!NEXT && !designed) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
+                    }
+                    if (bad && a.status) atomicOr(a.status, bad);
+                }
+            }
+            const bool single = !RES && f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
             if (single && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1)) {
                 bool ok = true;
 #pragma unroll
@@ -473,6 +538,15 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                       ic = (int)((w >> 16) & 15u);
             // OscTable is dispatched in front of the switch, and only in the TAB variant: a case of its own, even an empty one, changes
             // the code of every other instantiation (the compare chain of the dispatch), and those are to stay what they were
+            if constexpr (RES) {                                               // FilterQ: the Filter handler on a resonant slot, in front of the switch like OscTable
+                if (op == SIG_VP_FILTERQ) {
+                    with_index<NF>(ia, [&](auto I) {
+                        constexpr int F = decltype(I)::value;
+                        section(I, warm_r, rows_tag, [&](int) { return s2[F]; }, [&](int) { return s2[F]; }, true);
+                    });
+                    continue;
+                }
+            }
             if constexpr (TAB) {
                 // the column of table slot ib that parameter slot ic selects, per voice: its first float in `tab`
                 auto columns = [&](int (&col)[VPT], int& TT) {
@@ -817,7 +891,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, typename TABLES>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, typename TABLES>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
 {
     constexpr bool BUS = C > 0;
@@ -837,7 +911,7 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
+    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -867,11 +941,17 @@ void sig_vp_specialised(VpArgs a)
 {
     constexpr bool kBand = vp_static_has(SIG_VP_BAND), kPm = vp_static_has(SIG_VP_OSCPM), kShape = vp_static_has(SIG_VP_SHAPE);
     constexpr bool kTab = vp_static_has(SIG_VP_OSCTABLE) || kShape;
+    constexpr bool kRes = vp_static_has(SIG_VP_FILTERQ);
+#ifndef SIG_VP_S_RES
+#define SIG_VP_S_RES 0                     // 1: the program has a FilterQ word (the resonant design)
+#endif
+    static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
+    static_assert(!(kRes && (kTab || kBand || kPm)), "FilterQ with Band, OscPM, OscTable or Shape: no variant has both");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
 #if SIG_VP_S_TAB
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape>(a, tb);
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false>(a, tb);
 #else
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false>(a, VpNoTables{});
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes>(a, VpNoTables{});
 #endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
@@ -885,19 +965,25 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false>(a, VpNoTables{});
 }
 // the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, false>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false>(a, tb);
 }
 // the TAB variant with the Shape instruction (programs with a waveshaper, with or without a wavetable oscillator)
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_shape_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, true>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false>(a, tb);
+}
+// the RES variant (never with BAND, PM or TAB): programs with a resonant filter, whose design reads q
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_res_kernel(VpArgs a)
+{
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true>(a, VpNoTables{});
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -913,8 +999,8 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) && x.c == -1) ? 15 : x.c;       // (no select: a slot number no register file has)
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_SHAPE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
+        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ) && x.c == -1) ? 15 : x.c;       // (no select / no q: a slot number no register file has)
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTERQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
     }
@@ -931,7 +1017,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -993,9 +1079,21 @@ int vp_launch_shape_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nw
     return sig_launch_status();
 }
 
+template <int VPT, bool SMALL>
+int vp_launch_res_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_res_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a); break;
+        case 1: voice_program_res_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a); break;
+        case 2: voice_program_res_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
 template <int VPT>
 int vp_launch_file(const VpArgs& a, const VpTables& tb, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    // (a table never with a band or a PM carrier, a PM carrier never with a band: refused)
+    // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter with none of them: refused)
+    if (n.res) return small_file ? vp_launch_res_sink<VPT, true>(a, C, nwg, s) : vp_launch_res_sink<VPT, false>(a, C, nwg, s);
     if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
     if (n.table) return small_file ? vp_launch_table_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_table_sink<VPT, false>(a, tb, C, nwg, lds, s);
     if (n.pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);
@@ -1114,7 +1212,7 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false};
     // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
     const int n_tables = tables ? tables->n_tables : 0;
     SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
@@ -1130,8 +1228,8 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_SHAPE && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
-                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) ? -1 : 0) && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTERQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ) ? -1 : 0) && x.c <= 15);
         switch (x.op) {
             case SIG_VP_OSCTABLE:
                 SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
@@ -1141,6 +1239,7 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
             case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
+            case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
             case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
             case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
@@ -1154,7 +1253,9 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (x.op == SIG_VP_OSCPM) need.pm = true;
         if (x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) need.table = true;
         if (x.op == SIG_VP_SHAPE) need.shape = true;
+        if (x.op == SIG_VP_FILTERQ) need.res = true;
     }
+    SIG_CHECK_ARG(!(need.res && (need.band || need.pm || need.table)));
     SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no interpreter variant with two of them; the engine keeps such a graph per node)
     VpTables tb{};
     for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
@@ -1172,12 +1273,15 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     }
     // filter slots: a Filter instruction runs a LowPass / HighPass slot; a Band instruction at slot f runs the pair f, f + 1 (its
     // low and high rows), of one band type and one level, which the kernel finds by pairing every run of band slots from its start
-    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second
+    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second, 4: resonant (one FilterQ word)
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
         if (x.op == SIG_VP_FILTER) {
             SIG_CHECK_ARG(role[x.a] == 0 || role[x.a] == 1);
             role[x.a] = 1;
+        } else if (x.op == SIG_VP_FILTERQ) {
+            SIG_CHECK_ARG(role[x.a] == 0);
+            role[x.a] = 4;
         } else if (x.op == SIG_VP_BAND) {
             SIG_CHECK_ARG((role[x.a] == 0 || role[x.a] == 2) && (role[x.a + 1] == 0 || role[x.a + 1] == 3));
             role[x.a] = 2; role[x.a + 1] = 3;
@@ -1190,9 +1294,11 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         else if (role[k] == 2) SIG_CHECK_ARG(band && run % 2 == 1 && P.filter_type[k + 1] == P.filter_type[k] &&
                                              P.filter_level[k + 1] == P.filter_level[k]);
         else if (role[k] == 3) SIG_CHECK_ARG(band && run % 2 == 0);
+        const bool resonant = P.filter_type[k] == SIG_FILT_RES_LOWPASS || P.filter_type[k] == SIG_FILT_RES_HIGHPASS;
+        SIG_CHECK_ARG(resonant == (role[k] == 4));                             // a resonant slot and its FilterQ word go together
     }
     for (int k = 0; k < P.n_filters; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_BANDSTOP);
+        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_RES_HIGHPASS);
         a.cutoff[k] = Rows{P.cutoff[k].ptr, P.cutoff[k].col_stride, P.cutoff[k].rows};
         a.ftype[k] = P.filter_type[k];
         SIG_CHECK_ARG(P.filter_level[k] >= 1 && P.filter_level[k] <= P.depth);

@@ -389,6 +389,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.right]
     if isinstance(node, fx.Mix):
         return [node.mix]
+    if isinstance(node, ext.ResonantFilter):
+        return [node.cutoff, node.resonance]
     if isinstance(node, fx.SingleCritFilter):
         return [node.cutoff]
     if isinstance(node, fx.DoubleCritFilter):
@@ -558,6 +560,9 @@ class _ControlProgram:
             got = self._push(_native.CtlIns(_native.CTL_OPS[type(src).__name__], 0, a, b, c, 0, 0, 0, cols, int(window), None), cols)
         elif isinstance(src, noise.White):
             got = self._push(self._noise(src, window), self._request_width(src))
+        elif isinstance(src, ext.ResonantFilter):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a resonant filter has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
         elif window and isinstance(src, fx.CritFilter):
             raise NotBatchable('a filter whose input contains a filter, in a control path')
         elif isinstance(src, fx.SingleCritFilter):
@@ -746,6 +751,9 @@ class _Batch:
                                f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.Shaper):
             raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a waveshaper has no block-rate schedule '
+                               f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.ResonantFilter):
+            raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a resonant filter has no block-rate schedule '
                                f'(the eager node serves one-frame requests)')
         else:
             raise NotBatchable(f'{what}: no block-rate schedule for {src.cls_name()}')
@@ -1286,6 +1294,19 @@ class _Batch:
                           lambda: _native.band_coldstart_blocks(btype, self.rate, pos, N, K, CONTEXT, cutoff, high, window, c0,
                                                                 main, status=status),
                           units=N * K * channels)
+        elif isinstance(node, ext.ResonantFilter):
+            # the resonant low-pass / high-pass: a second control row, each of the two per block on its own (a swept cutoff, a swept q)
+            q = None if _ctl_unplugged(node.resonance) else self._control(node.resonance, 'resonance')
+            if q is not None:
+                if q.shape[1] < channels:
+                    raise IndexError(f'index {q.shape[1]} is out of bounds for axis 1 with size {q.shape[1]}')
+                q = q[:, :channels]
+                if not q.is_contiguous():
+                    q = q.contiguous()
+            swept = cutoff.shape[0] > 1 or (q is not None and q.shape[0] > 1)
+            o._launch(f'biquad_coldstart_q[{btype}{",blocks" if swept else ""}]',
+                      lambda: _native.biquad_coldstart_q(btype, self.rate, pos, N, K, CONTEXT, cutoff, q, window, c0, main, status=status),
+                      units=N * K * channels)
         else:
             o._launch(f'biquad_coldstart[{btype}{",env" if envelope else ""}]',
                       lambda: _native.biquad_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, window, c0, main,
@@ -1838,7 +1859,8 @@ class _ProgramRows:
 
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
-    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), waveshapers (ext.Shaper), in any arrangement in which every voice is computed from its own
+    Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), waveshapers (ext.Shaper),
+    resonant low-pass / high-pass filters (ext.ResonantFilter), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
@@ -1846,7 +1868,7 @@ class _VoiceProgram:
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
     KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
-                    ext.PMOsc, ext.Wavetable, ext.Shaper)
+                    ext.PMOsc, ext.Wavetable, ext.Shaper, ext.ResonantFilter)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
@@ -1855,6 +1877,7 @@ class _VoiceProgram:
         self.params: list = []                   # control index per parameter register
         self.filters: list = []                  # (cutoff control index, type, level, node); a band filter: two slots, low then high
         self.bands: list = []                    # the band filter nodes
+        self.resonant: list = []                 # (resonant filter node, the parameter register of its q rows | -1)
         self.controls: list = []                 # (port | None, constant tensor | None, filters between the node and the sink)
         self.adsr = None
         self.seeds: list = []
@@ -1875,6 +1898,12 @@ class _VoiceProgram:
             raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
         if self.tables and (self.bands or any(op == 'OscPM' for op, *_ in self.code)):
             raise _NoProgram('a wavetable oscillator or a waveshaper with a band filter or a phase-modulation oscillator: no interpreter variant has both')
+        if self.resonant and self.bands:
+            raise _NoProgram('a resonant filter and a band filter: no interpreter variant has both')
+        if self.resonant and any(op == 'OscPM' for op, *_ in self.code):
+            raise _NoProgram('a resonant filter and a phase-modulation oscillator: no interpreter variant has both')
+        if self.resonant and self.tables:
+            raise _NoProgram('a resonant filter and a wavetable oscillator or a waveshaper: no interpreter variant has both')
 
     # ---- pass 1: readers of every node inside the graph
     def _count(self, n):
@@ -2023,8 +2052,16 @@ class _VoiceProgram:
             edges = (n.low, n.high) if band else (n.cutoff,)
             if len(self.filters) + len(edges) > _native.VP_MAX_FILTERS:
                 raise _NoProgram('more filters than the machine has slots')
-            self.filters += [(self._control(p, below), str(n.type()), depth, n) for p in edges]
-            self.code.append(('Band' if band else 'Filter', 0, len(self.filters) - len(edges), 0, 0))
+            if isinstance(n, ext.ResonantFilter):
+                # one slot like LowPass / HighPass, of a type of its own; q in a parameter register the FilterQ word names (read per
+                # block with the cutoff, where the slot is designed), -1: unplugged = 1/sqrt2
+                self.filters.append((self._control(n.cutoff, below), 'r' + str(n.type()), depth, n))
+                q = -1 if _ctl_unplugged(n.resonance) else self._param(self._control(n.resonance, below))
+                self.code.append(('FilterQ', 0, len(self.filters) - 1, 0, q))
+                self.resonant.append((n, q))
+            else:
+                self.filters += [(self._control(p, below), str(n.type()), depth, n) for p in edges]
+                self.code.append(('Band' if band else 'Filter', 0, len(self.filters) - len(edges), 0, 0))
             if band:
                 self.bands.append(n)
         else:
@@ -2100,6 +2137,10 @@ class _VoiceProgram:
         for cut, _, _, _ in self.filters:
             if tensors[cut].shape[1] != v and v != 1:
                 raise IndexError(f'index {tensors[cut].shape[1]} is out of bounds for axis 1 with size {tensors[cut].shape[1]}')   # fx.py:99
+        for _, q in self.resonant:
+            if q >= 0 and tensors[self.params[q]].shape[1] != v and v != 1:
+                width = tensors[self.params[q]].shape[1]
+                raise IndexError(f'index {width} is out of bounds for axis 1 with size {width}')
         adsr = None
         if self.adsr is not None:
             adsr = b._envelope_rows(self.adsr)
@@ -2165,7 +2206,9 @@ class _VoiceProgram:
         Wavetable oscillators (OscTable) take the program under the same rule: 0.76 T interpreted against 0.32 T per node under a bus,
         0.55 against 0.21 T behind a LowPass (tools/time_wavetable.py).
         Waveshapers (Shape) likewise: 0.56 T interpreted against 0.22 T per node under a bus, 0.43 against 0.16 T with a LowPass in
-        front of the shaper (tools/time_shaper.py)."""
+        front of the shaper (tools/time_shaper.py).
+        Resonant filters (FilterQ) take the program under the same rule; the q rows cost one parameter register each
+        (tools/time_resonant.py)."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))

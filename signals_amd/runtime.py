@@ -51,10 +51,12 @@ class StatusWord:
 
 def check_status() -> None:
     """Raise what the reference would have raised inside the block (scipy's ValueError for a
-    critical frequency outside (0, 1), fx.py:99-121).  Costs one device sync per live status word:
+    critical frequency outside (0, 1), fx.py:99-121; for a resonant filter's q that is not finite and > 0 the build's own).  Costs one device sync per live status word:
     call at the sink edge, not per node."""
-    from signals_amd._native import STATUS_BAD_CUTOFF
+    from signals_amd._native import STATUS_BAD_CUTOFF, STATUS_BAD_RESONANCE
     for word in list(_status_words):
         bits = word.poll()
         if bits & STATUS_BAD_CUTOFF:
             raise ValueError(f'{word.owner_name}: Digital filter critical frequencies must be 0 < Wn < 1')
+        if bits & STATUS_BAD_RESONANCE:                   # (build-defined: chain/ext.py ResonantFilter)
+            raise ValueError(f'{word.owner_name}: filter resonance must be finite and > 0')

@@ -52,11 +52,12 @@ def flags(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, 
     slots it uses, voices per lane, sink, and the waves per SIMD the interpreter's small build asks for"""
     words = ','.join(f'0x{w:x}' for w in _native.voice_program_words(code))
     ext = int(any(op in _native.VP_EXT_OPS for op, *_ in code))                  # Amp, Adsr, Noise: the extended handlers
-    table = ['-DSIG_VP_S_TAB=1'] if any(op in _native.VP_TABLE_OPS for op, *_ in code) else []   # (the tables: a second kernel parameter)
+    more = ['-DSIG_VP_S_TAB=1'] if any(op in _native.VP_TABLE_OPS for op, *_ in code) else []   # (the tables: a second kernel parameter)
+    more += ['-DSIG_VP_S_RES=1'] if any(op in _native.VP_RES_OPS for op, *_ in code) else []    # (FilterQ: the resonant design)
     return [f'-DSIG_VP_STATIC_CODE={{{words}}}', f'-DSIG_VP_S_NF={max(n_filters, 1)}', f'-DSIG_VP_S_NO={max(n_oscs, 1)}',
             f'-DSIG_VP_S_NP={max(n_params, 1)}', f'-DSIG_VP_S_NT={n_temps}', f'-DSIG_VP_S_EXT={ext}',
             f'-DSIG_VP_STATIC_VPT={voices_per_lane}', f'-DSIG_VP_STATIC_C={bus_channels}',
-            f'-DSIG_VP_STATIC_WAVES={ {1: 3, 2: 2, 4: 1}[voices_per_lane] }'] + table
+            f'-DSIG_VP_STATIC_WAVES={ {1: 3, 2: 2, 4: 1}[voices_per_lane] }'] + more
 
 
 def _compile(source: str, defs: list, prefix: str) -> bytes:
