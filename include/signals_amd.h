@@ -106,6 +106,28 @@ int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, in
                        const float* table, int32_t table_points, int32_t table_waves,
                        void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Unison oscillator, chain/ext.py UnisonSine / UnisonSquare / UnisonSawtooth / UnisonTriangle: `copies` detuned copies of one waveform
+ * per voice, summed and divided by their number (the supersaw, detuned square leads, thickened sines).  For row n and voice v, in
+ * f64, every operation rounded, u = 0 .. copies - 1 ascending:
+ *   r_u = 1.0 + spread[v] * detune[u];   h_u = hertz[v] * r_u;   q_u = phase[v] + offsets[u]
+ *   t_u = (position + n * position_step) / rate * h_u + q_u
+ *   out[n,v] = (((w(t_0) + w(t_1)) + w(t_2)) + ...) / copies               w = wave_kind, sig_osc_bank's two-instruction forms
+ * hertz / phase / spread rows like sig_osc_bank_mod (per block with rows_per_param); phase or spread NULL = unplugged = 0.
+ * `detune` and `offsets` are HOST arrays of `copies` doubles, 1 <= copies <= SIG_UNISON_MAX_COPIES, copied into the kernel's
+ * argument block (wave-uniform values).  Position-pure.  Square / Sawtooth / Triangle: the float64 value in front of the store is
+ * bit-exact against numpy; Sine: the f64 store sums the f64 polynomial, the f32 store sums the hardware sine of sig_osc_bank's f32
+ * store per copy in f64 (within 1.3e-7 per copy, so is the mean).  copies == 1 with detune[0] == offsets[0] == 0: sig_osc_bank's
+ * bits in both stores.  A null hertz / out / detune / offsets, copies out of range, out_ld < voices or a stride other than 0 / 1:
+ * hipErrorInvalidValue, nothing launched; rows == 0: no launch. */
+enum { SIG_UNISON_MAX_COPIES = 16 };
+int sig_osc_bank_unison(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                        int32_t voices, int32_t rows_per_param,
+                        const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                        const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                        const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+                        int32_t copies, const double* detune, const double* offsets,
+                        void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Table-lookup waveshaper, chain/ext.py Shaper (build-defined: the reference has no memoryless non-linearity but Amp).  `table`
  * float32 (T, W) row-major in device memory: W transfer curves of T points each, spanning input -1 .. +1; T >= 2 (any integer: 2^k + 1
  * points put a knot at x = 0), W >= 1, T * W <= SIG_TABLE_MAX_POINTS.  For every row n and voice v, in f64, every operation rounded:
@@ -597,6 +619,11 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *          with the cutoff (the rows of the block the design is for), c == -1: unplugged = 1/sqrt2.  One FILTERQ word per slot;
  *          FILTER words run in the same program (ResonantHighPass -> LowPass is one program).  Refused together with BAND, OSCPM,
  *          OSCTABLE or SHAPE, hipErrorInvalidValue: the interpreter variant with the resonant design has none of them
+ *   OSCUNI acc = unison oscillator (sig_osc_bank_unison's expression with the fused waveforms: m = t - floor(t) as one v_fract_f64,
+ *          the f64 sine) of kind `kind` on oscillator slot a, over the copies of unison slot b of the `unison` argument of
+ *          sig_voice_program_unison (only slot 0 exists, SIG_VP_MAX_UNISON = 1), spread = params[c], c == -1: unplugged = 0.  The
+ *          copies travel by value in the launch.  Refused together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ,
+ *          hipErrorInvalidValue: the interpreter variant with the unison handler has none of them; so is one launched without `unison`
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -619,10 +646,10 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * > 0 likewise and sets SIG_STATUS_BAD_RESONANCE (never for a voice past `voices`). */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
-       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15 };
-enum { SIG_VP_MAX_TABLES = 2 };
+       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16 };
+enum { SIG_VP_MAX_TABLES = 2, SIG_VP_MAX_UNISON = 1 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ: c may be -1 */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI: c may be -1 */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];
@@ -650,6 +677,18 @@ int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64
                          const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                          double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                          const sig_vp_tables_t* tables);
+/* sig_voice_program_ex with the copies of its OSCUNI instructions: `unison` (HOST memory, copied into the launch as a kernel
+ * parameter of its own): 1 <= copies <= SIG_UNISON_MAX_COPIES rows (detune[u], offset[u]).  NULL for a program without the
+ * instruction: sig_voice_program_ex is this call with NULL.  Refused before any device work, hipErrorInvalidValue: copies out of
+ * range, NULL with an OSCUNI word in the program, an OSCUNI word with b != 0, a >= n_oscs, c >= n_params or a kind above
+ * SIG_OSC_TRIANGLE, and OSCUNI together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ. */
+typedef struct { int32_t copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; } sig_vp_unison_t;
+int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                             int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                             int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                             const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                             double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                             const sig_vp_tables_t* tables, const sig_vp_unison_t* unison);
 /* Tuning / test hook: force the voices per lane (1, 2; 0 = heuristic; ignored where the program does not fit the variant) and
  * the blocks per lane (0 = heuristic) of sig_voice_program.  Process-wide. */
 int sig_voice_program_set_tuning(int32_t voices_per_lane, int32_t blocks_per_lane);

@@ -50,12 +50,15 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15, 'OscUni': 16}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 VP_MAX_TABLES = 2
 VP_TABLE_OPS = ('OscTable', 'Shape')        # the instructions of the table variant (SIG_VP_S_TAB): table slot b, select = parameter slot c | -1
 VP_RES_OPS = ('FilterQ',)                   # the instruction of the resonant variant (SIG_VP_S_RES): filter slot a, q = parameter slot c | -1
+VP_UNI_OPS = ('OscUni',)                    # the instruction of the unison variant (SIG_VP_S_UNI): oscillator slot a, unison slot b = 0, spread = parameter slot c | -1
+VP_MAX_UNISON = 1                           # SIG_VP_MAX_UNISON: unison slots of a voice program (one `copies` array per launch)
+UNISON_MAX_COPIES = 16                      # SIG_UNISON_MAX_COPIES: copies of a unison oscillator (ext.py UnisonOsc)
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
 
 
@@ -87,6 +90,11 @@ class VpTablesT(ctypes.Structure):
     _fields_ = [('n_tables', ctypes.c_int32), ('table', VpTable * VP_MAX_TABLES)]
 
 
+class VpUnisonT(ctypes.Structure):
+    """sig_vp_unison_t (host memory): the copies of a program's OscUni words, by value"""
+    _fields_ = [('copies', ctypes.c_int32), ('detune', ctypes.c_double * UNISON_MAX_COPIES), ('offset', ctypes.c_double * UNISON_MAX_COPIES)]
+
+
 class Operand(ctypes.Structure):
     _fields_ = [('ptr', ctypes.c_void_p), ('row_stride', ctypes.c_int64),
                 ('col_stride', ctypes.c_int32), ('dtype', ctypes.c_int32),
@@ -113,6 +121,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_pm': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
                             vp, i32, i64, i32, vp, i32, i64, vp],
         'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
+        'sig_osc_bank_unison': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
@@ -157,6 +166,8 @@ def _argtypes() -> dict:
         'sig_voice_program': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out,
         'sig_voice_program_ex': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out
                                 + [ctypes.POINTER(VpTablesT)],
+        'sig_voice_program_unison': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out
+                                    + [ctypes.POINTER(VpTablesT), ctypes.POINTER(VpUnisonT)],
         'sig_voice_program_set_tuning': [i32, i32],
         'sig_voice_program_geometry': [i32, i32, i32, i32, i32, i32, i32, i32, p32, p32],
         'sig_voice_program_args_size': [],
@@ -389,6 +400,33 @@ def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.T
     _check(lib().sig_osc_bank_table(position, step, rate, rows, voices, rows_per_param,
                                     *params[0:3], *params[4:7], *params[8:11], *_table(table),
                                     out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_table')
+    return out
+
+
+def _copies(copies) -> tuple:
+    """(U, detune, offsets) of a unison oscillator's (U, 2) `copies` array: two host arrays of U doubles the launch takes by value"""
+    import numpy as np
+    c = np.asarray(copies, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= UNISON_MAX_COPIES or not np.isfinite(c).all():
+        raise NativeError(f'unison copies must be a finite (1..{UNISON_MAX_COPIES}, 2) array of (detune, phase offset) rows, got shape {c.shape}')
+    U = c.shape[0]
+    return U, (ctypes.c_double * U)(*c[:, 0].tolist()), (ctypes.c_double * U)(*c[:, 1].tolist())
+
+
+def osc_bank_unison(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, spread: torch.Tensor | None,
+                    copies, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- unison oscillator `kind` (sig_osc_bank_unison): the mean over the U rows (d, p) of `copies` (a host
+    (U, 2) array, by value) of wave(n / rate * (hertz * (1 + spread * d)) + (phase + p)).  hertz / phase / spread: (1|P, V|1) f64 like
+    `osc_bank`; spread None: unplugged = 0."""
+    _gpu(hertz, phase, spread, out)
+    _audio(out, 'osc out')
+    rows, voices = out.shape
+    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'), form=_ctrl_rows)
+    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'spread'))
+    U, detune, offsets = _copies(copies)
+    _check(lib().sig_osc_bank_unison(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
+                                     *params[0:3], *params[4:7], *params[8:11], U, detune, offsets,
+                                     out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_unison')
     return out
 
 
@@ -1034,8 +1072,9 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   block_frames: int, nblocks: int, context: int, voices: int, control_rows: int, hist_positions: list,
                   out: torch.Tensor, bus_gains: torch.Tensor | None = None, bus: bool = False,
                   adsr: dict | None = None, noise_seeds: tuple = (0, 0), workspace: torch.Tensor | None = None,
-                  status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None) -> torch.Tensor:
-    """One launch for a whole per-voice graph (sig_voice_program_ex; `tables`: the float32 (T, W) tables of its OscTable and Shape words).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
+                  status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None,
+                  unison=None) -> torch.Tensor:
+    """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
     'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
@@ -1082,16 +1121,24 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
         wrapped = {b for op, _, _, b, _ in code if op == 'OscTable'}            # slots an oscillator reads: powers of two
         for k, t in enumerate(tables):
             held.table[k] = VpTable(*_table(t, pow2=k in wrapped))
-    _check(lib().sig_voice_program_ex(ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows,
-                                      len(hist_positions), hist, blocks_before, gp, gld, C,
-                                      _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out),
-                                      ctypes.byref(held) if held is not None else None), 'sig_voice_program_ex')
+    uni = None
+    if unison is not None:
+        uni = VpUnisonT()
+        uni.copies, detune, offsets = _copies(unison)
+        uni.detune[:uni.copies], uni.offset[:uni.copies] = list(detune), list(offsets)
+    args = (ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows, len(hist_positions), hist,
+            blocks_before, gp, gld, C, _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out),
+            ctypes.byref(held) if held is not None else None)
+    if uni is None:                                       # (a program without the copies: the entry it always went through)
+        _check(lib().sig_voice_program_ex(*args), 'sig_voice_program_ex')
+    else:
+        _check(lib().sig_voice_program_unison(*args, ctypes.byref(uni)), 'sig_voice_program_unison')
     return out
 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's and FilterQ's c = -1: 15)
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's, FilterQ's and OscUni's c = -1: 15)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

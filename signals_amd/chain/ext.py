@@ -220,6 +220,106 @@ class Wavetable(BlockCachingEmitter, ImplicitChannels):
         return _native.osc_bank_table(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
 
 
+UNISON_DETUNE = (-0.11002313, -0.06288439, -0.01952356, 0.0, 0.01991221, 0.06216538, 0.10745242)
+
+
+def _default_copies() -> np.ndarray:
+    """seven copies at the uneven JP-8000 spacing (they never realign periodically), phase offsets a golden-ratio apart"""
+    return np.stack([np.array(UNISON_DETUNE), np.mod(np.arange(7) * 0.6180339887498949, 1.0)], axis=1)
+
+
+def _validate_copies(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and new_value.shape[1] == 2 and 1 <= new_value.shape[0] <= _native.UNISON_MAX_COPIES
+          and bool(np.isfinite(new_value).all()))
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a 2D real array (copies, 2) of finite (detune, phase offset) rows, 1 <= copies <= '
+                            f'{_native.UNISON_MAX_COPIES}')
+
+
+class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
+    """Unison oscillator: U detuned copies of one waveform of chain/osc.py per voice, summed and divided by U -- the supersaw, detuned
+    square leads, thickened sines.  The state `copies` is a (U, 2) array, 1 <= U <= 16: column 0 the relative detune d[u] of copy u,
+    column 1 its phase offset p[u] in cycles.  Ports, all block-rate: hertz, phase, spread (dimensionless; unplugged means zeros,
+    like every port: every copy then runs at `hertz`).  For row n and voice v, in float64 and every operation rounded:
+        r_u = 1.0 + spread[v] * d[u]
+        h_u = hertz[v] * r_u
+        q_u = phase[v] + p[u]
+        t_u = frame_range / rate * h_u + q_u                               (osc.py's order: frame / rate, times h_u, plus q_u)
+        s   = ((w(t_0) + w(t_1)) + w(t_2)) + ...                           (u ascending, w = osc.py's waveform of the kind)
+        out = s / U
+    (kernel: sig_osc_bank_unison; restated in numpy by tests/unison_reference.py).  With copies = [[0, 0]] this is `osc.Osc` bit for
+    bit.  The default is seven copies at the uneven JP-8000 spacing with golden-ratio phase offsets.  Integer arrays (what a .sigs
+    value arrives as) are converted; the copies travel by value with each launch, so an in-place edit of the array or a replaced
+    array takes effect at the next render.  Position-pure: no carried phase, no table.  Not an `osc.Osc`: that means a closed-form
+    leaf with two control ports to the engine's fused kernels.
+    Out of scope: a frame-rate `spread`; per-voice private `copies`; stereo spread of the copies (`SumBus` gains pan whole voices);
+    a phase-modulated or wavetable unison; the node inside a block-rate control path (the batched engine answers NotBatchable with
+    the reason and the graph keeps the eager path, which serves frames == 1 in float64); a combination with a band filter, a
+    phase-modulation oscillator, a wavetable oscillator, a waveshaper or a resonant filter in one voice program (such a graph stays
+    one kernel per node); the closed-form, row-walker and cascade fused kernels; band-limiting -- the copies alias like
+    `osc.Sawtooth` does."""
+    hertz: Receiver.BoundPort = port('hertz')
+    phase: Receiver.BoundPort = port('phase')
+    spread: Receiver.BoundPort = port('spread')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        copies: np.ndarray = attr.ib(factory=_default_copies, validator=_validate_copies, on_setattr=attr.setters.validate)
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR
+
+    @classmethod
+    @abc.abstractmethod
+    def kind(cls) -> str:
+        """kernel selector: 'Sine' | 'Square' | 'Sawtooth' | 'Triangle'"""
+        raise NotImplementedError
+
+    def host_copies(self) -> np.ndarray:
+        """the (U, 2) float64 array a launch takes by value, as the state holds it now"""
+        return np.ascontiguousarray(self._state.copies, dtype=np.float64)
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        phase = as_control(self.phase.forward_at_block_rate(request))
+        hertz = as_control(self.hertz.forward_at_block_rate(request))
+        spread = as_control(self.spread.forward_at_block_rate(request))        # unplugged: zeros((1, 1)), every copy at `hertz`
+        loc = request.loc
+        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, spread.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
+        return _native.osc_bank_unison(self.kind(), loc.position, loc.rate, hertz, phase, spread, self.host_copies(), out)
+
+
+class UnisonSine(UnisonOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sine'
+
+
+class UnisonSquare(UnisonOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Square'
+
+
+class UnisonSawtooth(UnisonOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sawtooth'
+
+
+class UnisonTriangle(UnisonOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Triangle'
+
+
 def _validate_curves(instance, attribute, new_value):
     ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
           and new_value.shape[0] >= 2 and new_value.shape[1] >= 1

@@ -346,7 +346,145 @@ int launch_table(const OscArgs& a, TableArgs tb, OUT* out, int64_t ld, hipStream
     return sig_launch_status();
 }
 
+// ---- unison: the mean of `copies` detuned copies of one waveform per voice (chain/ext.py UnisonOsc),
+//   r_u = 1 + spread * d[u];  h_u = hertz * r_u;  q_u = phase + p[u];  t_u = n / rate * h_u + q_u;  out = (sum_u w(t_u)) / copies
+// every operation rounded in that order, the sum in u ascending.  Same mapping as osc_bank_kernel (a wave = 64 * VEC voices x 16
+// rows, n / rate once per row).  d[] and p[] sit in the argument block: the copy loop's trip count and both values are
+// wave-uniform, so they are scalar loads and SGPRs, and the per-sample work is copies x (6 f64 operations + the waveform) on
+// VEC voices' registers.  No table, no LDS, no carried state.
+// Roofline: 4 B written per voice-sample (f32) against ~12 copies f64 operations: f64-VALU-bound from a few copies on.
+struct UniArgs {
+    const double* spread; int ss; int64_t srs;                     // (1|P, V|1) f64 like hertz / phase; NULL: unplugged = 0
+    int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES];
+};
+
+// one copy's sample as the f64 summand: the f32 store of Sine sums sig_osc_bank's hardware sine (so that one copy keeps its bits)
+template <int KIND, typename OUT> __device__ __forceinline__ double unison_wave(double t) {
+    if (KIND == SIG_OSC_SINE && sizeof(OUT) == 4) return (double)sig_osc::osc_sine_f32(t);
+    return osc_wave<KIND, double>(t);
+}
+
+template <int KIND, int VEC, typename OUT>
+__global__ __launch_bounds__(256) void osc_bank_unison_kernel(OscArgs a, UniArgs un, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int vt = blockIdx.x % voice_tiles;
+    const int64_t rt = blockIdx.x / voice_tiles;
+    const int v0 = (vt * SIG_WAVE + lane) * VEC;
+    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    if (r0 >= a.rows) return;                                      // wave-uniform
+
+    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const int copies = un.copies;                                  // 1 .. SIG_UNISON_MAX_COPIES (checked by the entry)
+    const double count = (double)copies;
+
+    double hz[VEC], ph[VEC], sp[VEC];
+    int64_t loaded = -1;
+    for (int j = 0; j < kRowsPerWave; ++j) {
+        const int64_t row = r0 + j;
+        if (row >= a.rows) break;                                  // wave-uniform
+        const int64_t prow = a.rpp ? row / a.rpp : 0;              // wave-uniform
+        if (prow != loaded) {
+            loaded = prow;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const int v = v0 + i;
+                hz[i] = (v < a.voices) ? a.hertz[prow * a.hrs + (int64_t)v * a.hs] : 0.0;
+                ph[i] = (v < a.voices && a.phase) ? a.phase[prow * a.prs + (int64_t)v * a.ps] : 0.0;
+                sp[i] = (v < a.voices && un.spread) ? un.spread[prow * un.srs + (int64_t)v * un.ss] : 0.0;
+            }
+        }
+        const double q = sig_readlane_f64(q_lane, j);
+        double s[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) s[i] = 0.0;
+        for (int u = 0; u < copies; ++u) {                         // wave-uniform trip count
+            const double d = un.detune[u], p = un.offset[u];       // (scalar loads from the argument block)
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const double r = 1.0 + sp[i] * d;
+                const double h = hz[i] * r;
+                const double qu = ph[i] + p;
+                const double w = unison_wave<KIND, OUT>(q * h + qu);
+                s[i] = (u == 0) ? w : s[i] + w;
+            }
+        }
+        OUT y[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) y[i] = (OUT)(s[i] / count);
+        OUT* dst = out + row * ld + v0;
+        if (VEC == 4) {
+            if (v0 < a.voices) {                                   // voices % 4 == 0 on this path
+                typename sig_vec4<OUT>::type o;
+                o.x = y[0]; o.y = y[1]; o.z = y[2]; o.w = y[3];
+                *reinterpret_cast<typename sig_vec4<OUT>::type*>(dst) = o;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i)
+                if (v0 + i < a.voices) dst[i] = y[i];
+        }
+    }
+}
+
+template <int KIND, typename OUT>
+int launch_unison(const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
+{
+    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
+                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
+    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
+    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
+    const int span = SIG_WAVE * (vec4 ? 4 : 1);
+    const int voice_tiles = (a.voices + span - 1) / span;
+    const int64_t nwg = row_tiles * voice_tiles;
+    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    if (vec4)
+        osc_bank_unison_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
+    else
+        osc_bank_unison_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
+    return sig_launch_status();
+}
+
+template <typename OUT>
+int dispatch_unison_kind(int kind, const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
+{
+    switch (kind) {
+        case SIG_OSC_SINE: return launch_unison<SIG_OSC_SINE, OUT>(a, un, out, ld, stream);
+        case SIG_OSC_SQUARE: return launch_unison<SIG_OSC_SQUARE, OUT>(a, un, out, ld, stream);
+        case SIG_OSC_SAWTOOTH: return launch_unison<SIG_OSC_SAWTOOTH, OUT>(a, un, out, ld, stream);
+        case SIG_OSC_TRIANGLE: return launch_unison<SIG_OSC_TRIANGLE, OUT>(a, un, out, ld, stream);
+    }
+    return (int)hipErrorInvalidValue;
+}
+
 }  // namespace
+
+extern "C" int sig_osc_bank_unison(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                                   int32_t voices, int32_t rows_per_param,
+                                   const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                                   const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                                   const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+                                   int32_t copies, const double* detune, const double* offsets,
+                                   void* out, int32_t out_dtype, int64_t out_ld, void* stream)
+{
+    SIG_CHECK_ARG(kind >= SIG_OSC_SINE && kind <= SIG_OSC_TRIANGLE);
+    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
+    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
+                  (spread_stride == 0 || spread_stride == 1));
+    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && spread_row_stride >= 0);
+    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
+    if (rows == 0 || voices == 0) return 0;
+    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
+                    phase, phase_stride, phase_row_stride, rows_per_param};
+    UniArgs un{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
+    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_dtype == SIG_F32) return dispatch_unison_kind<float>(kind, a, un, static_cast<float*>(out), out_ld, s);
+    return dispatch_unison_kind<double>(kind, a, un, static_cast<double*>(out), out_ld, s);
+}
 
 extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
                                   int32_t voices, int32_t rows_per_param,

@@ -77,6 +77,10 @@ struct VpArgs {
 // variant has, so that the argument block -- and with it the code -- of every other instantiation is what it was without the op.
 struct VpTables { const float* ptr[SIG_VP_MAX_TABLES]; int T[SIG_VP_MAX_TABLES], W[SIG_VP_MAX_TABLES]; };
 struct VpNoTables {};
+// The copies of the OscUni instruction (unison oscillators, ext.py UnisonOsc): relative detune and phase offset per copy, by value.
+// Travels the way VpTables does -- a second kernel parameter that only the UNI variant has -- and for the same reason.  Wave-uniform:
+// the handler's loop count and both values are scalars.
+struct VpUnison { int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; };
 
 // f(integral_constant<int, i>) for a wave-uniform i < N: a scalar switch, so arrays indexed inside stay in registers
 template <int N, typename F>
@@ -182,7 +186,10 @@ template <bool SMALL> struct VpLimits {
 // RES: the FilterQ instruction (resonant low-pass / high-pass, ext.py ResonantFilter): slots of type SIG_FILT_RES_* whose design reads
 // a second block-rate control, q, from the parameter rows the word names; a variant of its own (never with BAND, PM or TAB), so that
 // programs without the word keep their registers and scratch.  Filter words run in it too
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, typename TABLES>
+// UNI: the OscUni instruction (unison oscillators, ext.py UnisonOsc): the mean of the copies of one waveform; a variant of its own once
+// more (never with BAND, PM, TAB or RES).  `tb` is then the variant's VpUnison: TABLES is whatever second kernel parameter the
+// variant has (VpTables, VpUnison) or VpNoTables
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, typename TABLES>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
                                         [[maybe_unused]] const float* tab)
 {
@@ -547,6 +554,58 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                     continue;
                 }
             }
+            if constexpr (UNI) {                                               // OscUni: in front of the switch like OscTable
+                if (op == SIG_VP_OSCUNI) {
+                    // sig_osc_bank_unison's expression with the fused waveforms: r = 1 + spread d, h = hertz r, q = phase + p per copy
+                    // (block-invariant, but 2 x copies x VPT registers: recomputed per group), t = n / rate * h + q, the sum in u
+                    // ascending, divided by the count.  The copy loop's trip count is wave-uniform (the argument block)
+                    double sp[VPT];
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) sp[i] = 0.0;                 // (15: spread unplugged)
+                    if (ic < NP) {
+                        with_index<NP>(ic, [&](auto I) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) sp[i] = pr[decltype(I)::value][i];
+                        });
+                    }
+                    const int copies = tb.copies;
+                    with_index<NO>(ia, [&](auto I) {
+                        constexpr int S = decltype(I)::value;
+                        for (int u = 0; u < copies; ++u) {
+                            const double d = tb.detune[u], p = tb.offset[u];
+                            double h[VPT], qu[VPT];
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) {
+                                h[i] = ohz[S][i] * (1.0 + sp[i] * d);
+                                qu[i] = oph[S][i] + p;
+                            }
+                            auto add = [&](auto wave) {
+#pragma unroll
+                                for (int r = 0; r < R; ++r) {
+                                    const double qr = vp_pin(q[r]);
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) {
+                                        const double w = wave(qr * h[i] + qu[i]);
+                                        acc[r][i] = (u == 0) ? w : acc[r][i] + w;
+                                    }
+                                }
+                            };
+                            switch (kind) {
+                                case SIG_OSC_SINE: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SINE>(t); }); break;
+                                case SIG_OSC_SAWTOOTH: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SAWTOOTH>(t); }); break;
+                                case SIG_OSC_SQUARE: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SQUARE>(t); }); break;
+                                default: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_TRIANGLE>(t); }); break;
+                            }
+                        }
+                        const double count = (double)copies;
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
+                    });
+                    continue;
+                }
+            }
             if constexpr (TAB) {
                 // the column of table slot ib that parameter slot ic selects, per voice: its first float in `tab`
                 auto columns = [&](int (&col)[VPT], int& TT) {
@@ -891,7 +950,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, typename TABLES>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, typename TABLES>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
 {
     constexpr bool BUS = C > 0;
@@ -911,7 +970,7 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
+    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES, UNI>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -933,8 +992,13 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 #ifndef SIG_VP_S_TAB
 #define SIG_VP_S_TAB 0                     // 1: the program has an OscTable or a Shape word, the kernel takes the tables as a second parameter
 #endif
+#ifndef SIG_VP_S_UNI
+#define SIG_VP_S_UNI 0                     // 1: the program has an OscUni word, the kernel takes the copies as a second parameter
+#endif
 #if SIG_VP_S_TAB
 void sig_vp_specialised(VpArgs a, VpTables tb)
+#elif SIG_VP_S_UNI
+void sig_vp_specialised(VpArgs a, VpUnison un)
 #else
 void sig_vp_specialised(VpArgs a)
 #endif
@@ -948,10 +1012,15 @@ void sig_vp_specialised(VpArgs a)
     static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
     static_assert(!(kRes && (kTab || kBand || kPm)), "FilterQ with Band, OscPM, OscTable or Shape: no variant has both");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
+    constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI);
+    static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni word is built with -DSIG_VP_S_UNI=1, any other without");
+    static_assert(!(kUni && (kTab || kBand || kPm || kRes)), "OscUni with Band, OscPM, OscTable, Shape or FilterQ: no variant has both");
 #if SIG_VP_S_TAB
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false>(a, tb);
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false, false>(a, tb);
+#elif SIG_VP_S_UNI
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, false, false, false, false, false, true>(a, un);
 #else
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes>(a, VpNoTables{});
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes, false>(a, VpNoTables{});
 #endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
@@ -965,25 +1034,31 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false, false>(a, VpNoTables{});
 }
 // the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false, false>(a, tb);
 }
 // the TAB variant with the Shape instruction (programs with a waveshaper, with or without a wavetable oscillator)
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_shape_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false, false>(a, tb);
 }
 // the RES variant (never with BAND, PM or TAB): programs with a resonant filter, whose design reads q
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_res_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true, false>(a, VpNoTables{});
+}
+// the UNI variant (never with BAND, PM, TAB or RES): a kernel of its own, whose second parameter carries the copies
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_unison_kernel(VpArgs a, VpUnison un)
+{
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true>(a, un);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -999,8 +1074,8 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ) && x.c == -1) ? 15 : x.c;       // (no select / no q: a slot number no register file has)
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTERQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
+        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI) && x.c == -1) ? 15 : x.c;       // (no select / no q / no spread: a slot number no register file has)
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCUNI && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
     }
@@ -1017,7 +1092,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res, uni; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -1090,9 +1165,22 @@ int vp_launch_res_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
     return sig_launch_status();
 }
 
+template <int VPT, bool SMALL>
+int vp_launch_unison_sink(const VpArgs& a, const VpUnison& un, int C, unsigned nwg, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_unison_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a, un); break;
+        case 1: voice_program_unison_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a, un); break;
+        case 2: voice_program_unison_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a, un); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
 template <int VPT>
-int vp_launch_file(const VpArgs& a, const VpTables& tb, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter with none of them: refused)
+int vp_launch_file(const VpArgs& a, const VpTables& tb, const VpUnison& un, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
+    // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter or a unison oscillator with none
+    // of them nor with each other: refused)
+    if (n.uni) return small_file ? vp_launch_unison_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_unison_sink<VPT, false>(a, un, C, nwg, s);
     if (n.res) return small_file ? vp_launch_res_sink<VPT, true>(a, C, nwg, s) : vp_launch_res_sink<VPT, false>(a, C, nwg, s);
     if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
     if (n.table) return small_file ? vp_launch_table_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_table_sink<VPT, false>(a, tb, C, nwg, lds, s);
@@ -1192,6 +1280,19 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
                                     double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                                     const sig_vp_tables_t* tables)
 {
+    return sig_voice_program_unison(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks,
+                                    hist_positions, blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld,
+                                    status, stream, tables, nullptr);
+}
+
+extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                        int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                        int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                        const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                        double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                                        const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
+{
+    SIG_CHECK_ARG(!unison || (unison->copies >= 1 && unison->copies <= SIG_UNISON_MAX_COPIES));
     SIG_CHECK_ARG(program && rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
     SIG_CHECK_ARG(out && (bus_channels == 0 || bus_channels == 1 || bus_channels == 2));
     SIG_CHECK_ARG(bus_channels == 0 ? out_ld >= voices : (out_ld >= bus_channels && workspace != nullptr));
@@ -1212,7 +1313,7 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false, false};
     // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
     const int n_tables = tables ? tables->n_tables : 0;
     SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
@@ -1228,8 +1329,8 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTERQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
-                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ) ? -1 : 0) && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCUNI && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI) ? -1 : 0) && x.c <= 15);
         switch (x.op) {
             case SIG_VP_OSCTABLE:
                 SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
@@ -1240,6 +1341,9 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
             case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
             case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
+            case SIG_VP_OSCUNI:
+                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params && x.kind <= SIG_OSC_TRIANGLE);
+                break;
             case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
             case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
@@ -1254,12 +1358,19 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
         if (x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) need.table = true;
         if (x.op == SIG_VP_SHAPE) need.shape = true;
         if (x.op == SIG_VP_FILTERQ) need.res = true;
+        if (x.op == SIG_VP_OSCUNI) need.uni = true;
     }
+    SIG_CHECK_ARG(!(need.uni && (need.band || need.pm || need.table || need.res)));
     SIG_CHECK_ARG(!(need.res && (need.band || need.pm || need.table)));
     SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no interpreter variant with two of them; the engine keeps such a graph per node)
     VpTables tb{};
     for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
     if (!need.table) table_lds = 0;
+    VpUnison un{};
+    if (need.uni) {
+        un.copies = unison->copies;
+        for (int u = 0; u < un.copies; ++u) { un.detune[u] = unison->detune[u]; un.offset[u] = unison->offset[u]; }
+    }
     SIG_CHECK_ARG(vp_encode(P, a.code));
     a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
     for (int k = 0; k < P.n_oscs; ++k) {
@@ -1334,12 +1445,12 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
     hipStream_t s = static_cast<hipStream_t>(stream);
     int err;
     if (hipFunction_t fn = vp_find_special(a, P, vpt, bus_channels)) {         // this very program, built as straight-line code
-        void* params[] = {&a, &tb};                                           // (an image built for a table program takes both, any other the first)
+        void* params[] = {&a, need.uni ? (void*)&un : (void*)&tb};            // (an image built for a table or a unison program takes both, any other the first)
         err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, small_file, need, bus_channels, nwg, table_lds, s);
-    else err = vp_launch_file<1>(a, tb, small_file, need, bus_channels, nwg, table_lds, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, un, small_file, need, bus_channels, nwg, table_lds, s);
+    else err = vp_launch_file<1>(a, tb, un, small_file, need, bus_channels, nwg, table_lds, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);

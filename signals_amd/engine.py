@@ -383,6 +383,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.hertz, node.phase, node.index]
     if isinstance(node, ext.Wavetable):
         return [node.hertz, node.phase, node.select]
+    if isinstance(node, ext.UnisonOsc):
+        return [node.hertz, node.phase, node.spread]
     if isinstance(node, ext.Shaper):
         return [node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
@@ -572,6 +574,9 @@ class _ControlProgram:
         elif isinstance(src, ext.Wavetable):
             raise NotBatchable(f'{src.cls_name()} in a control path: a wavetable oscillator has no block-rate program '
                                f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.UnisonOsc):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a unison oscillator has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.Shaper):
             raise NotBatchable(f'{src.cls_name()} in a control path: a waveshaper has no block-rate program '
                                f'(the eager node serves one-frame requests)')
@@ -749,6 +754,9 @@ class _Batch:
         elif isinstance(src, ext.Wavetable):
             raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a wavetable oscillator has no block-rate schedule '
                                f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.UnisonOsc):
+            raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a unison oscillator has no block-rate schedule '
+                               f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.Shaper):
             raise NotBatchable(f'{what}: {src.cls_name()} in a control path: a waveshaper has no block-rate schedule '
                                f'(the eager node serves one-frame requests)')
@@ -870,6 +878,16 @@ class _Batch:
         def bank(kind, position, rate, hertz, phase, select, out, **kw):
             return _native.osc_bank_table(position, rate, hertz, phase, select, table, out, **kw)
         return self._osc_launch(node, 'osc_bank_table', bank, (hertz, phase, select), hist, rows, kind='Table')
+
+    def _sched_unison(self, node, channels, hist, rows):
+        """a unison oscillator: one sig_osc_bank_unison launch, per-block hertz / phase / spread rows when one is modulated; the copies
+        go with the launch by value, as the node's state holds them now"""
+        hertz, phase, spread = (self._control(p, p.name) for p in (node.hertz, node.phase, node.spread))
+        copies = node.host_copies()
+
+        def bank(kind, position, rate, hertz, phase, spread, out, **kw):
+            return _native.osc_bank_unison(kind, position, rate, hertz, phase, spread, copies, out, **kw)
+        return self._osc_launch(node, 'osc_bank_unison', bank, (hertz, phase, spread), hist, rows)
 
     def _sched_shaper(self, node, channels, hist, rows):
         """a waveshaper: one sig_shaper_table launch over its input's rows (history rows included when a filter reads it), scheduled
@@ -1226,6 +1244,7 @@ class _Batch:
         (osc.Osc, _sched_osc),
         (ext.PMOsc, _sched_pm),
         (ext.Wavetable, _sched_table),
+        (ext.UnisonOsc, _sched_unison),
         (noise.White, _sched_noise),
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
@@ -1860,7 +1879,7 @@ class _ProgramRows:
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
     Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), waveshapers (ext.Shaper),
-    resonant low-pass / high-pass filters (ext.ResonantFilter), in any arrangement in which every voice is computed from its own
+    resonant low-pass / high-pass filters (ext.ResonantFilter), unison oscillators (ext.UnisonOsc), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
@@ -1868,7 +1887,7 @@ class _VoiceProgram:
     front of it from where the reference cold-started them, so no tails are kept for what it covers."""
 
     KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
-                    ext.PMOsc, ext.Wavetable, ext.Shaper, ext.ResonantFilter)
+                    ext.PMOsc, ext.Wavetable, ext.Shaper, ext.ResonantFilter, ext.UnisonOsc)
 
     def __init__(self, batch: '_Batch', top: Emitter, voices: int):
         self.batch, self.top, self.voices = batch, top, voices
@@ -1882,6 +1901,7 @@ class _VoiceProgram:
         self.adsr = None
         self.seeds: list = []
         self.tables: list = []                   # the Wavetable / Shaper nodes whose tables the launch stages, one slot per distinct state array
+        self.unison = None                       # the UnisonOsc node whose `copies` array the launch carries (one distinct array per program)
         self.temps_used, self.temps_free, self.n_temps = set(), [], 0
         self.saved: dict = {}                    # node -> [temporary, readers left]
         self.depth_of: dict = {}
@@ -1904,6 +1924,9 @@ class _VoiceProgram:
             raise _NoProgram('a resonant filter and a phase-modulation oscillator: no interpreter variant has both')
         if self.resonant and self.tables:
             raise _NoProgram('a resonant filter and a wavetable oscillator or a waveshaper: no interpreter variant has both')
+        if self.unison is not None and (self.bands or self.tables or self.resonant or any(op == 'OscPM' for op, *_ in self.code)):
+            raise _NoProgram('a unison oscillator with a band filter, a phase-modulation oscillator, a wavetable oscillator, a waveshaper '
+                             'or a resonant filter: no interpreter variant has both')
 
     # ---- pass 1: readers of every node inside the graph
     def _count(self, n):
@@ -2002,6 +2025,14 @@ class _VoiceProgram:
         elif isinstance(n, ext.Wavetable):
             select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
             self.code.append(('OscTable', 0, self._osc_slot(n, below), self._table_slot(n), select))
+            depth = 0
+        elif isinstance(n, ext.UnisonOsc):
+            # an oscillator slot like Osc; the copies are the launch's one unison slot, so every node of the program shares one array
+            if self.unison is not None and self.unison.get_state().copies is not n.get_state().copies:
+                raise _NoProgram('two unison oscillators with distinct copies arrays: the launch carries one')
+            self.unison = self.unison or n
+            spread = -1 if _ctl_unplugged(n.spread) else self._param(self._control(n.spread, below))
+            self.code.append(('OscUni', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, spread))
             depth = 0
         elif isinstance(n, ext.Shaper):
             depth = self._emit(n.input.sig, below)                             # the input's sample: in the accumulator
@@ -2173,7 +2204,8 @@ class _VoiceProgram:
                                                               b.N, b.K, CONTEXT, v, control_rows, hist, out, bus_gains=bus_gains, bus=bus,
                                                               adsr=adsr, noise_seeds=seeds, workspace=o._workspace if bus else None,
                                                               status=status, blocks_before=before,
-                                                              tables=[n.resident_table() for n in self.tables]),
+                                                              tables=[n.resident_table() for n in self.tables],
+                                                              unison=self.unison.host_copies() if self.unison is not None else None),
                          units=out.shape[0] * v)
 
     @classmethod
@@ -2208,7 +2240,10 @@ class _VoiceProgram:
         Waveshapers (Shape) likewise: 0.56 T interpreted against 0.22 T per node under a bus, 0.43 against 0.16 T with a LowPass in
         front of the shaper (tools/time_shaper.py).
         Resonant filters (FilterQ) take the program under the same rule; the q rows cost one parameter register each
-        (tools/time_resonant.py)."""
+        (tools/time_resonant.py).
+        Unison oscillators (OscUni) take the program under the same rule: seven saws per voice under a bus run at 0.33 T interpreted
+        against 0.28 T per node, 0.27 against 0.19 T behind a LowPass (tools/time_unison.py) -- a narrower
+        margin than the other oscillators', since U copies of f64 work per sample bound both routes."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
