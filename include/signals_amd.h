@@ -689,6 +689,21 @@ int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, i
                              const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                              double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                              const sig_vp_tables_t* tables, const sig_vp_unison_t* unison);
+/* sig_voice_program_unison for programs that COMBINE the extension words: two or more of the families BAND, OSCPM, OSCTABLE / SHAPE,
+ * FILTERQ and OSCUNI in one program (a unison oscillator behind a resonant filter, a wavetable through a swept band filter ...), which
+ * the three entries above refuse as described per word.  Such a program runs the interpreter's MIXED variant -- one more kernel with
+ * every handler, its second parameter the tables and the copies together -- or the image attached for it (built with
+ * -DSIG_VP_S_MIXED=1, which has exactly the program's families).  Only the exclusivity rules are lifted: a FILTERQ word and its
+ * resonant slot still go together, band slots still pair from the start of their run, an OSCTABLE table is a power of two, the
+ * tables stay inside SIG_TABLE_MAX_POINTS, an OSCUNI word needs `unison`.  In this variant LowPass / HighPass slots are designed by
+ * the resonant design at damping sqrt2, which gives the Butterworth design's bits.  A program with one family or none is launched
+ * exactly as by sig_voice_program_unison. */
+int sig_voice_program_mixed(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                            int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                            int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                            const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                            double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                            const sig_vp_tables_t* tables, const sig_vp_unison_t* unison);
 /* Tuning / test hook: force the voices per lane (1, 2; 0 = heuristic; ignored where the program does not fit the variant) and
  * the blocks per lane (0 = heuristic) of sig_voice_program.  Process-wide. */
 int sig_voice_program_set_tuning(int32_t voices_per_lane, int32_t blocks_per_lane);

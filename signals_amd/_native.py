@@ -58,6 +58,9 @@ VP_TABLE_OPS = ('OscTable', 'Shape')        # the instructions of the table vari
 VP_RES_OPS = ('FilterQ',)                   # the instruction of the resonant variant (SIG_VP_S_RES): filter slot a, q = parameter slot c | -1
 VP_UNI_OPS = ('OscUni',)                    # the instruction of the unison variant (SIG_VP_S_UNI): oscillator slot a, unison slot b = 0, spread = parameter slot c | -1
 VP_MAX_UNISON = 1                           # SIG_VP_MAX_UNISON: unison slots of a voice program (one `copies` array per launch)
+# the families of which a single-family interpreter variant (and sig_voice_program, _ex, _unison) has at most one; a program with two
+# or more of them is a MIXED program (sig_voice_program_mixed, SIG_VP_S_MIXED)
+VP_FAMILIES = {'band': ('Band',), 'pm': ('OscPM',), 'table': VP_TABLE_OPS, 'resonant': VP_RES_OPS, 'unison': VP_UNI_OPS}
 UNISON_MAX_COPIES = 16                      # SIG_UNISON_MAX_COPIES: copies of a unison oscillator (ext.py UnisonOsc)
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
 
@@ -168,6 +171,8 @@ def _argtypes() -> dict:
                                 + [ctypes.POINTER(VpTablesT)],
         'sig_voice_program_unison': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out
                                     + [ctypes.POINTER(VpTablesT), ctypes.POINTER(VpUnisonT)],
+        'sig_voice_program_mixed': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out
+                                   + [ctypes.POINTER(VpTablesT), ctypes.POINTER(VpUnisonT)],
         'sig_voice_program_set_tuning': [i32, i32],
         'sig_voice_program_geometry': [i32, i32, i32, i32, i32, i32, i32, i32, p32, p32],
         'sig_voice_program_args_size': [],
@@ -1074,7 +1079,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   adsr: dict | None = None, noise_seeds: tuple = (0, 0), workspace: torch.Tensor | None = None,
                   status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None,
                   unison=None) -> torch.Tensor:
-    """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
+    """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison, or -- a program of two or more families, `vp_families` -- sig_voice_program_mixed; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
     'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
@@ -1129,11 +1134,19 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
     args = (ctypes.byref(P), rate, position, block_frames, nblocks, context, voices, control_rows, len(hist_positions), hist,
             blocks_before, gp, gld, C, _ptr(workspace), out.data_ptr(), out.stride(0), _ptr(status), _stream(out),
             ctypes.byref(held) if held is not None else None)
-    if uni is None:                                       # (a program without the copies: the entry it always went through)
+    if len(vp_families(code)) >= 2:                       # (a combined program: the one entry that takes it; every other refuses)
+        _check(lib().sig_voice_program_mixed(*args, ctypes.byref(uni) if uni is not None else None), 'sig_voice_program_mixed')
+    elif uni is None:                                     # (a program without the copies: the entry it always went through)
         _check(lib().sig_voice_program_ex(*args), 'sig_voice_program_ex')
     else:
         _check(lib().sig_voice_program_unison(*args, ctypes.byref(uni)), 'sig_voice_program_unison')
     return out
+
+
+def vp_families(code: list) -> tuple:
+    """the families (keys of VP_FAMILIES) a program given as (op name, kind, a, b, c) tuples has words of"""
+    ops = {op for op, *_ in code}
+    return tuple(name for name, words in VP_FAMILIES.items() if ops & set(words))
 
 
 def voice_program_words(code: list) -> list:

@@ -258,7 +258,7 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
     a phase-modulated or wavetable unison; the node inside a block-rate control path (the batched engine answers NotBatchable with
     the reason and the graph keeps the eager path, which serves frames == 1 in float64); a combination with a band filter, a
     phase-modulation oscillator, a wavetable oscillator, a waveshaper or a resonant filter in one voice program (such a graph stays
-    one kernel per node); the closed-form, row-walker and cascade fused kernels; band-limiting -- the copies alias like
+    one kernel per node unless the renderer is given mixed_programs=True); the closed-form, row-walker and cascade fused kernels; band-limiting -- the copies alias like
     `osc.Sawtooth` does."""
     hertz: Receiver.BoundPort = port('hertz')
     phase: Receiver.BoundPort = port('phase')
@@ -345,7 +345,7 @@ class Shaper(BlockCachingEmitter, ImplicitChannels):
     linear, Lipschitz with L = max_i |tbl[i+1, w] - tbl[i, w]| * (T - 1) / 2.
     Out of scope: the node inside a block-rate control path (the batched engine answers NotBatchable with the reason and the
     graph keeps the eager path, which serves frames == 1 in float64); a combination with a band filter or a phase-modulation
-    oscillator in one voice program (such a graph stays one kernel per node); oversampling and anti-aliasing of the shaper;
+    oscillator in one voice program (such a graph stays one kernel per node unless the renderer is given mixed_programs=True); oversampling and anti-aliasing of the shaper;
     morphing between columns; a frame-rate `select`; the closed-form, row-walker and cascade fused kernels."""
     input: Receiver.BoundPort = port('input')
     select: Receiver.BoundPort = port('select')
@@ -406,7 +406,7 @@ class ResonantFilter(fx.CritFilter, abc.ABC):
     Out of scope: the closed-form, row-walker, cascade, enveloped-filter and bus-over-filter fused kernels (none matches the node; the
     voice program is its fast route); the node inside a block-rate control path (the batched engine answers NotBatchable with the
     reason and the graph keeps the eager path); a combination with a band filter, a phase-modulation oscillator, a wavetable
-    oscillator or a waveshaper in one voice program (such a graph stays one kernel per node); band-pass, notch and peaking responses;
+    oscillator or a waveshaper in one voice program (such a graph stays one kernel per node unless the renderer is given mixed_programs=True); band-pass, notch and peaking responses;
     a frame-rate cutoff or q; self-oscillation (q = inf); carried state or a longer context."""
     cutoff: Receiver.BoundPort = port('cutoff')
     resonance: Receiver.BoundPort = port('resonance')

@@ -81,6 +81,13 @@ struct VpNoTables {};
 // Travels the way VpTables does -- a second kernel parameter that only the UNI variant has -- and for the same reason.  Wave-uniform:
 // the handler's loop count and both values are scalars.
 struct VpUnison { int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; };
+// Both at once, for the MIXED variant (programs that combine two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni): the
+// fields of VpTables followed by those of VpUnison.  The names are disjoint, so the handlers read tb.ptr / T / W and tb.copies /
+// detune / offset from it as they do from the one they were written for.
+struct VpMixed {
+    const float* ptr[SIG_VP_MAX_TABLES]; int T[SIG_VP_MAX_TABLES], W[SIG_VP_MAX_TABLES];
+    int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES];
+};
 
 // f(integral_constant<int, i>) for a wave-uniform i < N: a scalar switch, so arrays indexed inside stay in registers
 template <int N, typename F>
@@ -189,6 +196,15 @@ template <bool SMALL> struct VpLimits {
 // UNI: the OscUni instruction (unison oscillators, ext.py UnisonOsc): the mean of the copies of one waveform; a variant of its own once
 // more (never with BAND, PM, TAB or RES).  `tb` is then the variant's VpUnison: TABLES is whatever second kernel parameter the
 // variant has (VpTables, VpUnison) or VpNoTables
+// The "never with" above is the single-family variants'.  The MIXED variant (voice_program_mixed_kernel, reached only through
+// sig_voice_program_mixed) has all six flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
+//   * RES on: every LowPass / HighPass slot is designed by vp_design_res at d = sqrt2 (`single` is off), which are vp_design's bits;
+//     band slots are neither `resonant` nor `plain` there and keep design_band2;
+//   * a run of band slots pairs from its start whatever stands next to it: bfirst[f] looks only at bfirst[f - 1], and a resonant or
+//     plain slot at f - 1 is never a band's first.  Two pairs cannot share f / 2 (that would take slots f, f + 1 and f + 1, f + 2);
+//   * the qreg scan reads the FilterQ words alone, the handlers in front of the switch (FilterQ, OscUni, Shape, OscTable) each test
+//     their own opcode and `continue`, so their order does not matter;
+//   * with no table in the launch tb.ptr[0] is null and nothing is staged (no dynamic LDS is asked for either).
 template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, typename TABLES>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
                                         [[maybe_unused]] const float* tab)
@@ -995,7 +1011,12 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 #ifndef SIG_VP_S_UNI
 #define SIG_VP_S_UNI 0                     // 1: the program has an OscUni word, the kernel takes the copies as a second parameter
 #endif
-#if SIG_VP_S_TAB
+#ifndef SIG_VP_S_MIXED
+#define SIG_VP_S_MIXED 0                   // 1: the program combines two or more of Band, OscPM, OscTable / Shape, FilterQ, OscUni; the kernel takes a VpMixed
+#endif
+#if SIG_VP_S_MIXED
+void sig_vp_specialised(VpArgs a, VpMixed mx)
+#elif SIG_VP_S_TAB
 void sig_vp_specialised(VpArgs a, VpTables tb)
 #elif SIG_VP_S_UNI
 void sig_vp_specialised(VpArgs a, VpUnison un)
@@ -1010,12 +1031,19 @@ void sig_vp_specialised(VpArgs a)
 #define SIG_VP_S_RES 0                     // 1: the program has a FilterQ word (the resonant design)
 #endif
     static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
-    static_assert(!(kRes && (kTab || kBand || kPm)), "FilterQ with Band, OscPM, OscTable or Shape: no variant has both");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
     constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI);
     static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni word is built with -DSIG_VP_S_UNI=1, any other without");
+    constexpr int kFamilies = (int)kBand + (int)kPm + (int)kTab + (int)kRes + (int)kUni;
+    static_assert((kFamilies >= 2) == (SIG_VP_S_MIXED != 0), "a program with two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni is built with -DSIG_VP_S_MIXED=1, any other without");
+#if !SIG_VP_S_MIXED
+    static_assert(!(kRes && (kTab || kBand || kPm)), "FilterQ with Band, OscPM, OscTable or Shape: no variant has both");
     static_assert(!(kUni && (kTab || kBand || kPm || kRes)), "OscUni with Band, OscPM, OscTable, Shape or FilterQ: no variant has both");
-#if SIG_VP_S_TAB
+    static_assert(!(kBand && kPm) && !(kTab && (kBand || kPm)), "Band, OscPM and OscTable / Shape: no variant has two of them");
+#endif
+#if SIG_VP_S_MIXED
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, kTab, kShape, kRes, kUni>(a, mx);      // exactly the families the program has
+#elif SIG_VP_S_TAB
     vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false, false>(a, tb);
 #elif SIG_VP_S_UNI
     vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, false, false, false, false, false, true>(a, un);
@@ -1059,6 +1087,13 @@ template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_unison_kernel(VpArgs a, VpUnison un)
 {
     vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true>(a, un);
+}
+// the MIXED variant: every family at once, for programs that combine two or more of them (sig_voice_program_mixed only); its
+// second parameter carries the tables and the copies
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_mixed_kernel(VpArgs a, VpMixed mx)
+{
+    vp_kernel_body<VPT, SMALL, C, true, true, true, true, true, true>(a, mx);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -1176,10 +1211,25 @@ int vp_launch_unison_sink(const VpArgs& a, const VpUnison& un, int C, unsigned n
     return sig_launch_status();
 }
 
+template <int VPT, bool SMALL>
+int vp_launch_mixed_sink(const VpArgs& a, const VpMixed& mx, int C, unsigned nwg, size_t lds, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_mixed_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, mx); break;
+        case 1: voice_program_mixed_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, mx); break;
+        case 2: voice_program_mixed_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, mx); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
+// the families of which every single-family variant has one
+int vp_families(const VpNeeds& n) { return (int)n.band + (int)n.pm + (int)n.table + (int)n.res + (int)n.uni; }
+
 template <int VPT>
-int vp_launch_file(const VpArgs& a, const VpTables& tb, const VpUnison& un, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
+int vp_launch_file(const VpArgs& a, const VpTables& tb, const VpUnison& un, const VpMixed& mx, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
     // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter or a unison oscillator with none
-    // of them nor with each other: refused)
+    // of them nor with each other: refused by every entry but sig_voice_program_mixed, whose combined programs run the MIXED variant)
+    if (vp_families(n) >= 2) return small_file ? vp_launch_mixed_sink<VPT, true>(a, mx, C, nwg, lds, s) : vp_launch_mixed_sink<VPT, false>(a, mx, C, nwg, lds, s);
     if (n.uni) return small_file ? vp_launch_unison_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_unison_sink<VPT, false>(a, un, C, nwg, s);
     if (n.res) return small_file ? vp_launch_res_sink<VPT, true>(a, C, nwg, s) : vp_launch_res_sink<VPT, false>(a, C, nwg, s);
     if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
@@ -1262,35 +1312,14 @@ extern "C" int sig_voice_program_detach_all(void)
     return 0;
 }
 
-extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
-                                 int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
-                                 int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
-                                 const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
-                                 double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream)
-{
-    return sig_voice_program_ex(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks,
-                                hist_positions, blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld,
-                                status, stream, nullptr);
-}
-
-extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
-                                    int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
-                                    int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
-                                    const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
-                                    double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
-                                    const sig_vp_tables_t* tables)
-{
-    return sig_voice_program_unison(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks,
-                                    hist_positions, blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld,
-                                    status, stream, tables, nullptr);
-}
-
-extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
-                                        int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
-                                        int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
-                                        const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
-                                        double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
-                                        const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
+// The one body of sig_voice_program, _ex, _unison (allow_mixed false) and _mixed (true): everything but the three exclusivity
+// checks is the same for a program that combines the extension words.
+static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                  int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                  int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                  const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                  double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                  const sig_vp_tables_t* tables, const sig_vp_unison_t* unison, bool allow_mixed)
 {
     SIG_CHECK_ARG(!unison || (unison->copies >= 1 && unison->copies <= SIG_UNISON_MAX_COPIES));
     SIG_CHECK_ARG(program && rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
@@ -1360,9 +1389,12 @@ extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int3
         if (x.op == SIG_VP_FILTERQ) need.res = true;
         if (x.op == SIG_VP_OSCUNI) need.uni = true;
     }
-    SIG_CHECK_ARG(!(need.uni && (need.band || need.pm || need.table || need.res)));
-    SIG_CHECK_ARG(!(need.res && (need.band || need.pm || need.table)));
-    SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no interpreter variant with two of them; the engine keeps such a graph per node)
+    if (!allow_mixed) {
+        SIG_CHECK_ARG(!(need.uni && (need.band || need.pm || need.table || need.res)));
+        SIG_CHECK_ARG(!(need.res && (need.band || need.pm || need.table)));
+        SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no single-family variant with two of them; the engine keeps such a graph per node unless asked for mixed programs)
+    }
+    const bool mixed = vp_families(need) >= 2;
     VpTables tb{};
     for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
     if (!need.table) table_lds = 0;
@@ -1370,6 +1402,12 @@ extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int3
     if (need.uni) {
         un.copies = unison->copies;
         for (int u = 0; u < un.copies; ++u) { un.detune[u] = unison->detune[u]; un.offset[u] = unison->offset[u]; }
+    }
+    VpMixed mx{};
+    if (mixed) {
+        for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) { mx.ptr[k] = need.table ? tb.ptr[k] : nullptr; mx.T[k] = tb.T[k]; mx.W[k] = tb.W[k]; }     // (no table word: nothing is staged)
+        mx.copies = un.copies;
+        for (int u = 0; u < un.copies; ++u) { mx.detune[u] = un.detune[u]; mx.offset[u] = un.offset[u]; }
     }
     SIG_CHECK_ARG(vp_encode(P, a.code));
     a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
@@ -1445,16 +1483,61 @@ extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int3
     hipStream_t s = static_cast<hipStream_t>(stream);
     int err;
     if (hipFunction_t fn = vp_find_special(a, P, vpt, bus_channels)) {         // this very program, built as straight-line code
-        void* params[] = {&a, need.uni ? (void*)&un : (void*)&tb};            // (an image built for a table or a unison program takes both, any other the first)
+        void* params[] = {&a, mixed ? (void*)&mx : need.uni ? (void*)&un : (void*)&tb};     // (an image built for a mixed, a table or a unison program takes both, any other the first)
         err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, un, small_file, need, bus_channels, nwg, table_lds, s);
-    else err = vp_launch_file<1>(a, tb, un, small_file, need, bus_channels, nwg, table_lds, s);
+    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, un, mx, small_file, need, bus_channels, nwg, table_lds, s);
+    else err = vp_launch_file<1>(a, tb, un, mx, small_file, need, bus_channels, nwg, table_lds, s);
     if (err || bus_channels == 0 || a.bus_out) return err;
     switch (bus_channels) {
         case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);
         default: return sig_bus::launch_partials<2>(a.partials, a.voice_tiles, rows, out, out_ld, s);
     }
+}
+
+extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                 int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                 int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                 const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                 double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream)
+{
+    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, nullptr, nullptr, false);
+}
+
+extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                    int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                    int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                    const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                    double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                                    const sig_vp_tables_t* tables)
+{
+    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, nullptr, false);
+}
+
+extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                        int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                        int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                        const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                        double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                                        const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
+{
+    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, false);
+}
+
+// sig_voice_program_unison for programs that combine two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni: the MIXED
+// variant of the interpreter (or the image attached for the program).  Every other check of the body holds
+extern "C" int sig_voice_program_mixed(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
+                                        int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
+                                        int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
+                                        const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
+                                        double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
+                                        const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
+{
+    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, true);
 }
 #endif  // SIG_VP_STATIC_CODE

@@ -187,7 +187,7 @@ class BatchRenderer:
 
     def __init__(self, node: Emitter, channels: int, rate: int = 48000, timer: KernelTimer | None = None,
                  fuse: bool = True, fuse_bus: bool = True, graph_replay: bool = False, fuse_program: bool | None = None,
-                 specialise: bool | str | None = None, pipeline: int = 1):
+                 specialise: bool | str | None = None, pipeline: int = 1, mixed_programs: bool = False):
         """`fuse`: let Filter(Osc) [and a Gain on top] run as one kernel when the intermediate outputs have
         no other consumer (sig_fused_osc_biquad); `fuse_bus`: also fold a SumBus on top into that launch
         (sig_fused_voice_bus).  fuse=False = one kernel per node, bit-identical to the eager path.
@@ -200,6 +200,11 @@ class BatchRenderer:
         arithmetic as straight-line code, 1.6-2x its rate; without hipcc the interpreter keeps running.  'background': the build
         runs on a worker thread and the interpreter renders until the kernel is attached (a real-time sink never waits for
         the compiler).  Default: off, or the environment's SIG_SPECIALISE=1.
+        `mixed_programs` (default off): let a voice program COMBINE the extension nodes -- two or more of band filters, phase-modulation
+        carriers, wavetable oscillators / waveshapers, resonant filters and unison oscillators in one graph (UnisonSawtooth ->
+        ResonantLowPass, Wavetable -> BandPass ...).  Off, such a graph runs one kernel per node on every route; on, it is one launch
+        of the interpreter's mixed variant (sig_voice_program_mixed) or, with `specialise`, of the kernel built for it
+        (_VoiceProgram.worthwhile has the policy).
         `pipeline` (2 or 3; default 1 = off): consecutive batches of a graph that is ONE fused launch without history (the C2
         voice graph) go to alternating HIP streams, each with its own workspace, so the tail of one launch overlaps the head of
         the next (a 256-block batch is a single round of waves: 24.4 -> ~18 us per batch).  The caller's stream waits for each
@@ -232,6 +237,7 @@ class BatchRenderer:
         # one kernel per node (_VoiceProgram.worthwhile), 'always': wherever the graph compiles
         self.fuse_program = fuse if fuse_program is None else (fuse and fuse_program)
         self.specialise = bool(int(os.environ.get('SIG_SPECIALISE', '0'))) if specialise is None else specialise
+        self.mixed_programs = bool(mixed_programs)          # voice programs may combine the extension families (sig_voice_program_mixed)
         self.pipeline = max(1, int(pipeline))
         self._pipe = None                                  # streams, workspaces, pre-bound calls and output rings of the pipelined replay
         self._status: dict[Emitter, runtime.StatusWord] = {}
@@ -1042,7 +1048,7 @@ class _Batch:
     def _program_store(self, node, channels):
         """the per-voice graph under `node` as one interpreted launch (sig_voice_program) storing its rows, or None"""
         memo_keys = {k[0] for k in self._memo}
-        prog = _VoiceProgram.compile(self, node, channels)
+        prog = _VoiceProgram.compile(self, node, channels, mixed=self.owner.mixed_programs)
         if prog is None or any(n in memo_keys for n in prog.uses if n is not node):
             return None                                                        # (an inner node already has rows in this batch: someone else reads it)
         if self.owner.fuse_program != 'always' and not prog.worthwhile():
@@ -1055,7 +1061,7 @@ class _Batch:
         wide = any(t is None or t.shape[1] > 1 for t in tensors) or any(isinstance(n, (noise.White, ext.ADSR)) for n in prog.uses)
         voices = channels if wide else 1
         if voices != channels:
-            prog = _VoiceProgram.compile(self, node, voices)
+            prog = _VoiceProgram.compile(self, node, voices, mixed=self.owner.mixed_programs)
             if prog is None:
                 return None
         out = torch.empty((self.N * self.K, voices), dtype=AUDIO_DTYPE, device=runtime.device())
@@ -1070,7 +1076,7 @@ class _Batch:
         if C not in (1, 2) or voices is None or (gains is not None and gains.shape[1] != voices):
             return None
         memo_keys = {k[0] for k in self._memo}
-        prog = _VoiceProgram.compile(self, src_port.sig, voices, min_nodes=1)
+        prog = _VoiceProgram.compile(self, src_port.sig, voices, min_nodes=1, mixed=self.owner.mixed_programs)
         if prog is None or any(n in memo_keys for n in prog.uses):
             return None
         if self.owner.fuse_program != 'always' and not prog.worthwhile():
@@ -1889,8 +1895,10 @@ class _VoiceProgram:
     KERNEL_NODES = (osc.Osc, fx.SingleCritFilter, fx.DoubleCritFilter, fx.Gain, fx.Amp, fx.Mix, fx.RingMod, ext.ADSR, noise.White,
                     ext.PMOsc, ext.Wavetable, ext.Shaper, ext.ResonantFilter, ext.UnisonOsc)
 
-    def __init__(self, batch: '_Batch', top: Emitter, voices: int):
-        self.batch, self.top, self.voices = batch, top, voices
+    def __init__(self, batch: '_Batch', top: Emitter, voices: int, mixed: bool = False):
+        """`mixed`: the program may combine two or more of the extension families (_native.VP_FAMILIES); it then runs through
+        sig_voice_program_mixed.  Off (the default), such a graph is not a program: _NoProgram names the pair."""
+        self.batch, self.top, self.voices, self.mixed = batch, top, voices, mixed
         self.code: list = []
         self.oscs: list = []                     # (hertz control index, phase control index | None)
         self.params: list = []                   # control index per parameter register
@@ -1914,17 +1922,19 @@ class _VoiceProgram:
         self.depth = self._emit(top, 0)
         if len(self.code) > _native.VP_MAX_INS:
             raise _NoProgram('program too long')
-        if self.bands and any(op == 'OscPM' for op, *_ in self.code):
-            raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
-        if self.tables and (self.bands or any(op == 'OscPM' for op, *_ in self.code)):
-            raise _NoProgram('a wavetable oscillator or a waveshaper with a band filter or a phase-modulation oscillator: no interpreter variant has both')
-        if self.resonant and self.bands:
-            raise _NoProgram('a resonant filter and a band filter: no interpreter variant has both')
-        if self.resonant and any(op == 'OscPM' for op, *_ in self.code):
-            raise _NoProgram('a resonant filter and a phase-modulation oscillator: no interpreter variant has both')
-        if self.resonant and self.tables:
-            raise _NoProgram('a resonant filter and a wavetable oscillator or a waveshaper: no interpreter variant has both')
-        if self.unison is not None and (self.bands or self.tables or self.resonant or any(op == 'OscPM' for op, *_ in self.code)):
+        self.families = _native.vp_families(self.code)
+        if len(self.families) >= 2 and not mixed:
+            has = set(self.families)
+            if has >= {'band', 'pm'}:
+                raise _NoProgram('a band filter and a phase-modulation oscillator: no interpreter variant has both')
+            if 'table' in has and has & {'band', 'pm'}:
+                raise _NoProgram('a wavetable oscillator or a waveshaper with a band filter or a phase-modulation oscillator: no interpreter variant has both')
+            if has >= {'resonant', 'band'}:
+                raise _NoProgram('a resonant filter and a band filter: no interpreter variant has both')
+            if has >= {'resonant', 'pm'}:
+                raise _NoProgram('a resonant filter and a phase-modulation oscillator: no interpreter variant has both')
+            if has >= {'resonant', 'table'}:
+                raise _NoProgram('a resonant filter and a wavetable oscillator or a waveshaper: no interpreter variant has both')
             raise _NoProgram('a unison oscillator with a band filter, a phase-modulation oscillator, a wavetable oscillator, a waveshaper '
                              'or a resonant filter: no interpreter variant has both')
 
@@ -2209,13 +2219,13 @@ class _VoiceProgram:
                          units=out.shape[0] * v)
 
     @classmethod
-    def compile(cls, batch: '_Batch', top: Emitter, voices: int, min_nodes: int = 2):
+    def compile(cls, batch: '_Batch', top: Emitter, voices: int, min_nodes: int = 2, mixed: bool = False):
         """the program, or None when the graph is not one (or is a single kernel anyway: under a bus one node is enough, the
-        bus being the second -- `min_nodes`)"""
+        bus being the second -- `min_nodes`); `mixed`: as for the constructor"""
         if top is None or not top.get_state().enabled:
             return None
         try:
-            prog = cls(batch, top, voices)
+            prog = cls(batch, top, voices, mixed=mixed)
         except _NoProgram:
             return None
         return prog if prog.kernel_nodes >= min_nodes else None
@@ -2243,7 +2253,14 @@ class _VoiceProgram:
         (tools/time_resonant.py).
         Unison oscillators (OscUni) take the program under the same rule: seven saws per voice under a bus run at 0.33 T interpreted
         against 0.28 T per node, 0.27 against 0.19 T behind a LowPass (tools/time_unison.py) -- a narrower
-        margin than the other oscillators', since U copies of f64 work per sample bound both routes."""
+        margin than the other oscillators', since U copies of f64 work per sample bound both routes.
+        Mixed programs (two or more of the families of _native.VP_FAMILIES; only compiled with `mixed_programs=True`) take the program
+        under the same rule: measured (tools/time_mixed.py, 1024 voices, stereo bus, N = 256, three routes in alternation, median of 7
+        windows of 0.5 s, attached kernels switched off for the interpreter) the interpreter's mixed variant runs UnisonSawtooth ->
+        ResonantLowPass at 0.26 T against 0.19 T per node, Wavetable -> ResonantLowPass at 0.49 against 0.29 T, UnisonSawtooth ->
+        ResonantLowPass -> Shaper at 0.21 against 0.14 T -- 1.4-1.7x on all three, the spread over the windows below 1 % -- so the
+        small-file rule extends to them; the specialised kernels run at 0.39 / 0.82 / 0.30 T.  A mixed program that needs the full register file (an ADSR, three filters ...) stays per node
+        interpreted, like any other, and takes the short-block and the specialised routes."""
         b = self.batch
         small_file = (len(self.filters) <= 2 and len(self.oscs) <= 3 and len(self.params) <= 4 and self.n_temps <= 1
                       and self.adsr is None and not self.seeds and not any(op == 'Amp' for op, *_ in self.code))
