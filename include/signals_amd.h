@@ -128,6 +128,30 @@ int sig_osc_bank_unison(int kind, int64_t position, int64_t position_step, int32
                         int32_t copies, const double* detune, const double* offsets,
                         void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Band-limited oscillator, chain/ext.py BlepSquare / BlepSawtooth / BlepTriangle: sig_osc_bank_unison's arguments, checks and
+ * expression with each copy's waveform corrected by a two-sample polynomial band-limited step (PolyBLEP) around its edges.  kind is
+ * SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH or SIG_OSC_TRIANGLE; SIG_OSC_SINE has no edge and is hipErrorInvalidValue.  With r_u, h_u, q_u and
+ * t_u as there (bit for bit), per copy, voice and parameter row  d = min(|h_u| / rate, 0.5)  and, per sample,
+ *   step(m)   = 2x - x*x - 1, x = m / d  if m < d  |  y*y + 2y + 1, y = (m - 1) / d  if m > 1 - d  |  0
+ *   corner(m) = (1 - m/d)^3              if m < d  |  ((m - 1)/d + 1)^3              if m > 1 - d  |  0
+ *   Sawtooth: m = mod(t - 0.5, 1);   w = (2m - 1) - step(m)
+ *   Square:   m = mod(t, 1);         w = (m < 0.5 ? 1 : -1) + step(m) - step(mod(t + 0.5, 1))
+ *   Triangle: m = mod(t - 0.25, 1);  w = (4 mod(t - 0.25, 0.5) - 1) * (m < 0.5 ? -1 : 1) + (4/3) d (corner(mod(t + 0.25, 1)) - corner(m))
+ *             (the first term is 4|m - 0.5| - 1 in sig_osc_bank's order of operations)
+ *   out[n,v] = (((w_0 + w_1) + w_2) + ...) / copies
+ * The kernel multiplies by a rounded 1 / d (one divide per copy, voice and parameter row, none per sample): the float64 value in
+ * front of the store is within 1e-14 of the expression evaluated in numpy's order; outside every window it is the naive waveform's
+ * bits, so copies == 1 with detune[0] == offsets[0] == 0 gives sig_osc_bank's samples there.  d == 0 (0 Hz) selects no window;
+ * hertz < 0 uses |h_u|; above rate / 4 the Square's windows overlap and above rate / 2 d is clamped: defined, no longer a band
+ * limit.  A non-finite t gives NaN.  Position-pure. */
+int sig_osc_bank_blep(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                      int32_t voices, int32_t rows_per_param,
+                      const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                      const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                      const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+                      int32_t copies, const double* detune, const double* offsets,
+                      void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Table-lookup waveshaper, chain/ext.py Shaper (build-defined: the reference has no memoryless non-linearity but Amp).  `table`
  * float32 (T, W) row-major in device memory: W transfer curves of T points each, spanning input -1 .. +1; T >= 2 (any integer: 2^k + 1
  * points put a knot at x = 0), W >= 1, T * W <= SIG_TABLE_MAX_POINTS.  For every row n and voice v, in f64, every operation rounded:
@@ -624,6 +648,9 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *          sig_voice_program_unison (only slot 0 exists, SIG_VP_MAX_UNISON = 1), spread = params[c], c == -1: unplugged = 0.  The
  *          copies travel by value in the launch.  Refused together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ,
  *          hipErrorInvalidValue: the interpreter variant with the unison handler has none of them; so is one launched without `unison`
+ *   OSCBLEP acc = band-limited oscillator (sig_osc_bank_blep's expression, m = t - floor(t) as one v_fract_f64) of kind `kind` (not
+ *          SIG_OSC_SINE) with OSCUNI's operands: oscillator slot a, the copies of unison slot b = 0, spread = params[c], c == -1:
+ *          unplugged = 0.  A word of the unison family: it reads the `unison` argument, and is refused wherever OSCUNI is
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -646,10 +673,10 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * > 0 likewise and sets SIG_STATUS_BAD_RESONANCE (never for a voice past `voices`). */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
-       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16 };
+       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16, SIG_VP_OSCBLEP = 17 };
 enum { SIG_VP_MAX_TABLES = 2, SIG_VP_MAX_UNISON = 1 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI: c may be -1 */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI, OSCBLEP: c may be -1 */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];
@@ -681,7 +708,8 @@ int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64
  * parameter of its own): 1 <= copies <= SIG_UNISON_MAX_COPIES rows (detune[u], offset[u]).  NULL for a program without the
  * instruction: sig_voice_program_ex is this call with NULL.  Refused before any device work, hipErrorInvalidValue: copies out of
  * range, NULL with an OSCUNI word in the program, an OSCUNI word with b != 0, a >= n_oscs, c >= n_params or a kind above
- * SIG_OSC_TRIANGLE, and OSCUNI together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ. */
+ * SIG_OSC_TRIANGLE, and OSCUNI together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ.  An OSCBLEP word reads the same copies and
+ * is refused in the same cases, and with kind SIG_OSC_SINE. */
 typedef struct { int32_t copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; } sig_vp_unison_t;
 int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
                              int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,

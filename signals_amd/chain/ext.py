@@ -259,7 +259,7 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
     the reason and the graph keeps the eager path, which serves frames == 1 in float64); a combination with a band filter, a
     phase-modulation oscillator, a wavetable oscillator, a waveshaper or a resonant filter in one voice program (such a graph stays
     one kernel per node unless the renderer is given mixed_programs=True); the closed-form, row-walker and cascade fused kernels; band-limiting -- the copies alias like
-    `osc.Sawtooth` does."""
+    `osc.Sawtooth` does (`BlepOsc` below is the band-limited one)."""
     hertz: Receiver.BoundPort = port('hertz')
     phase: Receiver.BoundPort = port('phase')
     spread: Receiver.BoundPort = port('spread')
@@ -278,6 +278,12 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
         """kernel selector: 'Sine' | 'Square' | 'Sawtooth' | 'Triangle'"""
         raise NotImplementedError
 
+    @classmethod
+    def bandlimited(cls) -> bool:
+        """False: osc.py's naive waveform per copy (sig_osc_bank_unison, the OscUni word); True: BlepOsc's corrected one
+        (sig_osc_bank_blep, the OscBlep word).  Everything else about the node is the same to the engine"""
+        return False
+
     def host_copies(self) -> np.ndarray:
         """the (U, 2) float64 array a launch takes by value, as the state holds it now"""
         return np.ascontiguousarray(self._state.copies, dtype=np.float64)
@@ -289,7 +295,8 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
         loc = request.loc
         frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, spread.shape)
         out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
-        return _native.osc_bank_unison(self.kind(), loc.position, loc.rate, hertz, phase, spread, self.host_copies(), out)
+        bank = _native.osc_bank_blep if self.bandlimited() else _native.osc_bank_unison
+        return bank(self.kind(), loc.position, loc.rate, hertz, phase, spread, self.host_copies(), out)
 
 
 class UnisonSine(UnisonOsc):
@@ -314,6 +321,72 @@ class UnisonSawtooth(UnisonOsc):
 
 
 class UnisonTriangle(UnisonOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Triangle'
+
+
+def _single_copy() -> np.ndarray:
+    """one copy, no detune, no offset: one clean oscillator"""
+    return np.zeros((1, 2))
+
+
+class BlepOsc(UnisonOsc, abc.ABC):
+    """Band-limited square, sawtooth and triangle: `UnisonOsc` -- the same ports hertz, phase and spread, all block-rate, the same
+    `copies` state and validator, the same phase t_u per copy bit for bit -- with each copy's waveform corrected by a two-sample
+    polynomial band-limited step (PolyBLEP) around its edges, so that the partials above half the rate fold back some 15 dB weaker
+    than osc.py's closed forms let them.  The default is copies = [[0, 0]]: one clean oscillator; the JP-8000 array
+    (`ext.UNISON_DETUNE`, `UnisonOsc`'s default) gives the anti-aliased supersaw.  There is no Sine: it has no edge.
+    For copy u, row n and voice v, in float64 and every operation rounded:
+        r_u, h_u, q_u, t_u as UnisonOsc
+        d = min(|h_u| / rate, 0.5)                                   (the phase increment per sample; per copy, voice and block)
+        step(m)   = 2x - x*x - 1      with x = m / d            if m < d
+                  = y*y + 2y + 1      with y = (m - 1) / d      if m > 1 - d
+                  = 0                                            otherwise
+        corner(m) = (1 - m/d)^3                                  if m < d
+                  = ((m - 1)/d + 1)^3                            if m > 1 - d
+                  = 0                                            otherwise
+        Sawtooth: m = mod(t - 0.5, 1);  w = (2m - 1) - step(m)
+        Square:   m = mod(t, 1);        w = (m < 0.5 ? 1 : -1) + step(m) - step(mod(t + 0.5, 1))
+        Triangle: m = mod(t - 0.25, 1); w = tri(t - 0.25) + (4/3) d (corner(mod(t + 0.25, 1)) - corner(m))
+                  tri(u) = (4 mod(u, 0.5) - 1) * (m < 0.5 ? -1 : 1)       (= 4|m - 0.5| - 1, in osc.py's own order)
+        out = (sum over u ascending of w_u) / U
+    (kernel: sig_osc_bank_blep, which multiplies by a rounded 1 / d where this divides: within 1e-14; restated in numpy by
+    tests/blep_reference.py).  Continuous in t for every kind and every d > 0, so a phase one ulp off moves the sample by
+    (2 + 2/d) ulp at most, where the naive edge jumps by 2.  A non-finite t gives NaN.  The naive parts of Square and Triangle drop
+    np.sign's isolated zero at the edge (with it the corrected wave would spike at exactly m = 1/2); the Triangle's is written in
+    osc.py's order, because 4|m - 0.5| - 1 rounds m - 0.5 below m = 1/4: outside the windows every kind is `osc.Osc` bit for bit.  d = 0 (0 Hz) selects no window:
+    the naive value.  hertz < 0 uses |h|: the residual is symmetric under time reversal.  Above rate / 4 the Square's two windows
+    overlap, and above rate / 2 d is clamped: the formula is still the definition, but it no longer band-limits there.  The
+    correction is a pure function of t and d: position-pure like its parent, no carried state, no table.
+    Out of scope: what UnisonOsc leaves out; a band-limited phase-modulation or wavetable oscillator; `osc.*` itself and the
+    closed-form, row-walker and cascade fused kernels, which keep the naive forms; a 4-point BLEP; oversampling."""
+
+    @state
+    class State(UnisonOsc.State):
+        copies: np.ndarray = attr.ib(factory=_single_copy, validator=_validate_copies, on_setattr=attr.setters.validate)
+
+    @classmethod
+    def bandlimited(cls) -> bool:
+        return True
+
+
+class BlepSquare(BlepOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Square'
+
+
+class BlepSawtooth(BlepOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sawtooth'
+
+
+class BlepTriangle(BlepOsc):
 
     @classmethod
     def kind(cls) -> str:

@@ -136,6 +136,72 @@ template <int KIND> __device__ __forceinline__ double osc_wave_fused(double t) {
     return osc_sine(t);
 }
 
+// ---- band-limited Square / Sawtooth / Triangle (chain/ext.py BlepOsc): the naive waveform plus a two-sample polynomial residual
+// (PolyBLEP) around each edge.  d = min(|hertz| / rate, 0.5) is the phase increment per sample, inv_d = 1 / d (the caller divides
+// once per copy, voice and block; the rows multiply).  With x = m / d below d and y = (m - 1) / d above 1 - d the definition's
+//   step(m)   = 2x - x*x - 1 = -(x - 1)^2   |   y*y + 2y + 1 = (y + 1)^2   |   0
+//   corner(m) = (1 - x)^3    = -(x - 1)^3   |   (y + 1)^3                  |   0
+// are both one power of z = x - 1 | y + 1, negated below d: one multiply and one add per side, one select, the power, the sign.
+// Against the definition evaluated in numpy's order: inv_d is within 1 ulp of 1 / d and x, y lie in [-1, 1], so z is within 3.4e-16
+// of the definition's; the powers have slope <= 3 and round twice more: < 2e-15 per term, inside the 1e-14 the entry promises.
+// Every choice is a select: with d == 0 (inv_d == inf) z is an infinity or a NaN that no window takes, and the result is 0.
+// The two windows exclude each other for d <= 0.5.  A NaN m takes none.
+// SIG_BLEP_SKIP=1 is a tuning build of osc_bank.hip ALONE (FILE=osc_bank.hip tools/build_variant.sh): the residual behind a
+// wave-uniform branch, skipped where no lane of the wave is in a window.  The ballot needs every lane of the wave active, which
+// holds in osc_bank_blep_kernel (its only exits are wave-uniform) and was not examined for the program handlers: voice_program.hip
+// refuses the macro.  Measured against the selects and not taken: DESIGN.md section 7.
+#ifndef SIG_BLEP_SKIP
+#define SIG_BLEP_SKIP 0
+#endif
+template <int POW> __device__ __forceinline__ double blep_residual(double m, double d, double inv_d) {
+    const bool below = m < d, above = m > 1.0 - d;
+#if SIG_BLEP_SKIP
+    if (__builtin_amdgcn_ballot_w64(below || above) == 0) return 0.0;          // (every lane is active in osc_bank_blep_kernel)
+#endif
+    const double z = below ? m * inv_d - 1.0 : (m - 1.0) * inv_d + 1.0;
+    const double p = (POW == 2) ? z * z : z * z * z;
+    return below ? -p : (above ? p : 0.0);
+}
+
+// m = mod(t, 1): numpy's (the per-node kernel, whose f64 store is compared within 1e-14 and whose rows outside every window are
+// the plain oscillator's bits) or v_fract_f64 (the fused handlers: see osc_sawtooth_fract; the corrected waveform is continuous, so
+// the corner costs 2.2e-16 * (2 + 2 / d) in the sample at most)
+template <bool FRACT> __device__ __forceinline__ double blep_mod1(double t) {
+    if (FRACT) return __builtin_amdgcn_fract(t);
+    return sig_npmod_pow2<1>(t);
+}
+
+// Above rate / 4 (d > 0.25) the Square's two windows overlap and above rate / 2 d is clamped: still the definition, no longer a
+// band limit.  The naive parts of Square and Triangle have no zero at the edge (np.sign's there would leave a spike of height 1
+// at exactly m = 1/2 in the corrected wave); a NaN m stays a NaN.
+template <int KIND, bool FRACT = false> __device__ __forceinline__ double osc_blep(double t, double d, double inv_d) {
+    static_assert(KIND == SIG_OSC_SQUARE || KIND == SIG_OSC_SAWTOOTH || KIND == SIG_OSC_TRIANGLE, "no band-limited Sine: it has no edge");
+    if (KIND == SIG_OSC_SAWTOOTH) {
+        const double m = blep_mod1<FRACT>(t - 0.5);
+        return fma(m, 2.0, -1.0) - blep_residual<2>(m, d, inv_d);              // (2m is exact: the single rounding of 2 * m - 1)
+    }
+    if (KIND == SIG_OSC_SQUARE) {
+        const double m = blep_mod1<FRACT>(t);
+        const double naive = (m < 0.5) ? 1.0 : ((m >= 0.5) ? -1.0 : m);
+        return (naive + blep_residual<2>(m, d, inv_d)) - blep_residual<2>(blep_mod1<FRACT>(t + 0.5), d, inv_d);
+    }
+    // Triangle: the reference's own closed form (4 mod(u, 1/2) - 1) * sign(mod(u, 1) - 1/2), u = t - 1/4, with the sign's zero dropped
+    // -- 4 |m - 1/2| - 1 in real numbers, but in this order the value outside the windows is osc_triangle's bit for bit (m - 1/2
+    // rounds for m < 1/4).  mod(u, 1/2) is m or m - 1/2 (exact above 1/2) behind v_fract_f64
+    const double u = t - 0.25;
+    const double m = blep_mod1<FRACT>(u);
+    const double half = FRACT ? ((m < 0.5) ? m : m - 0.5) : sig_npmod_pow2<2>(u);
+    const double r = fma(half, 4.0, -1.0);                                     // (the product by 4 is exact: numpy's 4 * mod(u, 0.5) - 1)
+    const double naive = (m < 0.5) ? -r : r;                                   // (a NaN m: r is a NaN already)
+    return naive + (4.0 / 3.0 * d) * (blep_residual<3>(blep_mod1<FRACT>(t + 0.25), d, inv_d) - blep_residual<3>(m, d, inv_d));
+}
+
+// d and 1 / d of a copy at h hertz: one IEEE divide each, per copy, voice and block
+__device__ __forceinline__ void blep_increment(double h, double rate, double& d, double& inv_d) {
+    d = fmin(fabs(h) / rate, 0.5);                                             // (a NaN h: fmin answers 0.5, and t is NaN anyway)
+    inv_d = 1.0 / d;
+}
+
 template <int KIND, typename OUT> __device__ __forceinline__ OUT osc_wave(double t) {
     if (KIND == SIG_OSC_SINE) {
         if (sizeof(OUT) == 4) return (OUT)osc_sine_f32(t);

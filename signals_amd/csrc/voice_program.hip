@@ -40,6 +40,9 @@
 #include "sig_biquad.h"
 #include "sig_bus_tile.h"
 #include "sig_noise.h"
+#if defined(SIG_BLEP_SKIP) && SIG_BLEP_SKIP
+#error "SIG_BLEP_SKIP is a tuning build of osc_bank.hip alone: the OscBlep handler's lanes were not examined for its ballot"
+#endif
 #include "sig_osc.h"
 #include "sig_table.h"
 
@@ -196,16 +199,18 @@ template <bool SMALL> struct VpLimits {
 // UNI: the OscUni instruction (unison oscillators, ext.py UnisonOsc): the mean of the copies of one waveform; a variant of its own once
 // more (never with BAND, PM, TAB or RES).  `tb` is then the variant's VpUnison: TABLES is whatever second kernel parameter the
 // variant has (VpTables, VpUnison) or VpNoTables
+// BLP: the OscBlep instruction (band-limited oscillators, ext.py BlepOsc) on top of UNI, whose copies and operands it shares: a flag
+// of its own, so that programs with OscUni alone keep the UNI variant's code (voice_program_blep_kernel has both handlers)
 // The "never with" above is the single-family variants'.  The MIXED variant (voice_program_mixed_kernel, reached only through
-// sig_voice_program_mixed) has all six flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
+// sig_voice_program_mixed) has all seven flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
 //   * RES on: every LowPass / HighPass slot is designed by vp_design_res at d = sqrt2 (`single` is off), which are vp_design's bits;
 //     band slots are neither `resonant` nor `plain` there and keep design_band2;
 //   * a run of band slots pairs from its start whatever stands next to it: bfirst[f] looks only at bfirst[f - 1], and a resonant or
 //     plain slot at f - 1 is never a band's first.  Two pairs cannot share f / 2 (that would take slots f, f + 1 and f + 1, f + 2);
-//   * the qreg scan reads the FilterQ words alone, the handlers in front of the switch (FilterQ, OscUni, Shape, OscTable) each test
+//   * the qreg scan reads the FilterQ words alone, the handlers in front of the switch (FilterQ, OscUni, OscBlep, Shape, OscTable) each test
 //     their own opcode and `continue`, so their order does not matter;
 //   * with no table in the launch tb.ptr[0] is null and nothing is staged (no dynamic LDS is asked for either).
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, typename TABLES>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, bool BLP, typename TABLES>
 __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
                                         [[maybe_unused]] const float* tab)
 {
@@ -622,6 +627,58 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                     continue;
                 }
             }
+            if constexpr (BLP) {                                               // OscBlep: OscUni's operands and copies, sig_osc_bank_blep's waveforms
+                if (op == SIG_VP_OSCBLEP) {
+                    // the OscUni handler with sig_osc::osc_blep (m by v_fract_f64, like the fused waveforms) per copy.  d = min(|h| / rate,
+                    // 0.5) and 1 / d are block-invariant too, and 4 x copies x VPT registers with h and q: recomputed per group, two
+                    // divides per copy and voice for the group's R rows; the rows multiply
+                    double sp[VPT];
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) sp[i] = 0.0;                 // (15: spread unplugged)
+                    if (ic < NP) {
+                        with_index<NP>(ic, [&](auto I) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) sp[i] = pr[decltype(I)::value][i];
+                        });
+                    }
+                    const int copies = tb.copies;
+                    with_index<NO>(ia, [&](auto I) {
+                        constexpr int S = decltype(I)::value;
+                        for (int u = 0; u < copies; ++u) {
+                            const double du = tb.detune[u], pu = tb.offset[u];
+                            double h[VPT], qu[VPT], d[VPT], inv_d[VPT];
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) {
+                                h[i] = ohz[S][i] * (1.0 + sp[i] * du);
+                                qu[i] = oph[S][i] + pu;
+                                sig_osc::blep_increment(h[i], a.rate, d[i], inv_d[i]);
+                            }
+                            auto add = [&](auto wave) {
+#pragma unroll
+                                for (int r = 0; r < R; ++r) {
+                                    const double qr = vp_pin(q[r]);
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) {
+                                        const double w = wave(qr * h[i] + qu[i], d[i], inv_d[i]);
+                                        acc[r][i] = (u == 0) ? w : acc[r][i] + w;
+                                    }
+                                }
+                            };
+                            switch (kind) {                                    // (Sine is refused by the entry)
+                                case SIG_OSC_SAWTOOTH: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_SAWTOOTH, true>(t, d, v); }); break;
+                                case SIG_OSC_SQUARE: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_SQUARE, true>(t, d, v); }); break;
+                                default: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_TRIANGLE, true>(t, d, v); }); break;
+                            }
+                        }
+                        const double count = (double)copies;
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
+                    });
+                    continue;
+                }
+            }
             if constexpr (TAB) {
                 // the column of table slot ib that parameter slot ic selects, per voice: its first float in `tab`
                 auto columns = [&](int (&col)[VPT], int& TT) {
@@ -966,7 +1023,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #ifndef SIG_VP_WAVES1
 #define SIG_VP_WAVES1 3
 #endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, typename TABLES>
+template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, bool BLP, typename TABLES>
 __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
 {
     constexpr bool BUS = C > 0;
@@ -986,7 +1043,7 @@ __device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb
     }
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES, UNI>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
+    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES, UNI, BLP>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
     if constexpr (BUS) {
         if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
     }
@@ -1011,6 +1068,9 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 #ifndef SIG_VP_S_UNI
 #define SIG_VP_S_UNI 0                     // 1: the program has an OscUni word, the kernel takes the copies as a second parameter
 #endif
+#ifndef SIG_VP_S_BLEP
+#define SIG_VP_S_BLEP 0                    // 1: the program has an OscBlep word (with -DSIG_VP_S_UNI=1: the same copies parameter)
+#endif
 #ifndef SIG_VP_S_MIXED
 #define SIG_VP_S_MIXED 0                   // 1: the program combines two or more of Band, OscPM, OscTable / Shape, FilterQ, OscUni; the kernel takes a VpMixed
 #endif
@@ -1032,8 +1092,10 @@ void sig_vp_specialised(VpArgs a)
 #endif
     static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
-    constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI);
-    static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni word is built with -DSIG_VP_S_UNI=1, any other without");
+    constexpr bool kBlep = vp_static_has(SIG_VP_OSCBLEP);
+    constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI) || kBlep;               // (one family: OscBlep reads OscUni's copies)
+    static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni or an OscBlep word is built with -DSIG_VP_S_UNI=1, any other without");
+    static_assert(kBlep == (SIG_VP_S_BLEP != 0), "a program with an OscBlep word is built with -DSIG_VP_S_BLEP=1, any other without");
     constexpr int kFamilies = (int)kBand + (int)kPm + (int)kTab + (int)kRes + (int)kUni;
     static_assert((kFamilies >= 2) == (SIG_VP_S_MIXED != 0), "a program with two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni is built with -DSIG_VP_S_MIXED=1, any other without");
 #if !SIG_VP_S_MIXED
@@ -1042,13 +1104,13 @@ void sig_vp_specialised(VpArgs a)
     static_assert(!(kBand && kPm) && !(kTab && (kBand || kPm)), "Band, OscPM and OscTable / Shape: no variant has two of them");
 #endif
 #if SIG_VP_S_MIXED
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, kTab, kShape, kRes, kUni>(a, mx);      // exactly the families the program has
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, kTab, kShape, kRes, kUni, kBlep>(a, mx);      // exactly the families the program has
 #elif SIG_VP_S_TAB
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false, false>(a, tb);
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false, false, false>(a, tb);
 #elif SIG_VP_S_UNI
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, false, false, false, false, false, true>(a, un);
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, false, false, false, false, false, true, kBlep>(a, un);
 #else
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes, false>(a, VpNoTables{});
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes, false, false>(a, VpNoTables{});
 #endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
@@ -1062,38 +1124,44 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
 template <int VPT, bool SMALL, int C, bool BAND, bool PM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false, false>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false, false, false>(a, VpNoTables{});
 }
 // the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false, false>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false, false, false>(a, tb);
 }
 // the TAB variant with the Shape instruction (programs with a waveshaper, with or without a wavetable oscillator)
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_shape_kernel(VpArgs a, VpTables tb)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false, false>(a, tb);
+    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false, false, false>(a, tb);
 }
 // the RES variant (never with BAND, PM or TAB): programs with a resonant filter, whose design reads q
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_res_kernel(VpArgs a)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true, false>(a, VpNoTables{});
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true, false, false>(a, VpNoTables{});
 }
 // the UNI variant (never with BAND, PM, TAB or RES): a kernel of its own, whose second parameter carries the copies
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_unison_kernel(VpArgs a, VpUnison un)
 {
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true>(a, un);
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true, false>(a, un);
+}
+// the UNI variant with the OscBlep instruction (programs with a band-limited oscillator, with or without a plain unison one)
+template <int VPT, bool SMALL, int C>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_blep_kernel(VpArgs a, VpUnison un)
+{
+    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true, true>(a, un);
 }
 // the MIXED variant: every family at once, for programs that combine two or more of them (sig_voice_program_mixed only); its
 // second parameter carries the tables and the copies
 template <int VPT, bool SMALL, int C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_mixed_kernel(VpArgs a, VpMixed mx)
 {
-    vp_kernel_body<VPT, SMALL, C, true, true, true, true, true, true>(a, mx);
+    vp_kernel_body<VPT, SMALL, C, true, true, true, true, true, true, true>(a, mx);
 }
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
@@ -1109,8 +1177,8 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI) && x.c == -1) ? 15 : x.c;       // (no select / no q / no spread: a slot number no register file has)
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCUNI && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
+        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI || x.op == SIG_VP_OSCBLEP) && x.c == -1) ? 15 : x.c;       // (no select / no q / no spread: a slot number no register file has)
+        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
             return false;
         code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
     }
@@ -1127,7 +1195,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res, uni; };
+struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res, uni, blep; };
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
@@ -1212,6 +1280,17 @@ int vp_launch_unison_sink(const VpArgs& a, const VpUnison& un, int C, unsigned n
 }
 
 template <int VPT, bool SMALL>
+int vp_launch_blep_sink(const VpArgs& a, const VpUnison& un, int C, unsigned nwg, hipStream_t s) {
+    switch (C) {
+        case 0: voice_program_blep_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a, un); break;
+        case 1: voice_program_blep_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a, un); break;
+        case 2: voice_program_blep_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a, un); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return sig_launch_status();
+}
+
+template <int VPT, bool SMALL>
 int vp_launch_mixed_sink(const VpArgs& a, const VpMixed& mx, int C, unsigned nwg, size_t lds, hipStream_t s) {
     switch (C) {
         case 0: voice_program_mixed_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, mx); break;
@@ -1230,6 +1309,7 @@ int vp_launch_file(const VpArgs& a, const VpTables& tb, const VpUnison& un, cons
     // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter or a unison oscillator with none
     // of them nor with each other: refused by every entry but sig_voice_program_mixed, whose combined programs run the MIXED variant)
     if (vp_families(n) >= 2) return small_file ? vp_launch_mixed_sink<VPT, true>(a, mx, C, nwg, lds, s) : vp_launch_mixed_sink<VPT, false>(a, mx, C, nwg, lds, s);
+    if (n.blep) return small_file ? vp_launch_blep_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_blep_sink<VPT, false>(a, un, C, nwg, s);
     if (n.uni) return small_file ? vp_launch_unison_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_unison_sink<VPT, false>(a, un, C, nwg, s);
     if (n.res) return small_file ? vp_launch_res_sink<VPT, true>(a, C, nwg, s) : vp_launch_res_sink<VPT, false>(a, C, nwg, s);
     if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
@@ -1342,7 +1422,7 @@ static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t posi
         if (!r.ptr) return optional;
         return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
     };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false, false};
+    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false, false, false};
     // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
     const int n_tables = tables ? tables->n_tables : 0;
     SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
@@ -1358,8 +1438,8 @@ static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t posi
     a.n_ins = P.n_ins;
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCUNI && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
-                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI) ? -1 : 0) && x.c <= 15);
+        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI || x.op == SIG_VP_OSCBLEP) ? -1 : 0) && x.c <= 15);
         switch (x.op) {
             case SIG_VP_OSCTABLE:
                 SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
@@ -1372,6 +1452,10 @@ static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t posi
             case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
             case SIG_VP_OSCUNI:
                 SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params && x.kind <= SIG_OSC_TRIANGLE);
+                break;
+            case SIG_VP_OSCBLEP:                                               // OscUni's operands; no Sine
+                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params &&
+                              x.kind >= SIG_OSC_SQUARE && x.kind <= SIG_OSC_TRIANGLE);
                 break;
             case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
@@ -1388,6 +1472,7 @@ static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t posi
         if (x.op == SIG_VP_SHAPE) need.shape = true;
         if (x.op == SIG_VP_FILTERQ) need.res = true;
         if (x.op == SIG_VP_OSCUNI) need.uni = true;
+        if (x.op == SIG_VP_OSCBLEP) need.uni = need.blep = true;       // (the unison family: the same copies, the same exclusions)
     }
     if (!allow_mixed) {
         SIG_CHECK_ARG(!(need.uni && (need.band || need.pm || need.table || need.res)));

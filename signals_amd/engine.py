@@ -886,14 +886,16 @@ class _Batch:
         return self._osc_launch(node, 'osc_bank_table', bank, (hertz, phase, select), hist, rows, kind='Table')
 
     def _sched_unison(self, node, channels, hist, rows):
-        """a unison oscillator: one sig_osc_bank_unison launch, per-block hertz / phase / spread rows when one is modulated; the copies
-        go with the launch by value, as the node's state holds them now"""
+        """a unison oscillator: one sig_osc_bank_unison launch (sig_osc_bank_blep for a band-limited one, ext.BlepOsc), per-block
+        hertz / phase / spread rows when one is modulated; the copies go with the launch by value, as the node's state holds them now"""
         hertz, phase, spread = (self._control(p, p.name) for p in (node.hertz, node.phase, node.spread))
         copies = node.host_copies()
+        label = 'osc_bank_blep' if node.bandlimited() else 'osc_bank_unison'
+        entry = getattr(_native, label)
 
         def bank(kind, position, rate, hertz, phase, spread, out, **kw):
-            return _native.osc_bank_unison(kind, position, rate, hertz, phase, spread, copies, out, **kw)
-        return self._osc_launch(node, 'osc_bank_unison', bank, (hertz, phase, spread), hist, rows)
+            return entry(kind, position, rate, hertz, phase, spread, copies, out, **kw)
+        return self._osc_launch(node, label, bank, (hertz, phase, spread), hist, rows)
 
     def _sched_shaper(self, node, channels, hist, rows):
         """a waveshaper: one sig_shaper_table launch over its input's rows (history rows included when a filter reads it), scheduled
@@ -2042,7 +2044,8 @@ class _VoiceProgram:
                 raise _NoProgram('two unison oscillators with distinct copies arrays: the launch carries one')
             self.unison = self.unison or n
             spread = -1 if _ctl_unplugged(n.spread) else self._param(self._control(n.spread, below))
-            self.code.append(('OscUni', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, spread))
+            word = 'OscBlep' if n.bandlimited() else 'OscUni'                  # (ext.BlepOsc: the same operands, the band-limited waveforms)
+            self.code.append((word, _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, spread))
             depth = 0
         elif isinstance(n, ext.Shaper):
             depth = self._emit(n.input.sig, below)                             # the input's sample: in the accumulator
@@ -2254,6 +2257,9 @@ class _VoiceProgram:
         Unison oscillators (OscUni) take the program under the same rule: seven saws per voice under a bus run at 0.33 T interpreted
         against 0.28 T per node, 0.27 against 0.19 T behind a LowPass (tools/time_unison.py) -- a narrower
         margin than the other oscillators', since U copies of f64 work per sample bound both routes.
+        Band-limited oscillators (OscBlep) keep OscUni's rule: one copy under a bus 0.46 T interpreted against 0.43 T per node, 0.35
+        against 0.24 T behind a LowPass; seven copies 0.132 against 0.122 T behind a LowPass, but 0.155 against 0.156-0.158 T under a
+        bare bus (three runs): there the rule costs 1-2 %, which is accepted (tools/time_blep.py).
         Mixed programs (two or more of the families of _native.VP_FAMILIES; only compiled with `mixed_programs=True`) take the program
         under the same rule: measured (tools/time_mixed.py, 1024 voices, stereo bus, N = 256, three routes in alternation, median of 7
         windows of 0.5 s, attached kernels switched off for the interpreter) the interpreter's mixed variant runs UnisonSawtooth ->

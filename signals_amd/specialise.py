@@ -54,7 +54,8 @@ def flags(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, 
     ext = int(any(op in _native.VP_EXT_OPS for op, *_ in code))                  # Amp, Adsr, Noise: the extended handlers
     more = ['-DSIG_VP_S_TAB=1'] if any(op in _native.VP_TABLE_OPS for op, *_ in code) else []   # (the tables: a second kernel parameter)
     more += ['-DSIG_VP_S_RES=1'] if any(op in _native.VP_RES_OPS for op, *_ in code) else []    # (FilterQ: the resonant design)
-    more += ['-DSIG_VP_S_UNI=1'] if any(op in _native.VP_UNI_OPS for op, *_ in code) else []    # (OscUni: the copies, a second kernel parameter; run-time values)
+    more += ['-DSIG_VP_S_UNI=1'] if any(op in _native.VP_UNI_OPS + _native.VP_BLEP_OPS for op, *_ in code) else []    # (OscUni, OscBlep: the copies, a second kernel parameter; run-time values)
+    more += ['-DSIG_VP_S_BLEP=1'] if any(op in _native.VP_BLEP_OPS for op, *_ in code) else []   # (OscBlep: the band-limited handler)
     # two or more families: the second kernel parameter carries tables and copies together, the kernel has exactly the families of the
     # program.  (Appended last, and only then: the list -- and with it the cache key -- of every other program is what it was)
     more += ['-DSIG_VP_S_MIXED=1'] if len(_native.vp_families(code)) >= 2 else []
