@@ -743,6 +743,13 @@ int sig_voice_program_set_tuning(int32_t voices_per_lane, int32_t blocks_per_lan
 int sig_voice_program_geometry(int32_t voices, int32_t block_frames, int32_t nblocks, int32_t context, int32_t depth,
                                int32_t bus_channels, int32_t store_aligned, int32_t specialised,
                                int32_t* voices_per_lane, int32_t* blocks_per_lane);
+/* Introspection, no device work: the interpreter variant sig_voice_program (and _ex, _unison, _mixed) launches for a program --
+ * `family`: the one variant that has every extension word of the program, or MIXED for a program with words of two or more of
+ * band, pm, table / shape, resonant and unison / blep -- and whether the program fits the small register file (1) or takes the full
+ * one (0).  Reads the words and the slot counts of `program` (n_ins, ins, n_oscs, n_params, n_filters, n_temps), not its rows. */
+enum { SIG_VP_FAMILY_PLAIN = 0, SIG_VP_FAMILY_BAND = 1, SIG_VP_FAMILY_PM = 2, SIG_VP_FAMILY_TABLE = 3, SIG_VP_FAMILY_SHAPE = 4,
+       SIG_VP_FAMILY_RESONANT = 5, SIG_VP_FAMILY_UNISON = 6, SIG_VP_FAMILY_BLEP = 7, SIG_VP_FAMILY_MIXED = 8 };
+int sig_voice_program_variant(const sig_voice_program_t* program, int32_t* family, int32_t* small_file);
 /* SPECIALISED kernels.  The interpreter's source (signals_amd/csrc/voice_program.hip) built once more as a gfx950 code object
  * with ONE program as a compile-time constant -- macros SIG_VP_STATIC_CODE={words}, SIG_VP_S_NF / _NO / _NP / _NT / _EXT (the
  * register file: filter, oscillator, parameter, temporary slots; Amp / ADSR / White enabled), SIG_VP_STATIC_VPT, SIG_VP_STATIC_C,

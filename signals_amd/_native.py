@@ -62,6 +62,7 @@ VP_MAX_UNISON = 1                           # SIG_VP_MAX_UNISON: unison slots of
 # the families of which a single-family interpreter variant (and sig_voice_program, _ex, _unison) has at most one; a program with two
 # or more of them is a MIXED program (sig_voice_program_mixed, SIG_VP_S_MIXED)
 VP_FAMILIES = {'band': ('Band',), 'pm': ('OscPM',), 'table': VP_TABLE_OPS, 'resonant': VP_RES_OPS, 'unison': VP_UNI_OPS}
+VP_VARIANTS = ('plain', 'band', 'pm', 'table', 'shape', 'resonant', 'unison', 'blep', 'mixed')    # SIG_VP_FAMILY_*: the interpreter's variants (`voice_program_variant`)
 UNISON_MAX_COPIES = 16                      # SIG_UNISON_MAX_COPIES: copies of a unison oscillator (ext.py UnisonOsc)
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
 
@@ -177,6 +178,7 @@ def _argtypes() -> dict:
                                    + [ctypes.POINTER(VpTablesT), ctypes.POINTER(VpUnisonT)],
         'sig_voice_program_set_tuning': [i32, i32],
         'sig_voice_program_geometry': [i32, i32, i32, i32, i32, i32, i32, i32, p32, p32],
+        'sig_voice_program_variant': [ctypes.POINTER(VoiceProgramT), p32, p32],
         'sig_voice_program_args_size': [],
         'sig_voice_program_attach': [ctypes.POINTER(VoiceProgramT), i32, i32, ctypes.c_char_p],
         'sig_voice_program_detach_all': [],
@@ -1177,6 +1179,16 @@ def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context
     _check(lib().sig_voice_program_geometry(voices, block_frames, nblocks, context, depth, bus_channels, int(store_aligned),
                                             1 if specialised else 0, ctypes.byref(vpt), ctypes.byref(span)), 'sig_voice_program_geometry')
     return vpt.value, span.value
+
+
+def voice_program_variant(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int) -> tuple:
+    """(family, small_file): the interpreter variant (a name of VP_VARIANTS) sig_voice_program launches for this program and whether it
+    runs in the small register file (introspection, no device work)"""
+    P = _program_struct(code)
+    P.n_oscs, P.n_params, P.n_filters, P.n_temps = n_oscs, n_params, n_filters, n_temps
+    family, small = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    _check(lib().sig_voice_program_variant(ctypes.byref(P), ctypes.byref(family), ctypes.byref(small)), 'sig_voice_program_variant')
+    return VP_VARIANTS[family.value], bool(small.value)
 
 
 def voice_program_attach(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, voices_per_lane: int,

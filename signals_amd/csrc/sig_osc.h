@@ -148,7 +148,7 @@ template <int KIND> __device__ __forceinline__ double osc_wave_fused(double t) {
 // The two windows exclude each other for d <= 0.5.  A NaN m takes none.
 // SIG_BLEP_SKIP=1 is a tuning build of osc_bank.hip ALONE (FILE=osc_bank.hip tools/build_variant.sh): the residual behind a
 // wave-uniform branch, skipped where no lane of the wave is in a window.  The ballot needs every lane of the wave active, which
-// holds in osc_bank_blep_kernel (its only exits are wave-uniform) and was not examined for the program handlers: voice_program.hip
+// holds in osc_bank_blep_kernel (its only exits are wave-uniform) and was not examined for the program handlers: sig_vp_machine.h
 // refuses the macro.  Measured against the selects and not taken: DESIGN.md section 7.
 #ifndef SIG_BLEP_SKIP
 #define SIG_BLEP_SKIP 0

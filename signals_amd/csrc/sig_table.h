@@ -1,5 +1,5 @@
 // A (T, W) float32 table held in LDS: what the wavetable oscillator (osc_bank.hip), the waveshaper (shaper.hip) and the table
-// variant of the voice program (voice_program.hip) share.
+// variant of the voice program (sig_vp_machine.h) share.
 // Layout: column-major, S = T + 1 floats per column -- entry (i, w) at tab[w * S + i] -- and the guard entry tab[w * S + T] =
 // tab[w * S + 0].  A linear interpolation reads its two operands (i, i + 1) of one column as ONE paired access at one address; the
 // guard lets an oscillator's last segment wrap without a second mask (the shaper never reaches it: its last segment ends at T - 1);

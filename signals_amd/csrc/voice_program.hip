@@ -1,1058 +1,21 @@
-// A whole frame-rate voice graph in ONE launch, gfx950: the general form of the fused voice kernels.
+// The voice program's HOST half: tuning, attached images, geometry, validation, launch and the C entries of the accumulator
+// machine in sig_vp_machine.h (read that first).  The interpreter's kernels live one family per file (vp_<family>.hip) and are
+// reached through sig_vp_launch.h; this file instantiates none of them.
 //
-// The fused kernels of sig_fused_*.h / fused_cascade.hip each cover one graph shape (Filter(Osc), Filter(Filter(Osc)) ...).
-// Everything else -- an Amp or a Mix behind a filter, RingMod of two filtered voices, three filters in series, block-rate
-// FM together with a second oscillator, blocks shorter than the filter context -- ran one kernel per node (24+ B per
-// voice-sample through HBM) or, for short blocks, the eager pull path (~150 us per block).  Here the per-voice graph is
-// compiled on the host into a short straight-line program for an ACCUMULATOR MACHINE and interpreted per row by every
-// lane for its own voices (lanes = voices, like the walkers): the accumulator and a few temporaries live in VGPRs, the
-// program word of instruction pc sits in lane pc of one VGPR and is fetched with v_readlane (a wave-uniform scalar), the
-// dispatch is a scalar compare chain.  State arrays (filter slots, oscillator slots, parameter registers, temporaries)
-// are indexed by a wave-uniform slot number through a compile-time switch, so they stay in registers.
-//
-// What makes one machine enough for every shape is the reference's block structure, reproduced as a sequence of blocks:
-//   * a filter answers a block from ZERO state over [<=100 context rows | block] (CritFilter._filter, fx.py:85-106);
-//   * with blocks longer than the context, the context rows in front of block j are the input's rows of block j - 1: the
-//     input keeps its previous block cached and the context request is a slice of it (BlockCachingEmitter,
-//     chain/__init__.py:431-442) -- for a filter input that block was itself cold-started 100 rows before block j - 1;
-//   * every node reads its control ports once per block, at the block's position (forward_at_block_rate,
-//     chain/__init__.py:305-306).
-// So every filter slot carries TWO recurrences: the CURRENT block's chain, and -- over the last min(100, .) rows of a
-// block -- the NEXT block's chain, cold-started there on the same input (the current block's values, which is exactly
-// what the cache serves as context) with the next block's design.  At a block boundary next becomes current.  A lane
-// that starts its span at block b first re-walks the D - 1 blocks in front of it (D = filters in series) plus 100 rows:
-// a filter at level l of the cascade is exact from block b - D + l on (induction over levels), so level D is exact from
-// block b.  In front of the launch those are the previous render's blocks, or on a fresh graph the virtual 100-row
-// blocks the reference's context requests create ([p - 100, p) answered as a block of its own, controls read at p - 100).
-// Blocks SHORTER than the context (PortAudio callbacks of 32 or 64 frames): a context request then lies in no single
-// cached block, and the reference answers it as a block of its own for EVERY block -- each output block is walked on its
-// own behind its virtual block (controls read at max(p - 100, 0)); two filters in series at most in that mode.
-//
-// Arithmetic: f64 throughout, exact per-row phase t = n / rate * hertz + phase (osc.py:32, one IEEE divide per row shared
-// by the wave), Butterworth design per block in-kernel (sig_biquad.h), b0-normalised DF2T recurrence (4 FMAs + 1).  No
-// float32 rounding between nodes: closer to the f64 reference than the per-node schedule; 1e-6 parity by test.
+// Built with -DSIG_VP_STATIC_CODE={words} (signals_amd/specialise.py) this file is instead ONE kernel: the machine specialised
+// for one program, below.
 #include <cstring>
 #include <mutex>
-#include <type_traits>
+#include <tuple>
 #include <vector>
 
-#include "sig_adsr.h"
-#include "sig_biquad.h"
-#include "sig_bus_tile.h"
-#include "sig_noise.h"
-#if defined(SIG_BLEP_SKIP) && SIG_BLEP_SKIP
-#error "SIG_BLEP_SKIP is a tuning build of osc_bank.hip alone: the OscBlep handler's lanes were not examined for its ballot"
-#endif
-#include "sig_osc.h"
-#include "sig_table.h"
-
-namespace {
-
-using sig_biquad::Biquad;
-using sig_bus::kTileStride;
-
-constexpr int kMaxIns = SIG_VP_MAX_INS;
-#ifndef SIG_VP_ROWS
-#define SIG_VP_ROWS 8
-#endif
-constexpr int kRowGroup = SIG_VP_ROWS;     // the interpreter runs every instruction for this many consecutive rows at a time: its dispatch
-                                           // (fetch, decode, two scalar switches) is paid once per group, and a handler has rows x voices
-                                           // independent evaluations to overlap
-
-struct Rows { const double* ptr; int cs; int rows; };      // (rows, V | 1) float64: rows == 1 holds for every block
-
-struct VpArgs {
-    double rate; int64_t position; int N, K, ctx, voices;
-    int n_ins; uint32_t code[kMaxIns];                       // op | kind << 5 | a << 8 | b << 12 | c << 16
-    int n_oscs; Rows hertz[SIG_VP_MAX_OSCS], phase[SIG_VP_MAX_OSCS];
-    int n_params; Rows params[SIG_VP_MAX_PARAMS];
-    int n_filters; Rows cutoff[SIG_VP_MAX_FILTERS]; int ftype[SIG_VP_MAX_FILTERS]; int flevel[SIG_VP_MAX_FILTERS];
-    sig_env::AdsrRows adsr; int has_adsr;
-    uint64_t seeds[2];
-    int depth, hist, small, blocks_before; int64_t hist_pos[SIG_VP_MAX_HIST];
-    int span, voice_tiles;
-    float* out; int64_t out_ld;                              // store sink
-    const double* pan; int64_t pan_ld; double* partials; int64_t rows; float* bus_out; int64_t bus_out_ld;   // bus sink
-    int* status;
-};
-
-// The wavetables of the OscTable instruction: (T, W) float32, staged in LDS.  A kernel parameter of its own that only the TAB
-// variant has, so that the argument block -- and with it the code -- of every other instantiation is what it was without the op.
-struct VpTables { const float* ptr[SIG_VP_MAX_TABLES]; int T[SIG_VP_MAX_TABLES], W[SIG_VP_MAX_TABLES]; };
-struct VpNoTables {};
-// The copies of the OscUni instruction (unison oscillators, ext.py UnisonOsc): relative detune and phase offset per copy, by value.
-// Travels the way VpTables does -- a second kernel parameter that only the UNI variant has -- and for the same reason.  Wave-uniform:
-// the handler's loop count and both values are scalars.
-struct VpUnison { int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; };
-// Both at once, for the MIXED variant (programs that combine two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni): the
-// fields of VpTables followed by those of VpUnison.  The names are disjoint, so the handlers read tb.ptr / T / W and tb.copies /
-// detune / offset from it as they do from the one they were written for.
-struct VpMixed {
-    const float* ptr[SIG_VP_MAX_TABLES]; int T[SIG_VP_MAX_TABLES], W[SIG_VP_MAX_TABLES];
-    int copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES];
-};
-
-// f(integral_constant<int, i>) for a wave-uniform i < N: a scalar switch, so arrays indexed inside stay in registers
-template <int N, typename F>
-__device__ __forceinline__ void with_index(int i, F&& f) {
-    switch (i) {
-        case 0: if constexpr (N > 0) f(std::integral_constant<int, 0>{}); break;
-        case 1: if constexpr (N > 1) f(std::integral_constant<int, 1>{}); break;
-        case 2: if constexpr (N > 2) f(std::integral_constant<int, 2>{}); break;
-        case 3: if constexpr (N > 3) f(std::integral_constant<int, 3>{}); break;
-        case 4: if constexpr (N > 4) f(std::integral_constant<int, 4>{}); break;
-        case 5: if constexpr (N > 5) f(std::integral_constant<int, 5>{}); break;
-        case 6: if constexpr (N > 6) f(std::integral_constant<int, 6>{}); break;
-        case 7: if constexpr (N > 7) f(std::integral_constant<int, 7>{}); break;
-        default: break;
-    }
-}
-
-// An opaque copy of a wave-uniform double.  A handler's arithmetic on the row's n / rate and the slot's block-invariant
-// registers does not depend on the instruction counter, so the optimiser hoists it out of the instruction loop and evaluates
-// EVERY case of every slot once per row, unconditionally (measured: all four waveforms of all oscillator slots per row, ~10x
-// the work of the program itself and twice the registers).  Passing an input through an empty volatile asm pins the work to
-// the case that needs it.
-__device__ __forceinline__ double vp_pin(double x) {
-    asm volatile("" : "+s"(x));
-    return x;
-}
-
-// sig_biquad.h's design_butter2 with a light tangent: libm's tan() carries a Payne-Hanek reduction for huge arguments whose
-// temporaries set the register budget of the whole kernel (+110 VGPRs, measured), and the argument here is pi Wn / 2 with
-// Wn in (0, 1): tan = sin / cos from the odd polynomial of sig_osc.h on [0, pi/2], cos(x) = sin(pi/2 - x) with pi/2 as hi + lo.
-// Coefficients within 1e-15 (relative) of the libm form.
-struct VpTan {                                              // tan(x), x in [0, pi/2]
-    __device__ __forceinline__ double operator()(double x) const {
-        const double xc = (1.5707963267948966 - x) + 6.123233995736766e-17;
-        return sig_osc::sin_poly(x) / sig_osc::sin_poly(xc);
-    }
-};
-__device__ __forceinline__ bool vp_design(int type, double cutoff, double rate, Biquad& q) {
-    double wn = cutoff / (rate * 0.5);                      // scaled_crit /= rate / 2  (fx.py:99-101)
-    wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
-    const bool bad = !(wn > 0.0 && wn < 1.0);               // scipy raises (NaN too)
-    const double x = sig_biquad::kPi * wn / 2.0;
-    const double k = VpTan{}(x);
-    const double k2 = k * k;
-    const double nrm = 1.0 / (1.0 + sig_biquad::kSqrt2 * k + k2);
-    q.b0 = (type == SIG_FILT_LOWPASS) ? k2 * nrm : nrm;
-    q.a1 = 2.0 * (k2 - 1.0) * nrm;
-    q.a2 = (1.0 - sig_biquad::kSqrt2 * k + k2) * nrm;
-    if (bad) { q.b0 = q.a1 = q.a2 = __builtin_nan(""); }
-    q.b1 = q.b2 = 0.0;                                      // (the recurrence is b0-normalised: b = b0 [1, +-2, 1])
-    return !bad;
-}
-
-// vp_design with the damping as an argument: the resonant low-pass / high-pass of chain/ext.py (sig_biquad.h design_resonant2 with the
-// light tangent), d = 1 / q -- one divide more per voice and block -- or sqrt2 for a Butterworth slot of the same program, which
-// then gets vp_design's bits.  `lowpass`: the slot's response; `q_ok`: the resonance was finite and > 0 (or unplugged).  Returns 0 or
-// the status bits of what was refused.
-__device__ __forceinline__ int vp_design_res(bool lowpass, double cutoff, double d, bool q_ok, double rate, Biquad& q) {
-    double wn = cutoff / (rate * 0.5);
-    wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
-    const int bad = (!(wn > 0.0 && wn < 1.0) ? SIG_STATUS_BAD_CUTOFF : 0) | (q_ok ? 0 : SIG_STATUS_BAD_RESONANCE);
-    const double x = sig_biquad::kPi * wn / 2.0;
-    const double k = VpTan{}(x);
-    const double k2 = k * k;
-    const double nrm = 1.0 / (1.0 + d * k + k2);
-    q.b0 = lowpass ? k2 * nrm : nrm;
-    q.a1 = 2.0 * (k2 - 1.0) * nrm;
-    q.a2 = (1.0 - d * k + k2) * nrm;
-    if (bad) { q.b0 = q.a1 = q.a2 = __builtin_nan(""); }
-    q.b1 = q.b2 = 0.0;
-    return bad;
-}
-
-__device__ __noinline__ double vp_amp(double x, double e) { return copysign(pow(x, e), x); }   // fx.py:60 (kept out of line: pow is long)
-
-// Register-file sizes per variant (the host picks the smallest variant a program fits).  SMALL: two filter slots, three
-// oscillator slots, four parameter registers, one temporary (a temporary is a whole row group: 8 rows x 2 voices = 32 VGPRs), no Amp / ADSR / White -- the common synthesiser voice; its
-// state fits two waves per SIMD at two voices per lane, which the interpreter's scalar dispatch needs to hide its branches.
-// The full register file (four filters, four oscillators, eight parameters, four temporaries, every instruction) runs at one.
-template <bool SMALL> struct VpLimits {
-#ifndef SIG_VP_S_NF
-#define SIG_VP_S_NF 2
-#define SIG_VP_S_NO 3
-#define SIG_VP_S_NP 4
-#define SIG_VP_S_NT 1
-#endif
-    static constexpr int NF = SMALL ? SIG_VP_S_NF : 4, NO = SMALL ? SIG_VP_S_NO : 4, NP = SMALL ? SIG_VP_S_NP : 8, NT = SMALL ? SIG_VP_S_NT : 4;
-#ifdef SIG_VP_S_EXT
-    static constexpr bool EXT = !SMALL || (SIG_VP_S_EXT != 0);
-#else
-    static constexpr bool EXT = !SMALL;
-#endif
-};
-
-// C == 0: store (float) acc to a.out; C > 0: C bus channels into a.partials.  EXT: Amp, ADSR and White instructions.
-// BAND: the Band instruction (band filters' per-voice middle taps and their design; a variant of its own, so that programs
-// without one keep the registers they had -- the band state and its inlined design cost the SMALL file ~200 B of scratch per lane)
-// PM: the OscPM instruction (phase-modulation carriers), a variant of its own for the same reason
-// TAB: the OscTable and Shape instructions (wavetable oscillators and waveshapers, ext.py Wavetable / Shaper), likewise; `tab`: the launch's tables in LDS, each
-// column-major with T + 1 floats per column (the guard entry [T] = [0], sig_table.h), table 1 behind table 0
-// SHP: the Shape instruction on top of TAB, a variant of its own once more: with the handler in the one TAB variant the SMALL
-// table kernels went from 260-312 to 412-472 B of scratch per lane, which wavetable-only programs would have paid
-// RES: the FilterQ instruction (resonant low-pass / high-pass, ext.py ResonantFilter): slots of type SIG_FILT_RES_* whose design reads
-// a second block-rate control, q, from the parameter rows the word names; a variant of its own (never with BAND, PM or TAB), so that
-// programs without the word keep their registers and scratch.  Filter words run in it too
-// UNI: the OscUni instruction (unison oscillators, ext.py UnisonOsc): the mean of the copies of one waveform; a variant of its own once
-// more (never with BAND, PM, TAB or RES).  `tb` is then the variant's VpUnison: TABLES is whatever second kernel parameter the
-// variant has (VpTables, VpUnison) or VpNoTables
-// BLP: the OscBlep instruction (band-limited oscillators, ext.py BlepOsc) on top of UNI, whose copies and operands it shares: a flag
-// of its own, so that programs with OscUni alone keep the UNI variant's code (voice_program_blep_kernel has both handlers)
-// The "never with" above is the single-family variants'.  The MIXED variant (voice_program_mixed_kernel, reached only through
-// sig_voice_program_mixed) has all seven flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
-//   * RES on: every LowPass / HighPass slot is designed by vp_design_res at d = sqrt2 (`single` is off), which are vp_design's bits;
-//     band slots are neither `resonant` nor `plain` there and keep design_band2;
-//   * a run of band slots pairs from its start whatever stands next to it: bfirst[f] looks only at bfirst[f - 1], and a resonant or
-//     plain slot at f - 1 is never a band's first.  Two pairs cannot share f / 2 (that would take slots f, f + 1 and f + 1, f + 2);
-//   * the qreg scan reads the FilterQ words alone, the handlers in front of the switch (FilterQ, OscUni, OscBlep, Shape, OscTable) each test
-//     their own opcode and `continue`, so their order does not matter;
-//   * with no table in the launch tb.ptr[0] is null and nothing is staged (no dynamic LDS is asked for either).
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, bool BLP, typename TABLES>
-__device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane, int wave, [[maybe_unused]] const TABLES& tb,
-                                        [[maybe_unused]] const float* tab)
-{
-    constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
-    constexpr bool BUS = C > 0;
-    constexpr int CC = BUS ? C : 1;
-    using L = VpLimits<SMALL>;
-    constexpr int NF = L::NF, NO = L::NO, NP = L::NP, NT = L::NT;
-    constexpr bool EXT = L::EXT;
-    using Vec = typename sig_vec::OutVec<VPT>::type;
-    const int64_t item = (int64_t)blockIdx.x * 4 + wave;
-    const int vt = (int)(item % a.voice_tiles);
-    const int64_t b_first = (item / a.voice_tiles) * a.span;
-    if (b_first >= a.K) return;                                               // wave-uniform
-    const int nb = (int)((a.K - b_first < (int64_t)a.span) ? a.K - b_first : (int64_t)a.span);
-    const int v0 = (vt * SIG_WAVE + lane) * VPT;
-    const bool live0 = v0 < a.voices;
-    const int vc = live0 ? v0 : 0;
-    auto voice = [&](int i) { return (v0 + i < a.voices) ? v0 + i : vc; };     // dead voices shadow a live one (weight 0 / not stored)
-
-    // the program: word pc in lane pc
-    uint32_t codev = 0;
-#pragma unroll
-    for (int k = 0; k < kMaxIns; ++k) codev = (lane == k) ? a.code[k] : codev;
-
-    double acc[RG][VPT], T[NT > 0 ? NT : 1][RG][VPT], pr[NP][VPT], ohz[NO][VPT], oph[NO][VPT];
-    double z0[NF][VPT], z1[NF][VPT], w0[NF][VPT], w1[NF][VPT], na1[NF][VPT], na2[NF][VPT], fb0[NF][VPT], xa1[NF][VPT], xa2[NF][VPT];
-    double s2[NF];
-    // band filters (Band): two consecutive slots f, f + 1 -- the sections of butter(2, [low, high]) -- whose middle taps vary per
-    // voice and block: beta of the first section (current and next chains) in bq / xbq[f / 2]; the second's is -beta (bp) or beta
-    // (bs); the band's gain is the second slot's fb0.  A run of band slots pairs up from its start (the host emits them that way,
-    // sig_voice_program checks it)
-    constexpr int NB = NF / 2 > 0 ? NF / 2 : 1;
-    double bq[NB][VPT], xbq[NB][VPT];
-    bool bfirst[NF];
-    double wt[CC][VPT];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) bq[b][i] = xbq[b][i] = 0.0;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        const bool band = f < a.n_filters && (a.ftype[f] == SIG_FILT_BANDPASS || a.ftype[f] == SIG_FILT_BANDSTOP);
-        bfirst[f] = BAND && band && f + 1 < NF && !(f > 0 && bfirst[f > 0 ? f - 1 : 0]);
-        s2[f] = (f < a.n_filters && (a.ftype[f] == SIG_FILT_HIGHPASS || (RES && a.ftype[f] == SIG_FILT_RES_HIGHPASS))) ? -2.0 : 2.0;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) { z0[f][i] = z1[f][i] = w0[f][i] = w1[f][i] = 0.0; na1[f][i] = na2[f][i] = fb0[f][i] = xa1[f][i] = xa2[f][i] = 0.0; }
-    }
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-#pragma unroll
-        for (int r = 0; r < RG; ++r)
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) T[k][r][i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-#pragma unroll
-        for (int r = 0; r < RG; ++r) acc[r][i] = 0.0;
-#pragma unroll
-        for (int ch = 0; ch < CC; ++ch) wt[ch][i] = BUS ? ((v0 + i < a.voices) ? (a.pan ? a.pan[ch * a.pan_ld + voice(i)] : 1.0) : 0.0) : 1.0;
-    }
-
-    // RES: the parameter slot that holds filter slot f's q rows (-1: a Butterworth slot, or q unplugged), from the FilterQ words
-    [[maybe_unused]] int qreg[NF];
-    if constexpr (RES) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) qreg[f] = -1;
-        for (int k = 0; k < a.n_ins; ++k) {
-            const uint32_t w = a.code[k];                                      // (wave-uniform: the argument block)
-            if ((w & 31u) != (uint32_t)SIG_VP_FILTERQ) continue;
-            const int slot = (int)((w >> 8) & 15u), reg = (int)((w >> 16) & 15u);
-#pragma unroll
-            for (int f = 0; f < NF; ++f)
-                if (f == slot) qreg[f] = (reg < a.n_params) ? reg : -1;        // (15: unplugged)
-        }
-    }
-
-    // ---- per-block state: parameter registers, oscillator rows, filter designs
-    auto row_at = [&](const Rows& r, int64_t cri, int v) {
-        return r.ptr[(r.rows > 1 ? cri * (int64_t)(r.cs ? a.voices : 1) : 0) + (int64_t)v * r.cs];
-    };
-    bool params_loaded = false;
-    auto load_params = [&](int64_t cri) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-            if (k < a.n_params && (!params_loaded || a.params[k].rows > 1)) {
-#pragma unroll
-                for (int i = 0; i < VPT; ++i) pr[k][i] = row_at(a.params[k], cri, voice(i));
-            }
-#pragma unroll
-        for (int k = 0; k < NO; ++k)
-            if (k < a.n_oscs) {
-                if (!params_loaded || a.hertz[k].rows > 1) {
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) ohz[k][i] = row_at(a.hertz[k], cri, voice(i));
-                }
-                if (!params_loaded || a.phase[k].rows > 1) {
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) oph[k][i] = a.phase[k].ptr ? row_at(a.phase[k], cri, voice(i)) : 0.0;
-                }
-            }
-        params_loaded = true;
-    };
-    bool designed = false;                                                     // block-invariant designs are made once
-    auto design = [&](int64_t cri, int min_level, auto next_tag) {
-        constexpr bool NEXT = decltype(next_tag)::value;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            const int g = (f + 1 < NF) ? f + 1 : f;                            // the second slot of a band filter at f
-            if (BAND && f < a.n_filters && a.flevel[f] >= min_level && bfirst[f] && (!designed || a.cutoff[f].rows > 1 || a.cutoff[g].rows > 1)) {
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < VPT; ++i) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    Biquad q1, q2;
-                    double beta = 0.0;
-                    ok &= sig_biquad::design_band2<false>(a.ftype[f], row_at(a.cutoff[f], cri, voice(i)), row_at(a.cutoff[g], cri, voice(i)),
-                                                          a.rate, q1, q2, &beta, nullptr, VpTan{}) || !(v0 + i < a.voices);
-                    if (NEXT) { xa1[f][i] = -q1.a1; xa2[f][i] = -q1.a2; xa1[g][i] = -q2.a1; xa2[g][i] = -q2.a2; xbq[f / 2][i] = beta; }
-                    else { na1[f][i] = -q1.a1; na2[f][i] = -q1.a2; fb0[f][i] = 1.0; na1[g][i] = -q2.a1; na2[g][i] = -q2.a2; fb0[g][i] = q1.b0; bq[f / 2][i] = beta; }
-                    if (!NEXT && !designed) { xa1[f][i] = -q1.a1; xa2[f][i] = -q1.a2; xa1[g][i] = -q2.a1; xa2[g][i] = -q2.a2; xbq[f / 2][i] = beta; }
-                }
-                if (!ok && a.status) atomicOr(a.status, SIG_STATUS_BAD_CUTOFF);
-            }
-            if constexpr (RES) {                                               // every slot of this variant: vp_design_res, a Butterworth slot at d = sqrt2
-                const bool resonant = f < a.n_filters && (a.ftype[f] == SIG_FILT_RES_LOWPASS || a.ftype[f] == SIG_FILT_RES_HIGHPASS);
-                const bool plain = f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
-                const bool swept_q = resonant && qreg[f] >= 0 && a.params[qreg[f] >= 0 ? qreg[f] : 0].rows > 1;
-                if ((resonant || plain) && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1 || swept_q)) {
-                    const bool lowpass = a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_RES_LOWPASS;
-                    int bad = 0;
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        double d = sig_biquad::kSqrt2;
-                        bool q_ok = true;
-                        if (resonant && qreg[f] >= 0) {
-                            const double r = row_at(a.params[qreg[f]], cri, voice(i));
-                            q_ok = r > 0.0 && r < __builtin_inf();             // 0, negative, NaN, +-inf: refused
-                            d = 1.0 / r;
-                        }
-                        Biquad q;
-                        const int got = vp_design_res(lowpass, row_at(a.cutoff[f], cri, voice(i)), d, q_ok, a.rate, q);
-                        bad |= (v0 + i < a.voices) ? got : 0;                  // a dead (padding) lane never reports
-                        if (NEXT) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
-                        else { na1[f][i] = -q.a1; na2[f][i] = -q.a2; fb0[f][i] = q.b0; }
-                        if (!NEXT && !designed) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
-                    }
-                    if (bad && a.status) atomicOr(a.status, bad);
-                }
-            }
-            const bool single = !RES && f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
-            if (single && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1)) {
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < VPT; ++i) {
-                    __builtin_amdgcn_sched_barrier(0);                         // one design at a time: four interleaved tan() set the kernel's register budget
-                    Biquad q;
-                    ok &= vp_design(a.ftype[f], row_at(a.cutoff[f], cri, voice(i)), a.rate, q) || !(v0 + i < a.voices);
-                    if (NEXT) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
-                    else { na1[f][i] = -q.a1; na2[f][i] = -q.a2; fb0[f][i] = q.b0; }
-                    if (!NEXT && !designed) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
-                }
-                if (!ok && a.status) atomicOr(a.status, SIG_STATUS_BAD_CUTOFF);
-            }
-        }
-    };
-    auto start_next = [&](int64_t cri, int min_level) {                        // the next block's chains (of filters at that level of a cascade or deeper): zero state, its design
-        design(cri, min_level, std::true_type{});
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-            if (f < a.n_filters && a.flevel[f] >= min_level) {
-#pragma unroll
-                for (int i = 0; i < VPT; ++i) { w0[f][i] = 0.0; w1[f][i] = 0.0; }
-            }
-    };
-    auto enter_block = [&](int64_t cri) {                                      // next becomes current
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) { z0[f][i] = w0[f][i]; z1[f][i] = w1[f][i]; }
-        design(cri, 0, std::false_type{});
-        designed = true;
-    };
-
-    // ---- envelope (EXT): the voice's current linear stage, re-derived where a run of rows starts and where a stage ends
-    [[maybe_unused]] sig_env::Segment seg[EXT ? VPT : 1];
-    auto seed_envelope = [&](double t) {
-        if constexpr (EXT) {
-            if (a.has_adsr) {
-#pragma unroll
-                for (int i = 0; i < VPT; ++i) seg[i] = sig_env::segment_at(sig_env::load_voice(a.adsr, voice(i)), t);
-            }
-        }
-    };
-
-    float* dst = BUS ? nullptr : a.out + vc;
-    double* dstp = BUS ? a.partials + (int64_t)vt * a.rows * CC : nullptr;     // [tile][row][c]
-    sig_bus::PipelinedTile<CC> stage(tile, lane, dstp, b_first * a.N);
-
-    // ---- the block sequence of this span (see the header) as a list of STEPS: [load parameters] [next -> current] [start the
-    // next block's chains] then rows [from, to).  One loop, so that the row interpreter exists once in the code.
-    const int D = a.depth, H = a.hist;
-    const int ctx = (D > 0) ? a.ctx : 0;                                       // no filter: no context rows at all
-    // `warm_from`: the row from which the NEXT block's chains run too (their zero state and design are set up when the walk gets
-    // there); == to: none in this step
-    struct Step { bool load, enter, out, next0; int next_level; int64_t cri_load, cri_enter, cri_next, from, to, warm_from; };   // next0: the next chains start with the step, even an empty one
-    auto bpos = [&](int64_t j) -> int64_t { return j >= 0 ? a.position + j * (int64_t)a.N : a.hist_pos[H + j]; };   // j >= -H
-    auto cri = [&](int64_t j) -> int64_t { return j + H + 1; };                // control rows: [one in front | H blocks in front | K blocks]
-    int64_t j0 = b_first - (D > 1 ? D - 1 : 0);
-    if (j0 < -(int64_t)H) j0 = -(int64_t)H;
-    const int64_t j_end = b_first + nb;
-    int n_steps;
-    if (!a.small) n_steps = 1 + (int)(j_end - j0);
-    else n_steps = (D >= 2) ? 4 : 2;
-    auto make_step = [&](int t) {
-        Step st{false, false, false, false, 0, 0, 0, 0, 0, 0, 0};
-        if (!a.small) {
-            if (t == 0) {                                                      // the rows in front of the first block belong to the block before it
-                const int64_t s0 = bpos(j0);
-                const int64_t c0 = (s0 < (int64_t)ctx) ? s0 : (int64_t)ctx;
-                st.load = true; st.cri_load = cri(j0) - 1;
-                st.cri_next = cri(j0); st.next0 = true;
-                st.from = s0 - c0; st.to = s0; st.warm_from = st.from;
-                return st;
-            }
-            const int64_t j = j0 + (t - 1);
-            const int64_t s0 = bpos(j), e = bpos(j + 1);
-            int64_t cn = (j + 1 < j_end) ? ((e < (int64_t)ctx) ? e : (int64_t)ctx) : 0;     // the next block's context, inside this one
-            if (cn > e - s0) cn = e - s0;
-            st.out = j >= b_first;
-            st.enter = true; st.cri_enter = cri(j);
-            st.load = true; st.cri_load = cri(j);
-            st.cri_next = cri(j + 1);
-            st.from = s0; st.to = e; st.warm_from = e - cn;
-            return st;
-        }
-        // Blocks shorter than the context: every block behind its own virtual block [vp, p), vp = max(p - ctx, 0), whose
-        // controls are row b of the per-block arrays; the block's own are row K + b.  What feeds the LAST filter over the
-        // block's own rows is the oldest cached block of that input containing them: the input's reply to the `after`
-        // request made m = min((ctx - N) / N, blocks rendered before) blocks earlier, at q = p - m N (chain/__init__.py:
-        // 435-442: the first containing block in insertion order) -- a filter in it was cold-started min(ctx, q) rows before q,
-        // and everything in it read its controls at q (the caller evaluates those rows of the K + b group there).
-        const int64_t p = a.position + b_first * (int64_t)a.N;
-        const int64_t vp = (p > (int64_t)ctx) ? p - ctx : 0;
-        if (D < 2) {
-            if (t == 0) {                                                      // the virtual block: the whole of it is the block's context
-                st.load = true; st.cri_load = b_first;
-                st.cri_next = a.K + b_first; st.next0 = true;
-                st.from = vp; st.to = p; st.warm_from = vp;
-            } else {
-                st.enter = true; st.cri_enter = a.K + b_first;
-                st.load = true; st.cri_load = a.K + b_first;
-                st.from = p; st.to = p + a.N; st.warm_from = st.to; st.out = true;
-            }
-            return st;
-        }
-        const int64_t bg = (int64_t)a.blocks_before + b_first;                // blocks of this size rendered since the graph was fresh
-        int64_t m = (a.N > 0) ? (ctx - a.N) / a.N : 0;
-        if (m > bg - 1) m = bg - 1;
-        if (m < 0) m = 0;
-        const int64_t q = p - m * a.N;
-        const int64_t qc = q - ((q < (int64_t)ctx) ? q : (int64_t)ctx);        // where the inner filter of the block's own rows cold-starts
-        const int64_t c0 = (vp < (int64_t)ctx) ? vp : (int64_t)ctx;
-        const int64_t r0 = vp - c0;                                            // ... and where the virtual block's inner filter does
-        const int64_t r1 = (qc < r0) ? r0 : ((qc > vp) ? vp : qc);
-        if (t == 0) {                                                          // the virtual block's inner filter alone (current chains from zero)
-            st.enter = true; st.cri_enter = b_first;
-            st.load = true; st.cri_load = b_first;
-            st.from = r0; st.to = r1; st.warm_from = r1;
-        } else if (t == 1) {                                                   // + the inner filter of the block's own rows warms up
-            st.next_level = 1; st.cri_next = a.K + b_first; st.next0 = true;
-            st.from = r1; st.to = vp; st.warm_from = r1;
-        } else if (t == 2) {                                                   // the virtual block: the outer filter cold-starts on it
-            st.next_level = 2; st.cri_next = a.K + b_first; st.next0 = true;
-            st.from = vp; st.to = p; st.warm_from = vp;
-        } else {
-            st.enter = true; st.cri_enter = a.K + b_first;
-            st.load = true; st.cri_load = a.K + b_first;
-            st.from = p; st.to = p + a.N; st.warm_from = st.to; st.out = true;
-        }
-        return st;
-    };
-
-    // rows [from, to): every instruction of the program for a group of R consecutive rows at a time (R = RG, then single rows
-    // for what is left of the segment); WARM rows also advance the next block's chains
-    double q_lane = 0.0;
-    int64_t qbase = 0;
-    bool q_valid = false;
-    sig_bus::FoldedGroup<CC> folded(tile, lane, dstp);                         // whole groups of the bus sink: sums folded across lanes in registers
-    // one biquad section of filter slot F over the group's R rows, in place on the accumulator: DF2T of [1, beta, 1] / [1, a1, a2]
-    // (b0-normalised; `scale`: times the slot's b0 after).  beta(i) / xbeta(i): the current and next chains' middle taps
-    auto section = [&](auto I, int warm_r, auto rows_tag, auto beta, auto xbeta, bool scale) {
-        constexpr int F = decltype(I)::value;
-        constexpr int R = decltype(rows_tag)::value;
-        if (warm_r < R) {                                                      // wave-uniform: the next block's chain, on the same input rows
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (r >= warm_r) {                                             // (wave-uniform too: a group may straddle the first warm row)
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) {
-                        const double x = acc[r][i];
-                        const double yw = x + w0[F][i];
-                        w0[F][i] = fma(xa1[F][i], yw, fma(xbeta(i), x, w1[F][i]));
-                        w1[F][i] = fma(xa2[F][i], yw, x);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double x = acc[r][i];
-                const double y = x + z0[F][i];
-                z0[F][i] = fma(na1[F][i], y, fma(beta(i), x, z1[F][i]));
-                z1[F][i] = fma(na2[F][i], y, x);
-                acc[r][i] = scale ? fb0[F][i] * y : y;
-            }
-        }
-    };
-    auto group = [&](int64_t n, int warm_r, bool out, auto rows_tag) {        // warm_r: the first row of the group that also advances the next chains (R: none)
-        constexpr int R = decltype(rows_tag)::value;
-        if (!q_valid || n < qbase || n + R > qbase + SIG_WAVE) {                // n / rate (IEEE divide) for 64 rows at a time, one per lane
-            qbase = n;
-            q_lane = (double)(qbase + lane) / a.rate;
-            q_valid = true;
-        }
-        double q[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) q[r] = sig_readlane_f64(q_lane, (int)(n - qbase) + r);     // osc.py:32
-#ifdef SIG_VP_STATIC_CODE
-        // a specialised build: the program is a compile-time constant, the loop is unrolled and every switch below folds away
-        constexpr uint32_t kStatic[] = SIG_VP_STATIC_CODE;
-        constexpr bool kStaticExt = [] {
-            constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
-            bool ext = false;
-            for (unsigned k = 0; k < sizeof(c) / sizeof(c[0]); ++k) {
-                const uint32_t op = c[k] & 31u;
-                ext |= op == (uint32_t)SIG_VP_AMP || op == (uint32_t)SIG_VP_ADSR || op == (uint32_t)SIG_VP_NOISE;
-            }
-            return ext;
-        }();
-        static_assert(EXT || !kStaticExt, "the program uses Amp / ADSR / White: build with -DSIG_VP_S_EXT=1");
-#pragma unroll
-        for (int pc = 0; pc < (int)(sizeof(kStatic) / sizeof(kStatic[0])); ++pc) {
-            const uint32_t w = kStatic[pc];
-#else
-        for (int pc = 0; pc < a.n_ins; ++pc) {
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)codev, pc);
-#endif
-            const int op = (int)(w & 31u), kind = (int)((w >> 5) & 7u), ia = (int)((w >> 8) & 15u), ib = (int)((w >> 12) & 15u),
-                      ic = (int)((w >> 16) & 15u);
-            // OscTable is dispatched in front of the switch, and only in the TAB variant: a case of its own, even an empty one, changes
-            // the code of every other instantiation (the compare chain of the dispatch), and those are to stay what they were
-            if constexpr (RES) {                                               // FilterQ: the Filter handler on a resonant slot, in front of the switch like OscTable
-                if (op == SIG_VP_FILTERQ) {
-                    with_index<NF>(ia, [&](auto I) {
-                        constexpr int F = decltype(I)::value;
-                        section(I, warm_r, rows_tag, [&](int) { return s2[F]; }, [&](int) { return s2[F]; }, true);
-                    });
-                    continue;
-                }
-            }
-            if constexpr (UNI) {                                               // OscUni: in front of the switch like OscTable
-                if (op == SIG_VP_OSCUNI) {
-                    // sig_osc_bank_unison's expression with the fused waveforms: r = 1 + spread d, h = hertz r, q = phase + p per copy
-                    // (block-invariant, but 2 x copies x VPT registers: recomputed per group), t = n / rate * h + q, the sum in u
-                    // ascending, divided by the count.  The copy loop's trip count is wave-uniform (the argument block)
-                    double sp[VPT];
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) sp[i] = 0.0;                 // (15: spread unplugged)
-                    if (ic < NP) {
-                        with_index<NP>(ic, [&](auto I) {
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) sp[i] = pr[decltype(I)::value][i];
-                        });
-                    }
-                    const int copies = tb.copies;
-                    with_index<NO>(ia, [&](auto I) {
-                        constexpr int S = decltype(I)::value;
-                        for (int u = 0; u < copies; ++u) {
-                            const double d = tb.detune[u], p = tb.offset[u];
-                            double h[VPT], qu[VPT];
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                h[i] = ohz[S][i] * (1.0 + sp[i] * d);
-                                qu[i] = oph[S][i] + p;
-                            }
-                            auto add = [&](auto wave) {
-#pragma unroll
-                                for (int r = 0; r < R; ++r) {
-                                    const double qr = vp_pin(q[r]);
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) {
-                                        const double w = wave(qr * h[i] + qu[i]);
-                                        acc[r][i] = (u == 0) ? w : acc[r][i] + w;
-                                    }
-                                }
-                            };
-                            switch (kind) {
-                                case SIG_OSC_SINE: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SINE>(t); }); break;
-                                case SIG_OSC_SAWTOOTH: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SAWTOOTH>(t); }); break;
-                                case SIG_OSC_SQUARE: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_SQUARE>(t); }); break;
-                                default: add([](double t) { return sig_osc::osc_wave_fused<SIG_OSC_TRIANGLE>(t); }); break;
-                            }
-                        }
-                        const double count = (double)copies;
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
-                    });
-                    continue;
-                }
-            }
-            if constexpr (BLP) {                                               // OscBlep: OscUni's operands and copies, sig_osc_bank_blep's waveforms
-                if (op == SIG_VP_OSCBLEP) {
-                    // the OscUni handler with sig_osc::osc_blep (m by v_fract_f64, like the fused waveforms) per copy.  d = min(|h| / rate,
-                    // 0.5) and 1 / d are block-invariant too, and 4 x copies x VPT registers with h and q: recomputed per group, two
-                    // divides per copy and voice for the group's R rows; the rows multiply
-                    double sp[VPT];
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) sp[i] = 0.0;                 // (15: spread unplugged)
-                    if (ic < NP) {
-                        with_index<NP>(ic, [&](auto I) {
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) sp[i] = pr[decltype(I)::value][i];
-                        });
-                    }
-                    const int copies = tb.copies;
-                    with_index<NO>(ia, [&](auto I) {
-                        constexpr int S = decltype(I)::value;
-                        for (int u = 0; u < copies; ++u) {
-                            const double du = tb.detune[u], pu = tb.offset[u];
-                            double h[VPT], qu[VPT], d[VPT], inv_d[VPT];
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                h[i] = ohz[S][i] * (1.0 + sp[i] * du);
-                                qu[i] = oph[S][i] + pu;
-                                sig_osc::blep_increment(h[i], a.rate, d[i], inv_d[i]);
-                            }
-                            auto add = [&](auto wave) {
-#pragma unroll
-                                for (int r = 0; r < R; ++r) {
-                                    const double qr = vp_pin(q[r]);
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) {
-                                        const double w = wave(qr * h[i] + qu[i], d[i], inv_d[i]);
-                                        acc[r][i] = (u == 0) ? w : acc[r][i] + w;
-                                    }
-                                }
-                            };
-                            switch (kind) {                                    // (Sine is refused by the entry)
-                                case SIG_OSC_SAWTOOTH: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_SAWTOOTH, true>(t, d, v); }); break;
-                                case SIG_OSC_SQUARE: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_SQUARE, true>(t, d, v); }); break;
-                                default: add([](double t, double d, double v) { return sig_osc::osc_blep<SIG_OSC_TRIANGLE, true>(t, d, v); }); break;
-                            }
-                        }
-                        const double count = (double)copies;
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
-                    });
-                    continue;
-                }
-            }
-            if constexpr (TAB) {
-                // the column of table slot ib that parameter slot ic selects, per voice: its first float in `tab`
-                auto columns = [&](int (&col)[VPT], int& TT) {
-                    const int slot = ib & (SIG_VP_MAX_TABLES - 1);
-                    TT = tb.T[slot];
-                    const int W = tb.W[slot], S = TT + 1;
-                    const int first = slot ? (tb.T[0] + 1) * tb.W[0] : 0;
-#pragma unroll
-                    for (int i = 0; i < VPT; ++i) col[i] = first;
-                    if (ic < NP) {                                             // (15: select unplugged, column 0)
-                        with_index<NP>(ic, [&](auto I) {
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) col[i] = first + sig_table::column(pr[decltype(I)::value][i], W) * S;
-                        });
-                    }
-                };
-                if constexpr (SHP) {
-                    if (op == SIG_VP_SHAPE) {                                  // the accumulator through a transfer curve (ext.py Shaper, shaper.hip)
-                        int col[VPT], TT;
-                        columns(col, TT);
-                        const double half = (double)(TT - 1) * 0.5;
-                        const int last = TT - 2;
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                const double x = acc[r][i];
-                                const double c = (x < -1.0) ? -1.0 : ((x > 1.0) ? 1.0 : x);     // np.clip: NaN stays NaN
-                                const double u = (c + 1.0) * half;
-                                const int k = (u >= 0.0) ? min((int)floor(u), last) : 0;         // (NaN: entry 0, u - k carries it)
-                                const int at = col[i] + k;                     // at + 1 <= the column's entry T - 1
-                                const double lo = (double)tab[at], hi = (double)tab[at + 1];
-                                acc[r][i] = lo + (u - (double)k) * (hi - lo);
-                            }
-                        }
-                        continue;
-                    }
-                }
-                if (op == SIG_VP_OSCTABLE) {                                   // the Osc handler's phase, looked up in table slot ib (ext.py Wavetable)
-                    // m = t - floor(t) as v_fract_f64: not the definition's 1.0 for t in (-2^-54, 0) but the largest double below
-                    // it, i.e. the last segment at f = 1 - T 2^-53 instead of entry 0 at f = 0 -- one rounding of a table step apart
-                    int col[VPT], TT;
-                    columns(col, TT);
-                    const double scale = (double)TT;
-                    const int mask = TT - 1;
-                    with_index<NO>(ia, [&](auto I) {
-                        constexpr int S_ = decltype(I)::value;
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const double qr = vp_pin(q[r]);
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                const double u = __builtin_amdgcn_fract(qr * ohz[S_][i] + oph[S_][i]) * scale;
-                                const double fl = floor(u);
-                                const int at = col[i] + ((int)fl & mask);
-                                const double lo = (double)tab[at], hi = (double)tab[at + 1];
-                                acc[r][i] = lo + (u - fl) * (hi - lo);
-                            }
-                        }
-                    });
-                    continue;
-                }
-            }
-            switch (op) {
-                case SIG_VP_OSC:
-                    with_index<NO>(ia, [&](auto I) {
-                        constexpr int S = decltype(I)::value;
-                        double t[R][VPT];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const double qr = vp_pin(q[r]);
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) t[r][i] = qr * ohz[S][i] + oph[S][i];
-                        }
-                        switch (kind) {
-                            case SIG_OSC_SINE:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = (double)sig_osc::osc_sine_f32(t[r][i]);
-                                break;
-                            case SIG_OSC_SAWTOOTH:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_sawtooth_fract(t[r][i]);
-                                break;
-                            case SIG_OSC_SQUARE:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_square_fract(t[r][i]);
-                                break;
-                            default:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_triangle_fract(t[r][i]);
-                                break;
-                        }
-                    });
-                    break;
-                case SIG_VP_OSCPM: if constexpr (PM) {                         // the Osc handler, its phase offset by index * accumulator (ext.py PMOsc)
-                    double ix[VPT];
-                    with_index<NP>(ib, [&](auto I) {
-#pragma unroll
-                        for (int i = 0; i < VPT; ++i) ix[i] = pr[decltype(I)::value][i];
-                    });
-                    with_index<NO>(ia, [&](auto I) {
-                        constexpr int S = decltype(I)::value;
-                        double t[R][VPT];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const double qr = vp_pin(q[r]);
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) t[r][i] = (qr * ohz[S][i] + oph[S][i]) + ix[i] * acc[r][i];
-                        }
-                        switch (kind) {
-                            case SIG_OSC_SINE:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = (double)sig_osc::osc_sine_f32(t[r][i]);
-                                break;
-                            case SIG_OSC_SAWTOOTH:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_sawtooth_fract(t[r][i]);
-                                break;
-                            case SIG_OSC_SQUARE:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_square_fract(t[r][i]);
-                                break;
-                            default:
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = sig_osc::osc_triangle_fract(t[r][i]);
-                                break;
-                        }
-                    });
-                }
-                    break;
-                case SIG_VP_FILTER:
-                    with_index<NF>(ia, [&](auto I) {
-                        constexpr int F = decltype(I)::value;
-                        section(I, warm_r, rows_tag, [&](int) { return s2[F]; }, [&](int) { return s2[F]; }, true);
-                    });
-                    break;
-                case SIG_VP_BAND:                                              // two sections in series, the band's gain on the second's output
-                    with_index<NF>(ia, [&](auto I) {
-                        constexpr int F = decltype(I)::value;
-                        if constexpr (BAND && F + 1 < NF) {
-                            constexpr int G = F + 1;
-                            const double sg = (a.ftype[F] == SIG_FILT_BANDPASS) ? -1.0 : 1.0;     // the second section's beta
-                            if (warm_r < R) {                                  // the next block's band: BOTH next chains in series on the input
-#pragma unroll
-                                for (int r = 0; r < R; ++r) {
-                                    if (r >= warm_r) {
-#pragma unroll
-                                        for (int i = 0; i < VPT; ++i) {
-                                            const double x = acc[r][i];
-                                            const double y1 = x + w0[F][i];
-                                            w0[F][i] = fma(xa1[F][i], y1, fma(xbq[F / 2][i], x, w1[F][i]));
-                                            w1[F][i] = fma(xa2[F][i], y1, x);
-                                            const double y2 = y1 + w0[G][i];
-                                            w0[G][i] = fma(xa1[G][i], y2, fma(sg * xbq[F / 2][i], y1, w1[G][i]));
-                                            w1[G][i] = fma(xa2[G][i], y2, y1);
-                                        }
-                                    }
-                                }
-                            }
-                            section(I, R, rows_tag, [&](int i) { return bq[F / 2][i]; }, [&](int i) { return bq[F / 2][i]; }, false);
-                            section(std::integral_constant<int, G>{}, R, rows_tag, [&](int i) { return sg * bq[F / 2][i]; },
-                                    [&](int i) { return sg * bq[F / 2][i]; }, true);
-                        }
-                    });
-                    break;
-                case SIG_VP_GAIN:
-                    with_index<NP>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] * pr[decltype(I)::value][i];      // fx.py:52
-                    });
-                    break;
-                case SIG_VP_MUL:
-                    with_index<NT>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = T[decltype(I)::value][r][i] * acc[r][i];     // fx.py:46
-                    });
-                    break;
-                case SIG_VP_SAVE:
-                    with_index<NT>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) T[decltype(I)::value][r][i] = acc[r][i];
-                    });
-                    break;
-                case SIG_VP_LOAD:
-                    with_index<NT>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = T[decltype(I)::value][r][i];
-                    });
-                    break;
-                case SIG_VP_MIX: {                                             // m * L + (1 - m) * R (fx.py:40); ic: the accumulator is L
-                    double m[VPT];
-                    with_index<NP>(ib, [&](auto I) {
-#pragma unroll
-                        for (int i = 0; i < VPT; ++i) m[i] = pr[decltype(I)::value][i];
-                    });
-                    with_index<NT>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) {
-                                const double l = ic ? acc[r][i] : T[decltype(I)::value][r][i], rr = ic ? T[decltype(I)::value][r][i] : acc[r][i];
-                                acc[r][i] = m[i] * l + (1.0 - m[i]) * rr;
-                            }
-                    });
-                    break;
-                }
-                case SIG_VP_CONST:
-                    with_index<NP>(ia, [&](auto I) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) acc[r][i] = pr[decltype(I)::value][i];
-                    });
-                    break;
-                default:
-                    if constexpr (EXT) {
-                        if (op == SIG_VP_AMP) {
-                            with_index<NP>(ia, [&](auto I) {
-#pragma unroll
-                                for (int r = 0; r < R; ++r)
-#pragma unroll
-                                    for (int i = 0; i < VPT; ++i) acc[r][i] = vp_amp(acc[r][i], pr[decltype(I)::value][i]);
-                            });
-                        } else if (op == SIG_VP_ADSR) {
-#pragma unroll
-                            for (int r = 0; r < R; ++r) {
-                                const double qr = vp_pin(q[r]);
-                                bool stale = false;
-#pragma unroll
-                                for (int i = 0; i < VPT; ++i) stale |= !(qr < seg[i].end);
-                                if (__any(stale)) seed_envelope(qr);           // a stage ended: a handful of times per voice and stream
-#pragma unroll
-                                for (int i = 0; i < VPT; ++i) acc[r][i] = fma(seg[i].slope, qr - seg[i].t0, seg[i].l0);
-                            }
-                        } else if (op == SIG_VP_NOISE) {
-#pragma unroll
-                            for (int r = 0; r < R; ++r)
-#pragma unroll
-                                for (int i = 0; i < VPT; ++i) acc[r][i] = (double)sig_noise::noise_value(a.seeds[ia & 1], n + r, v0 + i);
-                        }
-                    }
-                    break;
-            }
-        }
-        if (out) {
-            if constexpr (BUS && (R * CC == 16 || R * CC == 8)) {
-                // a whole group of the bus: its R x C sums stay in registers, are folded across lanes four at a time (two
-                // register-to-register halving steps, sig_bus::FoldedGroup) and only a quarter goes through the LDS
-                if (stage.staged) stage.now();                                 // single rows staged before: out first, in order
-                double sums[16];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) sums[k] = 0.0;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int ch = 0; ch < CC; ++ch) {
-                        double sum = 0.0;
-#pragma unroll
-                        for (int i = 0; i < VPT; ++i) sum = fma(wt[ch][i], acc[r][i], sum);
-                        sums[r * CC + ch] = sum;
-                    }
-#pragma unroll
-                for (int g4 = 0; g4 < (R * CC) / 4; ++g4) folded.fold4(g4, sums[4 * g4], sums[4 * g4 + 1], sums[4 * g4 + 2], sums[4 * g4 + 3]);
-                double pend[4];
-                folded.issue(pend);
-                folded.finish(pend, stage.first, R);
-                stage.first += R;
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    if constexpr (BUS) {
-#pragma unroll
-                        for (int ch = 0; ch < CC; ++ch) {
-                            double sum = 0.0;
-#pragma unroll
-                            for (int i = 0; i < VPT; ++i) sum = fma(wt[ch][i], acc[r][i], sum);
-                            stage.slot[ch * kTileStride] = sum;
-                        }
-                        stage.advance();
-                    } else {
-                        float y32[VPT];
-#pragma unroll
-                        for (int i = 0; i < VPT; ++i) y32[i] = (float)acc[r][i];
-                        if (live0) {
-                            Vec o; sig_vec::put(o, y32);
-                            *reinterpret_cast<Vec*>(dst + (n + r - a.position) * a.out_ld) = o;
-                        }
-                    }
-                }
-            }
-        }
-    };
-    for (int t = 0; t < n_steps; ++t) {
-        const Step st = make_step(t);
-        if (st.load) load_params(st.cri_load);
-        if (st.enter) enter_block(st.cri_enter);
-        bool started = false;                                                  // the next chains of this step
-        if (st.next0) { start_next(st.cri_next, st.next_level); started = true; }
-        if (st.from >= st.to) continue;
-        seed_envelope((double)st.from / a.rate);
-        int64_t n = st.from;
-        auto warm_rows = [&](int64_t at, int rows) {                           // first warm row of the group at `at` (rows: none), chains started on arrival
-            if (st.warm_from >= at + rows) return rows;
-            if (!started) { start_next(st.cri_next, st.next_level); started = true; }
-            return (st.warm_from <= at) ? 0 : (int)(st.warm_from - at);
-        };
-        if constexpr (RG > 1) {
-            for (; n + RG <= st.to; n += RG) group(n, warm_rows(n, RG), st.out, std::integral_constant<int, RG>{});
-        }
-        for (; n < st.to; ++n) group(n, warm_rows(n, 1), st.out, std::integral_constant<int, 1>{});
-    }
-    if (BUS && stage.staged) stage.now();
-}
-
-#ifndef SIG_VP_WAVES
-#define SIG_VP_WAVES 2
-#endif
-#ifndef SIG_VP_WAVES1
-#define SIG_VP_WAVES1 3
-#endif
-template <int VPT, bool SMALL, int C, bool BAND, bool PM, bool TAB, bool SHP, bool RES, bool UNI, bool BLP, typename TABLES>
-__device__ __forceinline__ void vp_kernel_body(const VpArgs& a, const TABLES& tb)
-{
-    constexpr bool BUS = C > 0;
-    __shared__ double lds[BUS ? 4 : 1][BUS ? sig_bus::kPairs * kTileStride : 1];
-    const float* tab = nullptr;
-    if constexpr (TAB) {                                                       // the tables into (dynamic) LDS, once per workgroup
-        extern __shared__ float vp_tab[];
-        int first = 0;
-#pragma unroll
-        for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) {
-            if (!tb.ptr[k]) break;                                             // (slots are filled from 0)
-            sig_table::stage<256>(vp_tab + first, tb.ptr[k], tb.T[k], tb.W[k]);
-            first += (tb.T[k] + 1) * tb.W[k];
-        }
-        __syncthreads();
-        tab = vp_tab;
-    }
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    vp_wave<VPT, SMALL, C, BAND, PM, TAB, SHP, RES, UNI, BLP>(a, lds[BUS ? wave : 0], lane, wave, tb, tab);
-    if constexpr (BUS) {
-        if (a.bus_out) sig_bus::sum_tiles_in_workgroup<C>(a.partials, a.voice_tiles, a.rows, a.span, a.K, a.N, a.bus_out, a.bus_out_ld, lane, wave);
-    }
-}
+#include "sig_vp_machine.h"
 
 #ifdef SIG_VP_STATIC_CODE
 // A SPECIALISED build of this file (signals_amd/specialise.py: hipcc --genco with the program, the exact register file, the
 // voices per lane and the sink as macros): one kernel, the same source as the interpreter with the program a compile-time
 // constant -- the dispatch loop unrolls and every switch folds.  Attached to the library with sig_voice_program_attach.
+namespace {
 // does the program this file is specialised for have an instruction with this opcode?
 constexpr bool vp_static_has(int op) {
     constexpr uint32_t c[] = SIG_VP_STATIC_CODE;
@@ -1061,7 +24,6 @@ constexpr bool vp_static_has(int op) {
     return false;
 }
 }  // namespace
-extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
 #ifndef SIG_VP_S_TAB
 #define SIG_VP_S_TAB 0                     // 1: the program has an OscTable or a Shape word, the kernel takes the tables as a second parameter
 #endif
@@ -1074,12 +36,16 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 #ifndef SIG_VP_S_MIXED
 #define SIG_VP_S_MIXED 0                   // 1: the program combines two or more of Band, OscPM, OscTable / Shape, FilterQ, OscUni; the kernel takes a VpMixed
 #endif
+#ifndef SIG_VP_S_RES
+#define SIG_VP_S_RES 0                     // 1: the program has a FilterQ word (the resonant design)
+#endif
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
 #if SIG_VP_S_MIXED
-void sig_vp_specialised(VpArgs a, VpMixed mx)
+void sig_vp_specialised(VpArgs a, VpMixed extra)
 #elif SIG_VP_S_TAB
-void sig_vp_specialised(VpArgs a, VpTables tb)
+void sig_vp_specialised(VpArgs a, VpTables extra)
 #elif SIG_VP_S_UNI
-void sig_vp_specialised(VpArgs a, VpUnison un)
+void sig_vp_specialised(VpArgs a, VpUnison extra)
 #else
 void sig_vp_specialised(VpArgs a)
 #endif
@@ -1087,9 +53,6 @@ void sig_vp_specialised(VpArgs a)
     constexpr bool kBand = vp_static_has(SIG_VP_BAND), kPm = vp_static_has(SIG_VP_OSCPM), kShape = vp_static_has(SIG_VP_SHAPE);
     constexpr bool kTab = vp_static_has(SIG_VP_OSCTABLE) || kShape;
     constexpr bool kRes = vp_static_has(SIG_VP_FILTERQ);
-#ifndef SIG_VP_S_RES
-#define SIG_VP_S_RES 0                     // 1: the program has a FilterQ word (the resonant design)
-#endif
     static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
     constexpr bool kBlep = vp_static_has(SIG_VP_OSCBLEP);
@@ -1103,14 +66,12 @@ void sig_vp_specialised(VpArgs a)
     static_assert(!(kUni && (kTab || kBand || kPm || kRes)), "OscUni with Band, OscPM, OscTable, Shape or FilterQ: no variant has both");
     static_assert(!(kBand && kPm) && !(kTab && (kBand || kPm)), "Band, OscPM and OscTable / Shape: no variant has two of them");
 #endif
-#if SIG_VP_S_MIXED
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, kTab, kShape, kRes, kUni, kBlep>(a, mx);      // exactly the families the program has
-#elif SIG_VP_S_TAB
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, true, kShape, false, false, false>(a, tb);
-#elif SIG_VP_S_UNI
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, false, false, false, false, false, true, kBlep>(a, un);
+    using F = VpFamily<kBand, kPm, kTab, kShape, kRes, kUni, kBlep>;           // exactly the families the program has
+#if SIG_VP_S_MIXED || SIG_VP_S_TAB || SIG_VP_S_UNI
+    static_assert(std::is_same_v<F::Extra, decltype(extra)>, "the second kernel parameter is the one the program's families take");
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, F>(a, extra);
 #else
-    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, kBand, kPm, false, false, kRes, false, false>(a, VpNoTables{});
+    vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, F>(a, VpNoTables{});
 #endif
 }
 // what the attaching library checks before it trusts the image: the argument block's size and the program it was built for
@@ -1121,48 +82,9 @@ extern "C" __global__ void sig_vp_specialised_info(uint32_t* out)
     for (unsigned k = 0; k < sizeof(code) / sizeof(code[0]); ++k) out[4 + k] = code[k];
 }
 #else
-template <int VPT, bool SMALL, int C, bool BAND, bool PM>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_kernel(VpArgs a)
-{
-    vp_kernel_body<VPT, SMALL, C, BAND, PM, false, false, false, false, false>(a, VpNoTables{});
-}
-// the TAB variant (never with BAND or PM): a kernel of its own, whose second parameter carries the tables
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_table_kernel(VpArgs a, VpTables tb)
-{
-    vp_kernel_body<VPT, SMALL, C, false, false, true, false, false, false, false>(a, tb);
-}
-// the TAB variant with the Shape instruction (programs with a waveshaper, with or without a wavetable oscillator)
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_shape_kernel(VpArgs a, VpTables tb)
-{
-    vp_kernel_body<VPT, SMALL, C, false, false, true, true, false, false, false>(a, tb);
-}
-// the RES variant (never with BAND, PM or TAB): programs with a resonant filter, whose design reads q
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_res_kernel(VpArgs a)
-{
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, true, false, false>(a, VpNoTables{});
-}
-// the UNI variant (never with BAND, PM, TAB or RES): a kernel of its own, whose second parameter carries the copies
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_unison_kernel(VpArgs a, VpUnison un)
-{
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true, false>(a, un);
-}
-// the UNI variant with the OscBlep instruction (programs with a band-limited oscillator, with or without a plain unison one)
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_blep_kernel(VpArgs a, VpUnison un)
-{
-    vp_kernel_body<VPT, SMALL, C, false, false, false, false, false, true, true>(a, un);
-}
-// the MIXED variant: every family at once, for programs that combine two or more of them (sig_voice_program_mixed only); its
-// second parameter carries the tables and the copies
-template <int VPT, bool SMALL, int C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? (VPT == 1 ? SIG_VP_WAVES1 : SIG_VP_WAVES) : 1, 8))) void voice_program_mixed_kernel(VpArgs a, VpMixed mx)
-{
-    vp_kernel_body<VPT, SMALL, C, true, true, true, true, true, true, true>(a, mx);
-}
+#include "sig_vp_launch.h"
+
+namespace {
 
 struct VpTuning { int vpt = 0, span = 0, attached = 1; };
 VpTuning& vp_tuning() { static VpTuning t; return t; }
@@ -1174,13 +96,35 @@ struct VpSpecial { uint32_t code[kMaxIns]; int n_ins, n_oscs, n_params, n_filter
 std::vector<VpSpecial>& vp_specials() { static std::vector<VpSpecial> v; return v; }
 std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 
+// ---- the two rules about words, each written once
+// may this word's c be -1?  (no select / no q / no spread; encoded as 15, a slot number no register file has)
+constexpr bool vp_c_optional(int op) {
+    return op == SIG_VP_OSCTABLE || op == SIG_VP_SHAPE || op == SIG_VP_FILTERQ || op == SIG_VP_OSCUNI || op == SIG_VP_OSCBLEP;
+}
+// the variant that has this word's handler and no other extension word's (SIG_VP_FAMILY_*; PLAIN: every variant has it)
+constexpr int vp_word_family(int op) {
+    switch (op) {
+        case SIG_VP_BAND: return SIG_VP_FAMILY_BAND;
+        case SIG_VP_OSCPM: return SIG_VP_FAMILY_PM;
+        case SIG_VP_OSCTABLE: return SIG_VP_FAMILY_TABLE;
+        case SIG_VP_SHAPE: return SIG_VP_FAMILY_SHAPE;
+        case SIG_VP_FILTERQ: return SIG_VP_FAMILY_RESONANT;
+        case SIG_VP_OSCUNI: return SIG_VP_FAMILY_UNISON;
+        case SIG_VP_OSCBLEP: return SIG_VP_FAMILY_BLEP;
+        default: return SIG_VP_FAMILY_PLAIN;
+    }
+}
+
+bool vp_word_ok(const sig_vp_ins& x) {
+    return x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+           x.c >= (vp_c_optional(x.op) ? -1 : 0) && x.c <= 15;
+}
+
 bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
-        const int c = ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI || x.op == SIG_VP_OSCBLEP) && x.c == -1) ? 15 : x.c;       // (no select / no q / no spread: a slot number no register file has)
-        if (!(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 && c >= 0 && c <= 15))
-            return false;
-        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)c << 16);
+        if (!vp_word_ok(x)) return false;
+        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)(x.c & 15) << 16);
     }
     return true;
 }
@@ -1195,11 +139,59 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
     return nullptr;
 }
 
-struct VpNeeds { int oscs, params, temps, filters; bool ext, band, pm, table, shape, res, uni, blep; };
+// What a program asks of the machine: slots, the extended handlers (Amp, ADSR, White), and `words`: bit f is set when the program
+// has a word of family f (vp_word_family).
+struct VpNeeds {
+    int oscs, params, temps, filters; bool ext, adsr; unsigned words;
+    bool has(int family) const { return (words >> family) & 1u; }
+    bool table() const { return has(SIG_VP_FAMILY_TABLE) || has(SIG_VP_FAMILY_SHAPE); }      // (Shape sits on top of the table family)
+    bool uni() const { return has(SIG_VP_FAMILY_UNISON) || has(SIG_VP_FAMILY_BLEP); }        // (OscBlep: the unison family, the same copies, the same exclusions)
+    // the families of which every single-family variant has one
+    int families() const { return (int)has(SIG_VP_FAMILY_BAND) + (int)has(SIG_VP_FAMILY_PM) + (int)table() + (int)has(SIG_VP_FAMILY_RESONANT) + (int)uni(); }
+};
+
+VpNeeds vp_needs(const sig_voice_program_t& P) {              // (n_ins was checked; any op may stand in a word)
+    VpNeeds n{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, 0u};
+    for (int k = 0; k < P.n_ins; ++k) {
+        const int op = P.ins[k].op;
+        if (op == SIG_VP_AMP || op == SIG_VP_ADSR || op == SIG_VP_NOISE) n.ext = true;
+        if (op == SIG_VP_ADSR) n.adsr = true;
+        n.words |= 1u << vp_word_family(op);
+    }
+    return n;
+}
 
 bool fits_small(const VpNeeds& n) {
     using L = VpLimits<true>;
     return n.oscs <= L::NO && n.params <= L::NP && n.temps <= L::NT && n.filters <= L::NF && !n.ext;
+}
+
+// The variant a program runs in (SIG_VP_FAMILY_*): two or more families: MIXED (a table never with a band or a PM carrier, a PM
+// carrier never with a band, a resonant filter or a unison oscillator with none of them nor with each other: refused by every
+// entry but sig_voice_program_mixed); else the one variant that has every word of the program.
+int vp_variant(const VpNeeds& n) {
+    if (n.families() >= 2) return SIG_VP_FAMILY_MIXED;
+    for (int f : {SIG_VP_FAMILY_BLEP, SIG_VP_FAMILY_UNISON, SIG_VP_FAMILY_RESONANT, SIG_VP_FAMILY_SHAPE, SIG_VP_FAMILY_TABLE,
+                  SIG_VP_FAMILY_PM, SIG_VP_FAMILY_BAND})
+        if (n.has(f)) return f;
+    return SIG_VP_FAMILY_PLAIN;
+}
+
+// f(descriptor) for a SIG_VP_FAMILY_* value
+template <typename Fn>
+int vp_with_family(int variant, Fn&& f) {
+    switch (variant) {
+        case SIG_VP_FAMILY_PLAIN: return f(vp_family::plain{});
+        case SIG_VP_FAMILY_BAND: return f(vp_family::band{});
+        case SIG_VP_FAMILY_PM: return f(vp_family::pm{});
+        case SIG_VP_FAMILY_TABLE: return f(vp_family::table{});
+        case SIG_VP_FAMILY_SHAPE: return f(vp_family::shape{});
+        case SIG_VP_FAMILY_RESONANT: return f(vp_family::resonant{});
+        case SIG_VP_FAMILY_UNISON: return f(vp_family::unison{});
+        case SIG_VP_FAMILY_BLEP: return f(vp_family::blep{});
+        case SIG_VP_FAMILY_MIXED: return f(vp_family::mixed{});
+        default: return (int)hipErrorInvalidValue;
+    }
 }
 
 // voices per lane and blocks per lane.  4 voices per lane amortise the interpreter's scalar work best; a lane's span
@@ -1224,99 +216,224 @@ void vp_geometry(const VpArgs& a, int store_aligned, bool four, int& vpt, int& s
     }
 }
 
-template <int VPT, bool SMALL, bool BAND, bool PM>
-int vp_launch_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_kernel<VPT, SMALL, 0, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
-        case 1: voice_program_kernel<VPT, SMALL, 1, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
-        case 2: voice_program_kernel<VPT, SMALL, 2, BAND, PM><<<nwg, 256, 0, s>>>(a); break;
-        default: return (int)hipErrorInvalidValue;
+// what sig_voice_program and its three extensions are called with
+struct VpRequest {
+    const sig_voice_program_t* program; int32_t rate; int64_t position; int32_t block_frames, nblocks, context, voices, control_rows;
+    int32_t hist_blocks; const int64_t* hist_positions; int32_t blocks_before;
+    const double* bus_gains; int64_t bus_gains_ld; int32_t bus_channels;
+    double* workspace; float* out; int64_t out_ld; int32_t* status; void* stream;
+    const sig_vp_tables_t* tables; const sig_vp_unison_t* unison;
+    bool allow_mixed;                                                          // sig_voice_program_mixed: the three exclusivity checks are off
+};
+
+// a checked call: the kernels' arguments, but for the geometry
+struct VpCall {
+    bool empty;                                                                // nothing to render (and nothing below is filled)
+    VpArgs a; VpNeeds need; size_t table_lds;
+    std::tuple<VpNoTables, VpTables, VpUnison, VpMixed> extra;                 // the second kernel parameter, by family (VpFamily::Extra)
+};
+
+// Checks the call and the program and fills `c`.  Host only: no HIP call.
+int vp_check(const VpRequest& r, VpCall& c)
+{
+    const sig_vp_tables_t* tables = r.tables;
+    const sig_vp_unison_t* unison = r.unison;
+    SIG_CHECK_ARG(!unison || (unison->copies >= 1 && unison->copies <= SIG_UNISON_MAX_COPIES));
+    SIG_CHECK_ARG(r.program && r.rate > 0 && r.position >= 0 && r.block_frames >= 0 && r.nblocks >= 0 && r.context >= 0 && r.voices >= 0);
+    SIG_CHECK_ARG(r.out && (r.bus_channels == 0 || r.bus_channels == 1 || r.bus_channels == 2));
+    SIG_CHECK_ARG(r.bus_channels == 0 ? r.out_ld >= r.voices : (r.out_ld >= r.bus_channels && r.workspace != nullptr));
+    SIG_CHECK_ARG(r.bus_gains ? (r.bus_channels > 0 && r.bus_gains_ld >= r.voices) : r.bus_channels <= 1);
+    const sig_voice_program_t& P = *r.program;
+    SIG_CHECK_ARG(P.n_ins >= 1 && P.n_ins <= SIG_VP_MAX_INS && P.n_oscs >= 0 && P.n_oscs <= SIG_VP_MAX_OSCS);
+    SIG_CHECK_ARG(P.n_params >= 0 && P.n_params <= SIG_VP_MAX_PARAMS && P.n_filters >= 0 && P.n_filters <= SIG_VP_MAX_FILTERS);
+    SIG_CHECK_ARG(P.n_temps >= 0 && P.n_temps <= SIG_VP_MAX_TEMPS && P.depth >= 0 && P.depth <= P.n_filters);
+    SIG_CHECK_ARG(r.hist_blocks >= 0 && r.hist_blocks <= SIG_VP_MAX_HIST && (r.hist_blocks == 0 || r.hist_positions) && r.blocks_before >= 0);
+    const bool small = P.depth > 0 && r.block_frames < r.context;
+    SIG_CHECK_ARG(!small || (P.depth <= 2 && r.block_frames >= 16));          // (deeper cascades, or blocks so short that the reference's 16-entry block cache evicts what they read: the eager path)
+    SIG_CHECK_ARG(small || r.position == 0 || r.hist_blocks >= (P.depth > 1 ? 1 : 0));
+    SIG_CHECK_ARG(r.control_rows == (small ? 2 * r.nblocks : r.hist_blocks + 1 + r.nblocks));
+    c.empty = r.block_frames == 0 || r.nblocks == 0 || r.voices == 0;
+    if (c.empty) return 0;
+    VpArgs& a = c.a;
+    a = VpArgs{};
+    a.rate = (double)r.rate; a.position = r.position; a.N = r.block_frames; a.K = r.nblocks; a.ctx = r.context; a.voices = r.voices;
+    auto rows_ok = [&](const sig_vp_rows& rows, bool optional) {
+        if (!rows.ptr) return optional;
+        return (rows.col_stride | 1) == 1 && (rows.rows == 1 || rows.rows == r.control_rows);
+    };
+    // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
+    const int n_tables = tables ? tables->n_tables : 0;
+    SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
+    c.table_lds = 0;
+    for (int k = 0, points = 0; k < n_tables; ++k) {
+        const auto& t = tables->table[k];
+        SIG_CHECK_ARG(t.ptr != nullptr && t.points >= 2 && t.waves >= 1 &&
+                      (int64_t)t.points * t.waves <= SIG_TABLE_MAX_POINTS - points);
+        points += t.points * t.waves;
+        c.table_lds += (size_t)(t.points + 1) * t.waves * sizeof(float);
     }
-    return sig_launch_status();
+    a.n_ins = P.n_ins;
+    for (int k = 0; k < P.n_ins; ++k) {
+        const sig_vp_ins& x = P.ins[k];
+        SIG_CHECK_ARG(vp_word_ok(x));
+        switch (x.op) {
+            case SIG_VP_OSCTABLE:
+                SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
+                SIG_CHECK_ARG((tables->table[x.b].points & (tables->table[x.b].points - 1)) == 0);     // the oscillator wraps with a mask
+                break;
+            case SIG_VP_SHAPE: SIG_CHECK_ARG(x.b < n_tables && x.c < P.n_params); break;
+            case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
+            case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
+            case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
+            case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
+            case SIG_VP_OSCUNI:
+                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params && x.kind <= SIG_OSC_TRIANGLE);
+                break;
+            case SIG_VP_OSCBLEP:                                               // OscUni's operands; no Sine
+                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params &&
+                              x.kind >= SIG_OSC_SQUARE && x.kind <= SIG_OSC_TRIANGLE);
+                break;
+            case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
+            case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
+            case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
+            case SIG_VP_MIX: SIG_CHECK_ARG(x.a < P.n_temps && x.b < P.n_params); break;
+            case SIG_VP_NOISE: SIG_CHECK_ARG(x.a < 2); break;
+            default: break;
+        }
+    }
+    const VpNeeds need = c.need = vp_needs(P);
+    if (!r.allow_mixed) {
+        const bool band = need.has(SIG_VP_FAMILY_BAND), pm = need.has(SIG_VP_FAMILY_PM), res = need.has(SIG_VP_FAMILY_RESONANT);
+        SIG_CHECK_ARG(!(need.uni() && (band || pm || need.table() || res)));
+        SIG_CHECK_ARG(!(res && (band || pm || need.table())));
+        SIG_CHECK_ARG(!(band && pm) && !(need.table() && (band || pm)));      // (no single-family variant with two of them; the engine keeps such a graph per node unless asked for mixed programs)
+    }
+    VpTables& tb = std::get<VpTables>(c.extra);
+    tb = VpTables{};
+    for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
+    if (!need.table()) c.table_lds = 0;
+    VpUnison& un = std::get<VpUnison>(c.extra);
+    un = VpUnison{};
+    if (need.uni()) {
+        un.copies = unison->copies;
+        for (int u = 0; u < un.copies; ++u) { un.detune[u] = unison->detune[u]; un.offset[u] = unison->offset[u]; }
+    }
+    VpMixed& mx = std::get<VpMixed>(c.extra);
+    mx = VpMixed{};
+    if (need.families() >= 2) {
+        for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) { mx.ptr[k] = need.table() ? tb.ptr[k] : nullptr; mx.T[k] = tb.T[k]; mx.W[k] = tb.W[k]; }     // (no table word: nothing is staged)
+        mx.copies = un.copies;
+        for (int u = 0; u < un.copies; ++u) { mx.detune[u] = un.detune[u]; mx.offset[u] = un.offset[u]; }
+    }
+    SIG_CHECK_ARG(vp_encode(P, a.code));
+    a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
+    for (int k = 0; k < P.n_oscs; ++k) {
+        SIG_CHECK_ARG(rows_ok(P.hertz[k], false) && rows_ok(P.phase[k], true));
+        a.hertz[k] = Rows{P.hertz[k].ptr, P.hertz[k].col_stride, P.hertz[k].rows};
+        a.phase[k] = Rows{P.phase[k].ptr, P.phase[k].col_stride, P.phase[k].ptr ? P.phase[k].rows : 1};
+    }
+    for (int k = 0; k < P.n_params; ++k) {
+        SIG_CHECK_ARG(rows_ok(P.params[k], false));
+        a.params[k] = Rows{P.params[k].ptr, P.params[k].col_stride, P.params[k].rows};
+    }
+    // filter slots: a Filter instruction runs a LowPass / HighPass slot; a Band instruction at slot f runs the pair f, f + 1 (its
+    // low and high rows), of one band type and one level, which the kernel finds by pairing every run of band slots from its start
+    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second, 4: resonant (one FilterQ word)
+    for (int k = 0; k < P.n_ins; ++k) {
+        const sig_vp_ins& x = P.ins[k];
+        if (x.op == SIG_VP_FILTER) {
+            SIG_CHECK_ARG(role[x.a] == 0 || role[x.a] == 1);
+            role[x.a] = 1;
+        } else if (x.op == SIG_VP_FILTERQ) {
+            SIG_CHECK_ARG(role[x.a] == 0);
+            role[x.a] = 4;
+        } else if (x.op == SIG_VP_BAND) {
+            SIG_CHECK_ARG((role[x.a] == 0 || role[x.a] == 2) && (role[x.a + 1] == 0 || role[x.a + 1] == 3));
+            role[x.a] = 2; role[x.a + 1] = 3;
+        }
+    }
+    for (int k = 0, run = 0; k < P.n_filters; ++k) {
+        const bool band = P.filter_type[k] == SIG_FILT_BANDPASS || P.filter_type[k] == SIG_FILT_BANDSTOP;
+        run = band ? run + 1 : 0;
+        if (role[k] == 1) SIG_CHECK_ARG(P.filter_type[k] == SIG_FILT_LOWPASS || P.filter_type[k] == SIG_FILT_HIGHPASS);
+        else if (role[k] == 2) SIG_CHECK_ARG(band && run % 2 == 1 && P.filter_type[k + 1] == P.filter_type[k] &&
+                                             P.filter_level[k + 1] == P.filter_level[k]);
+        else if (role[k] == 3) SIG_CHECK_ARG(band && run % 2 == 0);
+        const bool resonant = P.filter_type[k] == SIG_FILT_RES_LOWPASS || P.filter_type[k] == SIG_FILT_RES_HIGHPASS;
+        SIG_CHECK_ARG(resonant == (role[k] == 4));                             // a resonant slot and its FilterQ word go together
+    }
+    for (int k = 0; k < P.n_filters; ++k) {
+        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_RES_HIGHPASS);
+        a.cutoff[k] = Rows{P.cutoff[k].ptr, P.cutoff[k].col_stride, P.cutoff[k].rows};
+        a.ftype[k] = P.filter_type[k];
+        SIG_CHECK_ARG(P.filter_level[k] >= 1 && P.filter_level[k] <= P.depth);
+        a.flevel[k] = P.filter_level[k];
+    }
+    if (need.adsr) {
+        SIG_CHECK_ARG(sig_env::load_rows(P.adsr, P.adsr_stride, a.adsr));
+        a.has_adsr = 1;
+    }
+    a.seeds[0] = P.noise_seed[0]; a.seeds[1] = P.noise_seed[1];
+    a.depth = P.depth; a.small = small ? 1 : 0; a.blocks_before = r.blocks_before;
+    a.hist = small ? 0 : r.hist_blocks;
+    for (int k = 0; k < a.hist; ++k) {
+        SIG_CHECK_ARG(r.hist_positions[k] >= 0 && r.hist_positions[k] < (k + 1 < a.hist ? r.hist_positions[k + 1] : r.position));
+        a.hist_pos[k] = r.hist_positions[k];
+    }
+    a.status = r.status;
+    if (r.bus_channels > 0) {
+        a.pan = r.bus_gains; a.pan_ld = r.bus_gains_ld; a.partials = r.workspace; a.rows = (int64_t)r.block_frames * r.nblocks;
+    } else {
+        a.out = r.out; a.out_ld = r.out_ld;
+    }
+    return 0;
 }
 
-template <int VPT, bool SMALL>
-int vp_launch_table_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_table_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, tb); break;
-        case 1: voice_program_table_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, tb); break;
-        case 2: voice_program_table_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, tb); break;
-        default: return (int)hipErrorInvalidValue;
+// Picks the geometry of a checked call and launches it: the image attached for this very program, or the interpreter variant
+// vp_variant names.
+int vp_launch_call(const VpRequest& r, VpCall& c)
+{
+    VpArgs& a = c.a;
+    const sig_voice_program_t& P = *r.program;
+    const int C = r.bus_channels;
+    const int64_t rows = (int64_t)r.block_frames * r.nblocks;
+    const int aligned = (r.voices % 4 == 0 && r.out_ld % 4 == 0 && reinterpret_cast<uintptr_t>(r.out) % 16 == 0) ? 4
+                      : (r.voices % 2 == 0 && r.out_ld % 2 == 0 && reinterpret_cast<uintptr_t>(r.out) % 8 == 0) ? 2 : 1;
+    int vpt = 1;
+    vp_geometry(a, aligned, vp_find_special(a, P, 4, C) != nullptr, vpt, a.span);
+    a.voice_tiles = sig_voice_tiles(r.voices, vpt);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, a.span), nwg)) return (int)hipErrorInvalidValue;
+    if (C > 0 && sig_bus::tiles_sum_in_workgroup(a.voice_tiles)) { a.bus_out = r.out; a.bus_out_ld = r.out_ld; }
+    hipStream_t s = static_cast<hipStream_t>(r.stream);
+    int err;
+    if (hipFunction_t fn = vp_find_special(a, P, vpt, C)) {                    // this very program, built as straight-line code
+        void* second = c.need.families() >= 2 ? (void*)&std::get<VpMixed>(c.extra)
+                     : c.need.uni() ? (void*)&std::get<VpUnison>(c.extra) : (void*)&std::get<VpTables>(c.extra);
+        void* params[] = {&a, second};                                         // (an image built for a mixed, a table or a unison program takes both, any other the first)
+        err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)c.table_lds, s, params, nullptr);
+    } else if (vpt == 4) {
+        return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
+    } else {
+        err = vp_with_family(vp_variant(c.need), [&](auto family) {
+            using F = decltype(family);
+            return VpLaunch<F>::run(a, std::get<typename F::Extra>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s);
+        });
     }
-    return sig_launch_status();
+    if (err || C == 0 || a.bus_out) return err;
+    switch (C) {
+        case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, r.out, r.out_ld, s);
+        default: return sig_bus::launch_partials<2>(a.partials, a.voice_tiles, rows, r.out, r.out_ld, s);
+    }
 }
 
-template <int VPT, bool SMALL>
-int vp_launch_shape_sink(const VpArgs& a, const VpTables& tb, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_shape_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, tb); break;
-        case 1: voice_program_shape_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, tb); break;
-        case 2: voice_program_shape_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, tb); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return sig_launch_status();
-}
-
-template <int VPT, bool SMALL>
-int vp_launch_res_sink(const VpArgs& a, int C, unsigned nwg, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_res_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a); break;
-        case 1: voice_program_res_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a); break;
-        case 2: voice_program_res_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return sig_launch_status();
-}
-
-template <int VPT, bool SMALL>
-int vp_launch_unison_sink(const VpArgs& a, const VpUnison& un, int C, unsigned nwg, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_unison_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a, un); break;
-        case 1: voice_program_unison_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a, un); break;
-        case 2: voice_program_unison_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a, un); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return sig_launch_status();
-}
-
-template <int VPT, bool SMALL>
-int vp_launch_blep_sink(const VpArgs& a, const VpUnison& un, int C, unsigned nwg, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_blep_kernel<VPT, SMALL, 0><<<nwg, 256, 0, s>>>(a, un); break;
-        case 1: voice_program_blep_kernel<VPT, SMALL, 1><<<nwg, 256, 0, s>>>(a, un); break;
-        case 2: voice_program_blep_kernel<VPT, SMALL, 2><<<nwg, 256, 0, s>>>(a, un); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return sig_launch_status();
-}
-
-template <int VPT, bool SMALL>
-int vp_launch_mixed_sink(const VpArgs& a, const VpMixed& mx, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    switch (C) {
-        case 0: voice_program_mixed_kernel<VPT, SMALL, 0><<<nwg, 256, lds, s>>>(a, mx); break;
-        case 1: voice_program_mixed_kernel<VPT, SMALL, 1><<<nwg, 256, lds, s>>>(a, mx); break;
-        case 2: voice_program_mixed_kernel<VPT, SMALL, 2><<<nwg, 256, lds, s>>>(a, mx); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    return sig_launch_status();
-}
-
-// the families of which every single-family variant has one
-int vp_families(const VpNeeds& n) { return (int)n.band + (int)n.pm + (int)n.table + (int)n.res + (int)n.uni; }
-
-template <int VPT>
-int vp_launch_file(const VpArgs& a, const VpTables& tb, const VpUnison& un, const VpMixed& mx, bool small_file, const VpNeeds& n, int C, unsigned nwg, size_t lds, hipStream_t s) {
-    // (a table never with a band or a PM carrier, a PM carrier never with a band, a resonant filter or a unison oscillator with none
-    // of them nor with each other: refused by every entry but sig_voice_program_mixed, whose combined programs run the MIXED variant)
-    if (vp_families(n) >= 2) return small_file ? vp_launch_mixed_sink<VPT, true>(a, mx, C, nwg, lds, s) : vp_launch_mixed_sink<VPT, false>(a, mx, C, nwg, lds, s);
-    if (n.blep) return small_file ? vp_launch_blep_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_blep_sink<VPT, false>(a, un, C, nwg, s);
-    if (n.uni) return small_file ? vp_launch_unison_sink<VPT, true>(a, un, C, nwg, s) : vp_launch_unison_sink<VPT, false>(a, un, C, nwg, s);
-    if (n.res) return small_file ? vp_launch_res_sink<VPT, true>(a, C, nwg, s) : vp_launch_res_sink<VPT, false>(a, C, nwg, s);
-    if (n.shape) return small_file ? vp_launch_shape_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_shape_sink<VPT, false>(a, tb, C, nwg, lds, s);
-    if (n.table) return small_file ? vp_launch_table_sink<VPT, true>(a, tb, C, nwg, lds, s) : vp_launch_table_sink<VPT, false>(a, tb, C, nwg, lds, s);
-    if (n.pm) return small_file ? vp_launch_sink<VPT, true, false, true>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, true>(a, C, nwg, s);
-    if (n.band) return small_file ? vp_launch_sink<VPT, true, true, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, true, false>(a, C, nwg, s);
-    return small_file ? vp_launch_sink<VPT, true, false, false>(a, C, nwg, s) : vp_launch_sink<VPT, false, false, false>(a, C, nwg, s);
+// The one body of sig_voice_program, _ex, _unison (allow_mixed false) and _mixed (true): everything but the three exclusivity
+// checks is the same for a program that combines the extension words.
+int vp_run(const VpRequest& r)
+{
+    VpCall c;
+    if (const int err = vp_check(r, c)) return err;
+    return c.empty ? 0 : vp_launch_call(r, c);
 }
 
 }  // namespace
@@ -1342,6 +459,15 @@ extern "C" int sig_voice_program_geometry(int32_t voices, int32_t block_frames, 
     int vpt = 1, span = 1;
     vp_geometry(a, store_aligned, specialised != 0, vpt, span);
     *voices_per_lane = vpt; *blocks_per_lane = span;
+    return 0;
+}
+
+extern "C" int sig_voice_program_variant(const sig_voice_program_t* program, int32_t* family, int32_t* small_file)
+{
+    SIG_CHECK_ARG(program && family && small_file && program->n_ins >= 1 && program->n_ins <= SIG_VP_MAX_INS);
+    const VpNeeds need = vp_needs(*program);
+    *family = vp_variant(need);                                                // (what vp_launch_call asks)
+    *small_file = fits_small(need) ? 1 : 0;
     return 0;
 }
 
@@ -1392,203 +518,14 @@ extern "C" int sig_voice_program_detach_all(void)
     return 0;
 }
 
-// The one body of sig_voice_program, _ex, _unison (allow_mixed false) and _mixed (true): everything but the three exclusivity
-// checks is the same for a program that combines the extension words.
-static int vp_run(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
-                  int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
-                  int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
-                  const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
-                  double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
-                  const sig_vp_tables_t* tables, const sig_vp_unison_t* unison, bool allow_mixed)
-{
-    SIG_CHECK_ARG(!unison || (unison->copies >= 1 && unison->copies <= SIG_UNISON_MAX_COPIES));
-    SIG_CHECK_ARG(program && rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
-    SIG_CHECK_ARG(out && (bus_channels == 0 || bus_channels == 1 || bus_channels == 2));
-    SIG_CHECK_ARG(bus_channels == 0 ? out_ld >= voices : (out_ld >= bus_channels && workspace != nullptr));
-    SIG_CHECK_ARG(bus_gains ? (bus_channels > 0 && bus_gains_ld >= voices) : bus_channels <= 1);
-    const sig_voice_program_t& P = *program;
-    SIG_CHECK_ARG(P.n_ins >= 1 && P.n_ins <= SIG_VP_MAX_INS && P.n_oscs >= 0 && P.n_oscs <= SIG_VP_MAX_OSCS);
-    SIG_CHECK_ARG(P.n_params >= 0 && P.n_params <= SIG_VP_MAX_PARAMS && P.n_filters >= 0 && P.n_filters <= SIG_VP_MAX_FILTERS);
-    SIG_CHECK_ARG(P.n_temps >= 0 && P.n_temps <= SIG_VP_MAX_TEMPS && P.depth >= 0 && P.depth <= P.n_filters);
-    SIG_CHECK_ARG(hist_blocks >= 0 && hist_blocks <= SIG_VP_MAX_HIST && (hist_blocks == 0 || hist_positions) && blocks_before >= 0);
-    const bool small = P.depth > 0 && block_frames < context;
-    SIG_CHECK_ARG(!small || (P.depth <= 2 && block_frames >= 16));            // (deeper cascades, or blocks so short that the reference's 16-entry block cache evicts what they read: the eager path)
-    SIG_CHECK_ARG(small || position == 0 || hist_blocks >= (P.depth > 1 ? 1 : 0));
-    SIG_CHECK_ARG(control_rows == (small ? 2 * nblocks : hist_blocks + 1 + nblocks));
-    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
-    VpArgs a{};
-    a.rate = (double)rate; a.position = position; a.N = block_frames; a.K = nblocks; a.ctx = context; a.voices = voices;
-    auto rows_ok = [&](const sig_vp_rows& r, bool optional) {
-        if (!r.ptr) return optional;
-        return (r.col_stride | 1) == 1 && (r.rows == 1 || r.rows == control_rows);
-    };
-    VpNeeds need{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, false, false, false, false, false, false};
-    // the tables: together inside the cap (one workgroup's LDS holds them all); a power of two where an OscTable word reads one (below)
-    const int n_tables = tables ? tables->n_tables : 0;
-    SIG_CHECK_ARG(n_tables >= 0 && n_tables <= SIG_VP_MAX_TABLES);
-    size_t table_lds = 0;
-    for (int k = 0, points = 0; k < n_tables; ++k) {
-        const auto& t = tables->table[k];
-        SIG_CHECK_ARG(t.ptr != nullptr && t.points >= 2 && t.waves >= 1 &&
-                      (int64_t)t.points * t.waves <= SIG_TABLE_MAX_POINTS - points);
-        points += t.points * t.waves;
-        table_lds += (size_t)(t.points + 1) * t.waves * sizeof(float);
-    }
-    bool has_adsr = false;
-    a.n_ins = P.n_ins;
-    for (int k = 0; k < P.n_ins; ++k) {
-        const sig_vp_ins& x = P.ins[k];
-        SIG_CHECK_ARG(x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
-                      x.c >= ((x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE || x.op == SIG_VP_FILTERQ || x.op == SIG_VP_OSCUNI || x.op == SIG_VP_OSCBLEP) ? -1 : 0) && x.c <= 15);
-        switch (x.op) {
-            case SIG_VP_OSCTABLE:
-                SIG_CHECK_ARG(x.a < P.n_oscs && x.b < n_tables && x.c < P.n_params);
-                SIG_CHECK_ARG((tables->table[x.b].points & (tables->table[x.b].points - 1)) == 0);     // the oscillator wraps with a mask
-                break;
-            case SIG_VP_SHAPE: SIG_CHECK_ARG(x.b < n_tables && x.c < P.n_params); break;
-            case SIG_VP_OSC: SIG_CHECK_ARG(x.a < P.n_oscs && x.kind <= SIG_OSC_TRIANGLE); break;
-            case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
-            case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
-            case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
-            case SIG_VP_OSCUNI:
-                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params && x.kind <= SIG_OSC_TRIANGLE);
-                break;
-            case SIG_VP_OSCBLEP:                                               // OscUni's operands; no Sine
-                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params &&
-                              x.kind >= SIG_OSC_SQUARE && x.kind <= SIG_OSC_TRIANGLE);
-                break;
-            case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
-            case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
-            case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
-            case SIG_VP_MIX: SIG_CHECK_ARG(x.a < P.n_temps && x.b < P.n_params); break;
-            case SIG_VP_NOISE: SIG_CHECK_ARG(x.a < 2); break;
-            default: break;
-        }
-        if (x.op == SIG_VP_AMP || x.op == SIG_VP_ADSR || x.op == SIG_VP_NOISE) need.ext = true;
-        if (x.op == SIG_VP_ADSR) has_adsr = true;
-        if (x.op == SIG_VP_BAND) need.band = true;
-        if (x.op == SIG_VP_OSCPM) need.pm = true;
-        if (x.op == SIG_VP_OSCTABLE || x.op == SIG_VP_SHAPE) need.table = true;
-        if (x.op == SIG_VP_SHAPE) need.shape = true;
-        if (x.op == SIG_VP_FILTERQ) need.res = true;
-        if (x.op == SIG_VP_OSCUNI) need.uni = true;
-        if (x.op == SIG_VP_OSCBLEP) need.uni = need.blep = true;       // (the unison family: the same copies, the same exclusions)
-    }
-    if (!allow_mixed) {
-        SIG_CHECK_ARG(!(need.uni && (need.band || need.pm || need.table || need.res)));
-        SIG_CHECK_ARG(!(need.res && (need.band || need.pm || need.table)));
-        SIG_CHECK_ARG(!(need.band && need.pm) && !(need.table && (need.band || need.pm)));   // (no single-family variant with two of them; the engine keeps such a graph per node unless asked for mixed programs)
-    }
-    const bool mixed = vp_families(need) >= 2;
-    VpTables tb{};
-    for (int k = 0; k < n_tables; ++k) { tb.ptr[k] = tables->table[k].ptr; tb.T[k] = tables->table[k].points; tb.W[k] = tables->table[k].waves; }
-    if (!need.table) table_lds = 0;
-    VpUnison un{};
-    if (need.uni) {
-        un.copies = unison->copies;
-        for (int u = 0; u < un.copies; ++u) { un.detune[u] = unison->detune[u]; un.offset[u] = unison->offset[u]; }
-    }
-    VpMixed mx{};
-    if (mixed) {
-        for (int k = 0; k < SIG_VP_MAX_TABLES; ++k) { mx.ptr[k] = need.table ? tb.ptr[k] : nullptr; mx.T[k] = tb.T[k]; mx.W[k] = tb.W[k]; }     // (no table word: nothing is staged)
-        mx.copies = un.copies;
-        for (int u = 0; u < un.copies; ++u) { mx.detune[u] = un.detune[u]; mx.offset[u] = un.offset[u]; }
-    }
-    SIG_CHECK_ARG(vp_encode(P, a.code));
-    a.n_oscs = P.n_oscs; a.n_params = P.n_params; a.n_filters = P.n_filters;
-    for (int k = 0; k < P.n_oscs; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.hertz[k], false) && rows_ok(P.phase[k], true));
-        a.hertz[k] = Rows{P.hertz[k].ptr, P.hertz[k].col_stride, P.hertz[k].rows};
-        a.phase[k] = Rows{P.phase[k].ptr, P.phase[k].col_stride, P.phase[k].ptr ? P.phase[k].rows : 1};
-    }
-    for (int k = 0; k < P.n_params; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.params[k], false));
-        a.params[k] = Rows{P.params[k].ptr, P.params[k].col_stride, P.params[k].rows};
-    }
-    // filter slots: a Filter instruction runs a LowPass / HighPass slot; a Band instruction at slot f runs the pair f, f + 1 (its
-    // low and high rows), of one band type and one level, which the kernel finds by pairing every run of band slots from its start
-    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second, 4: resonant (one FilterQ word)
-    for (int k = 0; k < P.n_ins; ++k) {
-        const sig_vp_ins& x = P.ins[k];
-        if (x.op == SIG_VP_FILTER) {
-            SIG_CHECK_ARG(role[x.a] == 0 || role[x.a] == 1);
-            role[x.a] = 1;
-        } else if (x.op == SIG_VP_FILTERQ) {
-            SIG_CHECK_ARG(role[x.a] == 0);
-            role[x.a] = 4;
-        } else if (x.op == SIG_VP_BAND) {
-            SIG_CHECK_ARG((role[x.a] == 0 || role[x.a] == 2) && (role[x.a + 1] == 0 || role[x.a + 1] == 3));
-            role[x.a] = 2; role[x.a + 1] = 3;
-        }
-    }
-    for (int k = 0, run = 0; k < P.n_filters; ++k) {
-        const bool band = P.filter_type[k] == SIG_FILT_BANDPASS || P.filter_type[k] == SIG_FILT_BANDSTOP;
-        run = band ? run + 1 : 0;
-        if (role[k] == 1) SIG_CHECK_ARG(P.filter_type[k] == SIG_FILT_LOWPASS || P.filter_type[k] == SIG_FILT_HIGHPASS);
-        else if (role[k] == 2) SIG_CHECK_ARG(band && run % 2 == 1 && P.filter_type[k + 1] == P.filter_type[k] &&
-                                             P.filter_level[k + 1] == P.filter_level[k]);
-        else if (role[k] == 3) SIG_CHECK_ARG(band && run % 2 == 0);
-        const bool resonant = P.filter_type[k] == SIG_FILT_RES_LOWPASS || P.filter_type[k] == SIG_FILT_RES_HIGHPASS;
-        SIG_CHECK_ARG(resonant == (role[k] == 4));                             // a resonant slot and its FilterQ word go together
-    }
-    for (int k = 0; k < P.n_filters; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_RES_HIGHPASS);
-        a.cutoff[k] = Rows{P.cutoff[k].ptr, P.cutoff[k].col_stride, P.cutoff[k].rows};
-        a.ftype[k] = P.filter_type[k];
-        SIG_CHECK_ARG(P.filter_level[k] >= 1 && P.filter_level[k] <= P.depth);
-        a.flevel[k] = P.filter_level[k];
-    }
-    if (has_adsr) {
-        SIG_CHECK_ARG(sig_env::load_rows(P.adsr, P.adsr_stride, a.adsr));
-        a.has_adsr = 1;
-    }
-    a.seeds[0] = P.noise_seed[0]; a.seeds[1] = P.noise_seed[1];
-    a.depth = P.depth; a.small = small ? 1 : 0; a.blocks_before = blocks_before;
-    a.hist = small ? 0 : hist_blocks;
-    for (int k = 0; k < a.hist; ++k) {
-        SIG_CHECK_ARG(hist_positions[k] >= 0 && hist_positions[k] < (k + 1 < a.hist ? hist_positions[k + 1] : position));
-        a.hist_pos[k] = hist_positions[k];
-    }
-    a.status = status;
-    const int64_t rows = (int64_t)block_frames * nblocks;
-    if (bus_channels > 0) {
-        a.pan = bus_gains; a.pan_ld = bus_gains_ld; a.partials = workspace; a.rows = rows;
-    } else {
-        a.out = out; a.out_ld = out_ld;
-    }
-    const int aligned = (voices % 4 == 0 && out_ld % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) ? 4
-                      : (voices % 2 == 0 && out_ld % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) ? 2 : 1;
-    int vpt = 1;
-    vp_geometry(a, aligned, vp_find_special(a, P, 4, bus_channels) != nullptr, vpt, a.span);
-    const bool small_file = fits_small(need);
-    a.voice_tiles = sig_voice_tiles(voices, vpt);
-    unsigned nwg;
-    if (!sig_workgroups(sig_span_waves(a.voice_tiles, a.K, a.span), nwg)) return (int)hipErrorInvalidValue;
-    if (bus_channels > 0 && sig_bus::tiles_sum_in_workgroup(a.voice_tiles)) { a.bus_out = out; a.bus_out_ld = out_ld; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int err;
-    if (hipFunction_t fn = vp_find_special(a, P, vpt, bus_channels)) {         // this very program, built as straight-line code
-        void* params[] = {&a, mixed ? (void*)&mx : need.uni ? (void*)&un : (void*)&tb};     // (an image built for a mixed, a table or a unison program takes both, any other the first)
-        err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)table_lds, s, params, nullptr);
-    } else if (vpt == 4) {
-        return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
-    } else if (vpt == 2) err = vp_launch_file<2>(a, tb, un, mx, small_file, need, bus_channels, nwg, table_lds, s);
-    else err = vp_launch_file<1>(a, tb, un, mx, small_file, need, bus_channels, nwg, table_lds, s);
-    if (err || bus_channels == 0 || a.bus_out) return err;
-    switch (bus_channels) {
-        case 1: return sig_bus::launch_partials<1>(a.partials, a.voice_tiles, rows, out, out_ld, s);
-        default: return sig_bus::launch_partials<2>(a.partials, a.voice_tiles, rows, out, out_ld, s);
-    }
-}
-
 extern "C" int sig_voice_program(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
                                  int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,
                                  int32_t hist_blocks, const int64_t* hist_positions, int32_t blocks_before,
                                  const double* bus_gains, int64_t bus_gains_ld, int32_t bus_channels,
                                  double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream)
 {
-    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
-                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, nullptr, nullptr, false);
+    return vp_run({program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                   blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, nullptr, nullptr, false});
 }
 
 extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
@@ -1598,8 +535,8 @@ extern "C" int sig_voice_program_ex(const sig_voice_program_t* program, int32_t 
                                     double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                                     const sig_vp_tables_t* tables)
 {
-    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
-                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, nullptr, false);
+    return vp_run({program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                   blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, nullptr, false});
 }
 
 extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
@@ -1609,8 +546,8 @@ extern "C" int sig_voice_program_unison(const sig_voice_program_t* program, int3
                                         double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                                         const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
 {
-    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
-                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, false);
+    return vp_run({program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                   blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, false});
 }
 
 // sig_voice_program_unison for programs that combine two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni: the MIXED
@@ -1622,7 +559,7 @@ extern "C" int sig_voice_program_mixed(const sig_voice_program_t* program, int32
                                         double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream,
                                         const sig_vp_tables_t* tables, const sig_vp_unison_t* unison)
 {
-    return vp_run(program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
-                  blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, true);
+    return vp_run({program, rate, position, block_frames, nblocks, context, voices, control_rows, hist_blocks, hist_positions,
+                   blocks_before, bus_gains, bus_gains_ld, bus_channels, workspace, out, out_ld, status, stream, tables, unison, true});
 }
 #endif  // SIG_VP_STATIC_CODE

@@ -24,7 +24,7 @@ from . import _native
 
 CSRC = pathlib.Path(__file__).resolve().parent / 'csrc'
 CACHE = pathlib.Path(os.environ.get('SIG_SPECIALISE_CACHE') or pathlib.Path(__file__).resolve().parent / '_specialised')
-SOURCES = ('voice_program.hip', 'control_program.hip', 'sig_adsr.h', 'sig_biquad.h', 'sig_bus_tile.h', 'sig_noise.h', 'sig_osc.h', 'sig_table.h', 'sig_common.h', '../../include/signals_amd.h')
+SOURCES = ('voice_program.hip', 'sig_vp_machine.h', 'control_program.hip', 'sig_adsr.h', 'sig_biquad.h', 'sig_bus_tile.h', 'sig_noise.h', 'sig_osc.h', 'sig_table.h', 'sig_common.h', '../../include/signals_amd.h')
 
 _attached: set = set()
 _failed: set = set()

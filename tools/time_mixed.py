@@ -6,7 +6,7 @@ voice-program interpreter, and the kernel specialised for the program.  Every ro
 time each route in turn over a window of `window` seconds of back-to-back batches, so that clock and temperature drift hit all three
 alike.  Attached specialised kernels are process-wide and found by the program's words, so every warm-up and every window switches
 them on for the specialised route and off for the other two (sig_voice_program_use_attached): the interpreter route runs
-voice_program_mixed_kernel.  Per patch one JSON object:
+voice_program_kernel<.., vp_family::mixed>.  Per patch one JSON object:
 the median over the rounds per route, the spread (max - min over the rounds, relative to the median) per route, and whether the
 interpreter beats the baseline by more than the larger of the two spreads.
 
