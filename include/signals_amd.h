@@ -38,14 +38,19 @@ enum { SIG_OSC_SINE = 0, SIG_OSC_SQUARE = 1, SIG_OSC_SAWTOOTH = 2, SIG_OSC_TRIAN
 /* critical-frequency filter types: fx.py:68-72 (only lp/hp are live in the reference, fx.py:142-151) */
 enum { SIG_FILT_LOWPASS = 0, SIG_FILT_HIGHPASS = 1, SIG_FILT_BANDPASS = 2, SIG_FILT_BANDSTOP = 3,
        /* filter slots of a voice program that a FILTERQ word runs: the resonant low-pass / high-pass of chain/ext.py */
-       SIG_FILT_RES_LOWPASS = 4, SIG_FILT_RES_HIGHPASS = 5 };
+       SIG_FILT_RES_LOWPASS = 4, SIG_FILT_RES_HIGHPASS = 5,
+       /* the RBJ equaliser biquads of chain/ext.py EqFilter: sig_biquad_coldstart_eq's types, and the filter slots of a voice program
+        * that a FILTEREQ word runs */
+       SIG_FILT_EQ_BANDPASS = 6, SIG_FILT_EQ_NOTCH = 7, SIG_FILT_EQ_ALLPASS = 8, SIG_FILT_EQ_PEAKING = 9, SIG_FILT_EQ_LOWSHELF = 10,
+       SIG_FILT_EQ_HIGHSHELF = 11 };
 
 /* element-wise effects: fx.py:35-60 */
 enum { SIG_EW_GAIN = 0, SIG_EW_MIX = 1, SIG_EW_RINGMOD = 2, SIG_EW_AMP = 3 };
 
 /* bits OR-ed into the optional device status word by kernels (never cleared by them) */
 enum { SIG_STATUS_BAD_CUTOFF = 1,     /* Wn <= 0 or >= 1: scipy raises ValueError (fx.py:99-102) */
-       SIG_STATUS_BAD_RESONANCE = 2 };  /* a resonant filter's q that is not finite and > 0 (build-defined, chain/ext.py ResonantFilter) */
+       SIG_STATUS_BAD_RESONANCE = 2,    /* a resonant filter's q that is not finite and > 0 (build-defined, chain/ext.py ResonantFilter) */
+       SIG_STATUS_BAD_GAIN = 4 };       /* an equaliser filter's gain (dB) that is not finite (build-defined, chain/ext.py EqFilter) */
 
 int sig_abi_version(void);
 
@@ -205,6 +210,32 @@ int sig_biquad_coldstart_q(int type, int32_t rate, int64_t position,
                            const void* in, int64_t in_ld, int64_t in_history,
                            void* out, int64_t out_ld, int32_t dtype,
                            int32_t* status, void* stream);
+
+/* sig_biquad_coldstart_q for the RBJ equaliser biquads of chain/ext.py (ResonantBandPass, Notch, AllPass, Peaking, LowShelf,
+ * HighShelf; build-defined): three free numerator taps and, for the last three, a gain control.  Per voice and block, in f64:
+ *   wn, k and d = 1 / q as sig_biquad_coldstart_q;  A = exp(gain ln(10) / 40);  g = sqrt(A) d;  sos = [b nrm, 1, a1 nrm, a2 nrm]
+ *   EQ_BANDPASS  b = (d k, 0, -d k)                                   a1 = 2 (k k - 1), a2 = 1 - d k + k k, 1 / nrm = 1 + d k + k k
+ *   EQ_NOTCH     b = (1 + k k, 2 (k k - 1), 1 + k k)                  a and nrm as EQ_BANDPASS
+ *   EQ_ALLPASS   b = (1 - d k + k k, 2 (k k - 1), 1 + d k + k k)      a and nrm as EQ_BANDPASS
+ *   EQ_PEAKING   b = (1 + d A k + k k, 2 (k k - 1), 1 - d A k + k k)  a1 = 2 (k k - 1), a2 = 1 - (d / A) k + k k, 1 / nrm = 1 + (d / A) k + k k
+ *   EQ_LOWSHELF  b = A (1 + g k + A k k, 2 (A k k - 1), 1 - g k + A k k)   a1 = 2 (k k - A), a2 = A - g k + k k, 1 / nrm = A + g k + k k
+ *   EQ_HIGHSHELF b = A (A + g k + k k, 2 (k k - A), A - g k + k k)         a1 = 2 (A k k - 1), a2 = 1 - g k + A k k, 1 / nrm = 1 + g k + A k k
+ * (the cookbook's BPF with a constant 0 dB peak, notch, APF, peakingEQ, lowShelf, highShelf), then the general transposed direct
+ * form II  y = b0 x + z0;  z0 = b1 x - a1 y + z1;  z1 = b2 x - a2 y  from zero state over [<= context rows | block], buffers and block
+ * semantics as sig_biquad_coldstart.  resonance and gain: f64 (blocks, voices | 1) rows like sig_biquad_coldstart_q's resonance, each
+ * per block on its own; resonance NULL: unplugged = 1/sqrt2; gain (dB) NULL: unplugged = 0 dB; gain is not read for the first three
+ * types (its stride and row count are still checked).  A q that is not finite and > 0 sets SIG_STATUS_BAD_RESONANCE, a gain that is
+ * not finite SIG_STATUS_BAD_GAIN, a cutoff outside (0, rate / 2) SIG_STATUS_BAD_CUTOFF; that voice's rows (of that block) are NaN;
+ * voices past `voices` never set a bit.  type: SIG_FILT_EQ_BANDPASS .. SIG_FILT_EQ_HIGHSHELF.  Argument errors:
+ * hipErrorInvalidValue, nothing launched. */
+int sig_biquad_coldstart_eq(int type, int32_t rate, int64_t position,
+                            int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                            const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
+                            const double* resonance, int32_t resonance_stride, int32_t resonance_blocks,
+                            const double* gain, int32_t gain_stride, int32_t gain_blocks,
+                            const void* in, int64_t in_ld, int64_t in_history,
+                            void* out, int64_t out_ld, int32_t dtype,
+                            int32_t* status, void* stream);
 
 /* sig_biquad_coldstart whose stored rows are multiplied by a per-voice ADSR envelope evaluated at the row's
  * time (f32 buffers): RingMod(Filter(x), ADSR) -- fx.py:43-46 over fx.py:85-121 and the envelope of sig_adsr --
@@ -651,6 +682,13 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *   OSCBLEP acc = band-limited oscillator (sig_osc_bank_blep's expression, m = t - floor(t) as one v_fract_f64) of kind `kind` (not
  *          SIG_OSC_SINE) with OSCUNI's operands: oscillator slot a, the copies of unison slot b = 0, spread = params[c], c == -1:
  *          unplugged = 0.  A word of the unison family: it reads the `unison` argument, and is refused wherever OSCUNI is
+ *   FILTEREQ acc = equaliser filter slot a applied to acc (sig_biquad_coldstart_eq's design and recurrence): the slot's filter_type
+ *          is SIG_FILT_EQ_BANDPASS .. SIG_FILT_EQ_HIGHSHELF, its cutoff rows as for FILTER, q = params[c] and gain (dB) = params[b]
+ *          read per block with the cutoff, c == -1: unplugged = 1/sqrt2, b == -1: unplugged = 0 dB (the only word whose b may be -1;
+ *          gain is not read for the three types without one).  One FILTEREQ word per slot; FILTER and FILTERQ words run in the same
+ *          program.  A word of the resonant family: refused wherever FILTERQ is, and launched by kernels of its own (the resonant and
+ *          the mixed variant once more with the general numerator), so that programs without the word run the code they ran before;
+ *          sig_voice_program_variant still answers RESONANT or MIXED
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -670,13 +708,15 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  * bus_gains[c, v] * sample (bus_gains NULL: mono sum), float64 accumulation in a fixed order; workspace of
  * sig_fused_voice_bus_workspace(voices, rows, bus_channels) bytes.  f64 arithmetic, no float32 rounding between the nodes.
  * A rejected filter design (fx.py:99-102) gives NaN rows and sets SIG_STATUS_BAD_CUTOFF; a FILTERQ slot's q that is not finite and
- * > 0 likewise and sets SIG_STATUS_BAD_RESONANCE (never for a voice past `voices`). */
+ * > 0 likewise and sets SIG_STATUS_BAD_RESONANCE, a FILTEREQ slot's gain that is not finite SIG_STATUS_BAD_GAIN (never for a voice past
+ * `voices`). */
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
-       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16, SIG_VP_OSCBLEP = 17 };
+       SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16, SIG_VP_OSCBLEP = 17,
+       SIG_VP_FILTEREQ = 18 };
 enum { SIG_VP_MAX_TABLES = 2, SIG_VP_MAX_UNISON = 1 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI, OSCBLEP: c may be -1 */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI, OSCBLEP: c may be -1; FILTEREQ: c and b may */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];

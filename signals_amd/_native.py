@@ -17,10 +17,13 @@ LIB_PATH = pathlib.Path(os.environ.get('SIG_LIB_PATH') or pathlib.Path(__file__)
 
 F32, F64 = 0, 1
 OSC_KINDS = {'Sine': 0, 'Square': 1, 'Sawtooth': 2, 'Triangle': 3}
-FILT_TYPES = {'lp': 0, 'hp': 1, 'bp': 2, 'bs': 3, 'rlp': 4, 'rhp': 5}     # rlp / rhp: a voice program's resonant slots (SIG_FILT_RES_*)
+FILT_TYPES = {'lp': 0, 'hp': 1, 'bp': 2, 'bs': 3, 'rlp': 4, 'rhp': 5,     # rlp / rhp: a voice program's resonant slots (SIG_FILT_RES_*)
+              'eqbp': 6, 'eqnotch': 7, 'eqap': 8, 'eqpeak': 9, 'eqls': 10, 'eqhs': 11}    # SIG_FILT_EQ_*: the equaliser biquads (chain/ext.py EqFilter)
+EQ_GAIN_TYPES = ('eqpeak', 'eqls', 'eqhs')  # the equaliser types that read a gain
 EW_OPS = {'Gain': 0, 'Mix': 1, 'RingMod': 2, 'Amp': 3}
 STATUS_BAD_CUTOFF = 1
 STATUS_BAD_RESONANCE = 2
+STATUS_BAD_GAIN = 4
 ABI_VERSION = 7
 SINE_FAST_MAX_CYCLES = 2.0 ** 26     # sig_osc.h kSineFastMaxT: |t| up to which the fused Sine kernels advance the phase incrementally
 
@@ -50,12 +53,13 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15, 'OscUni': 16, 'OscBlep': 17}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15, 'OscUni': 16, 'OscBlep': 17, 'FilterEq': 18}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 VP_MAX_TABLES = 2
 VP_TABLE_OPS = ('OscTable', 'Shape')        # the instructions of the table variant (SIG_VP_S_TAB): table slot b, select = parameter slot c | -1
 VP_RES_OPS = ('FilterQ',)                   # the instruction of the resonant variant (SIG_VP_S_RES): filter slot a, q = parameter slot c | -1
+VP_EQ_OPS = ('FilterEq',)                   # FilterQ on an equaliser slot (ext.py EqFilter; SIG_VP_S_RES and SIG_VP_S_EQ): gain = parameter slot b | -1 too; the same family
 VP_UNI_OPS = ('OscUni',)                    # the instruction of the unison variant (SIG_VP_S_UNI): oscillator slot a, unison slot b = 0, spread = parameter slot c | -1
 VP_BLEP_OPS = ('OscBlep',)                  # OscUni with the band-limited waveforms (ext.py BlepOsc; SIG_VP_S_UNI and SIG_VP_S_BLEP): the same operands, the same family
 VP_MAX_UNISON = 1                           # SIG_VP_MAX_UNISON: unison slots of a voice program (one `copies` array per launch)
@@ -131,6 +135,7 @@ def _argtypes() -> dict:
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
+        'sig_biquad_coldstart_eq': cold + [dp, i32, i32] * 3 + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
         'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
         'sig_band_coldstart': cold + [dp, i32, dp, i32] + window + [vp, i64, i32, vp, vp],
@@ -531,6 +536,25 @@ def biquad_coldstart_q(btype: str, rate: int, position: int, block_frames: int, 
     _check(lib().sig_biquad_coldstart_q(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
                                         *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, in_ptr, buf.stride(0), history,
                                         out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), 'sig_biquad_coldstart_q')
+    return out
+
+
+def biquad_coldstart_eq(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
+                        cutoff: torch.Tensor, resonance: torch.Tensor | None, gain: torch.Tensor | None, buf: torch.Tensor, history: int,
+                        out: torch.Tensor, status: torch.Tensor | None = None) -> torch.Tensor:
+    """`biquad_coldstart_q` for the equaliser biquads (sig_biquad_coldstart_eq; btype 'eqbp' | 'eqnotch' | 'eqap' | 'eqpeak' | 'eqls' |
+    'eqhs').  cutoff: f64 (1|nblocks, V); resonance and gain (dB): f64 (1|nblocks, V|1), each per block on its own; None: unplugged
+    = 1/sqrt2 and 0 dB."""
+    _gpu(cutoff, resonance, gain, buf, out, status)
+    _audio(buf, 'biquad in')
+    _audio(out, 'biquad out')
+    voices = out.shape[1]
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
+    q = (None, 0, 1) if resonance is None else _block_rows(resonance, 'resonance', nblocks, voices, broadcast=True)
+    g = (None, 0, 1) if gain is None else _block_rows(gain, 'gain', nblocks, voices, broadcast=True)
+    _check(lib().sig_biquad_coldstart_eq(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
+                                         *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, *g, in_ptr, buf.stride(0), history,
+                                         out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), 'sig_biquad_coldstart_eq')
     return out
 
 
@@ -1098,7 +1122,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   unison=None) -> torch.Tensor:
     """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison, or -- a program of two or more families, `vp_families` -- sig_voice_program_mixed; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni and OscBlep words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
-    'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
+    'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows; 'eqbp' ... 'eqhs': an equaliser slot, run by a FilterEq word whose c names the q rows and whose b the gain rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
     tensors = [t for pair in oscs for t in pair] + list(params) + [f[0] for f in filters] + list((adsr or {}).values())
     _gpu(out, bus_gains, workspace, status, *tensors, *(tables or ()))
@@ -1162,13 +1186,13 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
 
 def vp_families(code: list) -> tuple:
     """the families (keys of VP_FAMILIES) a program given as (op name, kind, a, b, c) tuples has words of"""
-    ops = {'OscUni' if op in VP_BLEP_OPS else op for op, *_ in code}           # (OscBlep: a word of the unison family)
+    ops = {'OscUni' if op in VP_BLEP_OPS else 'FilterQ' if op in VP_EQ_OPS else op for op, *_ in code}   # (OscBlep: a word of the unison family; FilterEq: of the resonant family)
     return tuple(name for name, words in VP_FAMILIES.items() if ops & set(words))
 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | (b << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's, FilterQ's, OscUni's and OscBlep's c = -1: 15)
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | ((b & 15) << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's, FilterQ's, OscUni's, OscBlep's and FilterEq's c = -1: 15; FilterEq's b too)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

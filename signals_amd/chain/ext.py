@@ -3,6 +3,7 @@ voice sum (`shape.Flatten`) but it sums over frames and crashes; these nodes are
 configurations need and are pinned against `oracle/chain_ref.py` ("parity unpinned" by the
 reference itself)."""
 import abc
+import enum
 import typing
 
 import attr
@@ -479,7 +480,7 @@ class ResonantFilter(fx.CritFilter, abc.ABC):
     Out of scope: the closed-form, row-walker, cascade, enveloped-filter and bus-over-filter fused kernels (none matches the node; the
     voice program is its fast route); the node inside a block-rate control path (the batched engine answers NotBatchable with the
     reason and the graph keeps the eager path); a combination with a band filter, a phase-modulation oscillator, a wavetable
-    oscillator or a waveshaper in one voice program (such a graph stays one kernel per node unless the renderer is given mixed_programs=True); band-pass, notch and peaking responses;
+    oscillator or a waveshaper in one voice program (such a graph stays one kernel per node unless the renderer is given mixed_programs=True); band-pass, notch and peaking responses (those are `EqFilter`'s);
     a frame-rate cutoff or q; self-oscillation (q = inf); carried state or a longer context."""
     cutoff: Receiver.BoundPort = port('cutoff')
     resonance: Receiver.BoundPort = port('resonance')
@@ -503,6 +504,121 @@ class ResonantHighPass(ResonantFilter):
 
     def type(self) -> fx.CritFilter.Type:
         return self.Type.high_pass
+
+
+class EqFilter(ResonantFilter, abc.ABC):
+    """The RBJ equaliser biquads: band-pass with a constant 0 dB peak (`ResonantBandPass`), `Notch`, `AllPass`, and -- with a third
+    control, `gain` in dB -- `Peaking`, `LowShelf`, `HighShelf`: a peaking band to shape a formant, shelves to tilt a voice, a notch or
+    an all-pass chain swept by an LFO (the phaser).  `ResonantFilter`'s bilinear transform, s -> (1 - 1/z) / (k (1 + 1/z)), of the
+    cookbook's analogue prototypes (BPF, notch, APF, peakingEQ, lowShelf, highShelf), with three free numerator taps.
+    Ports: `input` at frame rate; `cutoff` (Hz: the centre, notch, or shelf midpoint frequency) and `resonance` (q) at block rate, both
+    exactly as on `ResonantFilter` (an unplugged `resonance` means 1/sqrt2, a bad value the same errors, a narrow control the same
+    IndexError); the three gain classes add `gain` (dB) at block rate.  Per voice and block, in float64:
+        wn, k = tan(pi * wn / 2) and d = 1 / q as `ResonantFilter`;  A = exp(gain * ln(10) / 40);  g = sqrt(A) * d
+        sos = [b * nrm, 1, a1 * nrm, a2 * nrm]
+        ResonantBandPass  b = (d*k, 0, -d*k)                                    a1 = 2*(k*k - 1), a2 = 1 - d*k + k*k, 1/nrm = 1 + d*k + k*k
+        Notch             b = (1 + k*k, 2*(k*k - 1), 1 + k*k)                   a and nrm as ResonantBandPass
+        AllPass           b = (1 - d*k + k*k, 2*(k*k - 1), 1 + d*k + k*k)       a and nrm as ResonantBandPass
+        Peaking           b = (1 + d*A*k + k*k, 2*(k*k - 1), 1 - d*A*k + k*k)   a1 = 2*(k*k - 1), a2 = 1 - (d/A)*k + k*k, 1/nrm = 1 + (d/A)*k + k*k
+        LowShelf          b = A*(1 + g*k + A*k*k, 2*(A*k*k - 1), 1 - g*k + A*k*k)   a1 = 2*(k*k - A), a2 = A - g*k + k*k, 1/nrm = A + g*k + k*k
+        HighShelf         b = A*(A + g*k + k*k, 2*(k*k - A), A - g*k + k*k)         a1 = 2*(A*k*k - 1), a2 = 1 - g*k + A*k*k, 1/nrm = 1 + g*k + A*k*k
+    then `CritFilter._filter` exactly as for `ResonantFilter`: zero state over [<= 100 context rows | block], one section, sosfilt's
+    transposed direct form II  y = b0 x + z0; z0 = b1 x - a1 y + z1; z1 = b2 x - a2 y,  every control read once per block at the block's
+    position (kernel: sig_biquad_coldstart_eq; restated in numpy by tests/eq_reference.py).  `Peaking` at 0 dB has b = a: the input.
+    An unplugged or disabled `gain` means 0 dB -- the ordinary zeros((1, 1)) of an unplugged port.  A plugged gain that is NaN or +-inf
+    is an error like a bad q: the voice's rows are NaN and `runtime.check_status()` raises ValueError('...: filter gain must be finite').
+    `gain` narrower than the request raises the IndexError of a narrow `cutoff`.
+    The inherited limit: the 100-frame cold start truncates a ring of about q * rate / (pi * cutoff)
+    frames, as for `ResonantFilter`.  It applies most to a high-q `Notch` and `ResonantBandPass` at low cutoffs, whose ring IS the
+    response: a notch at 100 Hz and q = 8 rings for some 1200 frames at 48 kHz, and what 100 frames of it reject is far from the
+    streaming filter's null.  That is the reference's block semantics, not a defect of this node.
+    Out of scope: a frame-rate cutoff, q or gain; the closed-form, row-walker, cascade, enveloped-filter and bus-over-filter fused
+    kernels (none matches the node; the voice program is its fast route, through kernels of its own beside the resonant and the mixed
+    variant); the node inside a block-rate control path (the batched engine answers NotBatchable with the reason and the graph keeps
+    the eager path); a combination with a band filter, a phase-modulation oscillator, a wavetable oscillator, a waveshaper or a unison
+    oscillator in one voice program unless the renderer is given mixed_programs=True; the constant-skirt band-pass; the shelf-slope S
+    parametrisation (the shelves take q); carried state or a longer context."""
+
+    class Type(str, enum.Enum):
+        """the equaliser designs: SIG_FILT_EQ_* by their _native.FILT_TYPES names"""
+        band_pass = 'eqbp'
+        notch = 'eqnotch'
+        all_pass = 'eqap'
+        peaking = 'eqpeak'
+        low_shelf = 'eqls'
+        high_shelf = 'eqhs'
+
+        def __str__(self) -> str:
+            return str(self.value)
+
+        @property
+        def is_band(self) -> bool:
+            return False
+
+        @property
+        def has_gain(self) -> bool:
+            return self.value in _native.EQ_GAIN_TYPES
+
+    def gain_port(self):
+        """the `gain` port of the three gain classes, None for the others"""
+        return getattr(self, 'gain', None) if self.type().has_gain else None
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        hertz = as_control(self.cutoff.forward_at_block_rate(request))
+        src = self.resonance.sig
+        q = None if src is None or not src.get_state().enabled else as_control(self.resonance.forward_at_block_rate(request))
+        port_ = self.gain_port()
+        gain = None
+        if port_ is not None and port_.sig is not None and port_.sig.get_state().enabled:
+            gain = as_control(port_.forward_at_block_rate(request))
+        return self._filter(request, hertz, resonant=True, resonance=q, equaliser=str(self.type()), gain=gain)
+
+
+class ResonantBandPass(EqFilter):
+    """`EqFilter` with b = (d*k, 0, -d*k) * nrm: the band-pass whose peak is 0 dB at every q"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.band_pass
+
+
+class Notch(EqFilter):
+    """`EqFilter` with b = (1 + k*k, 2*(k*k - 1), 1 + k*k) * nrm: a null at the cutoff, unity gain away from it"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.notch
+
+
+class AllPass(EqFilter):
+    """`EqFilter` with b = (a2, a1, 1) (the denominator reversed): unit magnitude, a phase turn of 2 pi around the cutoff"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.all_pass
+
+
+class GainEqFilter(EqFilter, abc.ABC):
+    """the `EqFilter` classes with a `gain` port (dB, block rate; unplugged: 0 dB)"""
+    gain: Receiver.BoundPort = port('gain')
+
+
+class Peaking(GainEqFilter):
+    """`EqFilter` with a bell of `gain` dB at the cutoff, q wide; at 0 dB b = a, the input"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.peaking
+
+
+class LowShelf(GainEqFilter):
+    """`EqFilter` that lifts (or cuts) what lies below the cutoff by `gain` dB; the cutoff is the shelf's midpoint"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.low_shelf
+
+
+class HighShelf(GainEqFilter):
+    """`EqFilter` that lifts (or cuts) what lies above the cutoff by `gain` dB; the cutoff is the shelf's midpoint"""
+
+    def type(self) -> EqFilter.Type:
+        return self.Type.high_shelf
 
 
 def _validate_matrix(instance, attribute, new_value):

@@ -107,9 +107,12 @@ class CritFilter(Effect, abc.ABC):
         return 100
 
     def _filter(self, request: Request, crit_1: torch.Tensor, crit_2: torch.Tensor = None,
-                resonant: bool = False, resonance: typing.Optional[torch.Tensor] = None) -> torch.Tensor:
+                resonant: bool = False, resonance: typing.Optional[torch.Tensor] = None,
+                equaliser: typing.Optional[str] = None, gain: typing.Optional[torch.Tensor] = None) -> torch.Tensor:
         """`resonant` (chain/ext.py ResonantFilter, single-cutoff types only): the resonant design with `resonance`, a one-row q
-        tensor, or None for an unplugged port (1/sqrt2); otherwise a Butterworth filter of the reference"""
+        tensor, or None for an unplugged port (1/sqrt2); otherwise a Butterworth filter of the reference.  `equaliser` (with
+        `resonant`; chain/ext.py EqFilter): the equaliser design of that name (a key of _native.FILT_TYPES) instead, with `gain`, a
+        one-row tensor of dB, or None for an unplugged port (0 dB)"""
         assert Shape.of_array(crit_1).frames == 1
         if crit_2 is not None:
             assert Shape.of_array(crit_2).frames == 1
@@ -147,13 +150,18 @@ class CritFilter(Effect, abc.ABC):
                                           context_frames, cutoff, high, buf, history, result,
                                           status=self._status.tensor)
         if resonant:
-            if resonance is not None:
-                assert Shape.of_array(resonance).frames == 1
-                if resonance.shape[1] < shape.channels:
-                    raise IndexError(f'index {resonance.shape[1]} is out of bounds for axis 1 with size {resonance.shape[1]}')
-                resonance = resonance[:, :shape.channels]
-                if not resonance.is_contiguous():
-                    resonance = resonance.contiguous()
+            def one_row(row):
+                if row is None:
+                    return None
+                assert Shape.of_array(row).frames == 1
+                if row.shape[1] < shape.channels:
+                    raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
+                row = row[:, :shape.channels]
+                return row if row.is_contiguous() else row.contiguous()
+            resonance = one_row(resonance)
+            if equaliser is not None:
+                return _native.biquad_coldstart_eq(equaliser, request.loc.rate, request.loc.position, shape.frames, 1, context_frames, cutoff,
+                                                   resonance, one_row(gain), buf, history, result, status=self._status.tensor)
             return _native.biquad_coldstart_q(str(self.type()), request.loc.rate, request.loc.position, shape.frames, 1,
                                               context_frames, cutoff, resonance, buf, history, result, status=self._status.tensor)
         return _native.biquad_coldstart(str(self.type()), request.loc.rate, request.loc.position,

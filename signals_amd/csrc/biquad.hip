@@ -47,6 +47,7 @@ __device__ __forceinline__ void pack(double4& v, const double (&y)[4]) { v = mak
 // RES: the resonance rows of sig_biquad_coldstart_q (ResRows), or NoRes: the Butterworth design, and nothing of the other in the code
 struct NoRes {};
 struct ResRows { const double* ptr; int rs, blocks; };    // (blocks, voices | 1) f64 rows of q; ptr null: unplugged = 1/sqrt2
+struct EqRows { ResRows q, gain; };                       // sig_biquad_coldstart_eq: q as above, gain (dB) likewise; null: 0 dB
 
 template <typename T, int VPT, int kRing, bool ENV, typename RES>   // kRing = rows of loads in flight per lane
 __device__ __forceinline__ void biquad_coldstart_body(
@@ -80,6 +81,19 @@ __device__ __forceinline__ void biquad_coldstart_body(
             z0[i] = 0.0; z1[i] = 0.0;
         }
         if (!ok && live && status) atomicOr(status, SIG_STATUS_BAD_CUTOFF);
+    } else if constexpr (std::is_same<RES, EqRows>::value) {
+        int bad = 0;                                                           // SIG_STATUS_BAD_CUTOFF | _BAD_RESONANCE | _BAD_GAIN
+        auto at = [&](const ResRows& rows, int v) {
+            return rows.ptr ? rows.ptr + (rows.blocks > 1 ? b * (int64_t)(rows.rs ? voices : 1) : 0) + (int64_t)v * rows.rs : nullptr;
+        };
+#pragma unroll
+        for (int i = 0; i < VPT; ++i) {
+            const int v = (vc + i < voices) ? vc + i : vc;
+            const double hz = cutoff[(cutoff_blocks > 1 ? b * (int64_t)(cs ? voices : 1) : 0) + (int64_t)v * cs];
+            bad |= sig_biquad::design_eq2(type, hz, at(res.q, v), at(res.gain, v), rate, q[i]);
+            z0[i] = 0.0; z1[i] = 0.0;
+        }
+        if (bad && live && status) atomicOr(status, bad);
     } else {
         int bad = 0;                                                           // SIG_STATUS_BAD_CUTOFF | SIG_STATUS_BAD_RESONANCE
 #pragma unroll
@@ -166,6 +180,18 @@ __global__ __launch_bounds__(256) void biquad_coldstart_q_kernel(
 {
     biquad_coldstart_body<T, VPT, kRing, false>(type, rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld,
                                                 voice_tiles, status, sig_env::AdsrRows{}, res);
+}
+
+// ... and with the equaliser designs (sig_biquad_coldstart_eq): the recurrence of the body is the general one already
+template <typename T, int VPT, int kRing>
+__global__ __launch_bounds__(256) void biquad_coldstart_eq_kernel(
+    int type, double rate, int64_t position, int N, int K, int ctx, int voices,
+    const double* __restrict__ cutoff, int cs, int cutoff_blocks, EqRows eq,
+    const T* __restrict__ in, int64_t in_ld, T* __restrict__ out, int64_t out_ld,
+    int voice_tiles, int* __restrict__ status)
+{
+    biquad_coldstart_body<T, VPT, kRing, false>(type, rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld,
+                                                voice_tiles, status, sig_env::AdsrRows{}, eq);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -287,7 +313,7 @@ template <typename T, bool ENV>
 int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K, int32_t ctx, int32_t voices,
                   const double* cutoff, int32_t cs, int32_t cutoff_blocks,
                   const T* in, int64_t in_ld, T* out, int64_t out_ld, int32_t* status, hipStream_t stream,
-                  const sig_env::AdsrRows& env, const ResRows* res = nullptr)
+                  const sig_env::AdsrRows& env, const ResRows* res = nullptr, const EqRows* eq = nullptr)
 {
     auto ok = [&](int vpt) {
         return (voices % vpt == 0) && (in_ld % vpt == 0) && (out_ld % vpt == 0) &&
@@ -308,7 +334,7 @@ int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K
         int span = (int)(((int64_t)tiles * K) / 1024);
         if (span > 4) span = 4;
         if (walk_env >= 0) span = walk_env;                                    // tuning: 0/1 disables
-        if (span >= 2 && N > ctx && cutoff_blocks == 1 && variant == 0 && !res) {   // (the resonant entry: the plain kernel only)
+        if (span >= 2 && N > ctx && cutoff_blocks == 1 && variant == 0 && !res && !eq) {   // (the resonant and the equaliser entries: the plain kernel only)
             const int64_t items = (int64_t)tiles * ((K + span - 1) / span);
             const int64_t nwg = (items + 3) / 4;
             if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
@@ -345,6 +371,11 @@ int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K
     if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
 #define SIG_BQ(V, R) do { \
         if constexpr (!ENV) { \
+            if (eq) { \
+                biquad_coldstart_eq_kernel<T, V, R><<<(unsigned)nwg, 256, 0, stream>>>( \
+                    type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, *eq, in, in_ld, out, out_ld, voice_tiles, status); \
+                break; \
+            } \
             if (res) { \
                 biquad_coldstart_q_kernel<T, V, R><<<(unsigned)nwg, 256, 0, stream>>>( \
                     type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, *res, in, in_ld, out, out_ld, voice_tiles, status); \
@@ -377,10 +408,12 @@ namespace {
 int run_biquad(int type, int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context,
                int32_t voices, const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
                const void* in, int64_t in_ld, int64_t in_history, void* out, int64_t out_ld, int32_t dtype,
-               int32_t* status, void* stream, const sig_env::AdsrRows* env, const ResRows* res = nullptr)
+               int32_t* status, void* stream, const sig_env::AdsrRows* env, const ResRows* res = nullptr, const EqRows* eq = nullptr)
 {
-    SIG_CHECK_ARG(type == SIG_FILT_LOWPASS || type == SIG_FILT_HIGHPASS);
-    SIG_CHECK_ARG(!res || (!env && (res->rs == 0 || res->rs == 1) && (res->blocks == 1 || res->blocks == nblocks)));
+    auto rows_ok = [&](const ResRows& r) { return (r.rs == 0 || r.rs == 1) && (r.blocks == 1 || r.blocks == nblocks); };
+    SIG_CHECK_ARG(eq ? (type >= SIG_FILT_EQ_BANDPASS && type <= SIG_FILT_EQ_HIGHSHELF) : (type == SIG_FILT_LOWPASS || type == SIG_FILT_HIGHPASS));
+    SIG_CHECK_ARG(!res || (!env && rows_ok(*res)));
+    SIG_CHECK_ARG(!eq || (!env && !res && rows_ok(eq->q) && rows_ok(eq->gain)));
     SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
     SIG_CHECK_ARG(cutoff != nullptr && in != nullptr && out != nullptr);
     SIG_CHECK_ARG(cutoff_stride == 0 || cutoff_stride == 1);
@@ -401,12 +434,12 @@ int run_biquad(int type, int32_t rate, int64_t position, int32_t block_frames, i
         return env ? launch_biquad<float, true>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, *env)
                    : launch_biquad<float, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
-                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, none, res);
+                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, none, res, eq);
     }
     if (dtype == SIG_F64 && !env)
         return launch_biquad<double, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
                                             cutoff_stride, cutoff_blocks, static_cast<const double*>(in), in_ld,
-                                            static_cast<double*>(out), out_ld, status, s, none, res);
+                                            static_cast<double*>(out), out_ld, status, s, none, res, eq);
     return (int)hipErrorInvalidValue;
 }
 
@@ -447,4 +480,18 @@ extern "C" int sig_biquad_coldstart_q(int type, int32_t rate, int64_t position,
     const ResRows res{resonance, resonance_stride, resonance_blocks};          // (a null row: unplugged, its stride and count still checked)
     return run_biquad(type, rate, position, block_frames, nblocks, context, voices, cutoff, cutoff_stride, cutoff_blocks,
                       in, in_ld, in_history, out, out_ld, dtype, status, stream, nullptr, &res);
+}
+
+extern "C" int sig_biquad_coldstart_eq(int type, int32_t rate, int64_t position,
+                                       int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                                       const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
+                                       const double* resonance, int32_t resonance_stride, int32_t resonance_blocks,
+                                       const double* gain, int32_t gain_stride, int32_t gain_blocks,
+                                       const void* in, int64_t in_ld, int64_t in_history,
+                                       void* out, int64_t out_ld, int32_t dtype,
+                                       int32_t* status, void* stream)
+{
+    const EqRows eq{{resonance, resonance_stride, resonance_blocks}, {gain, gain_stride, gain_blocks}};     // (null rows: unplugged, still checked)
+    return run_biquad(type, rate, position, block_frames, nblocks, context, voices, cutoff, cutoff_stride, cutoff_blocks,
+                      in, in_ld, in_history, out, out_ld, dtype, status, stream, nullptr, nullptr, &eq);
 }

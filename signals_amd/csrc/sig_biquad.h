@@ -136,4 +136,58 @@ __device__ __forceinline__ bool design_band2(int type, double lo_hz, double hi_h
     return !bad;
 }
 
+// ---- the RBJ equaliser biquads (chain/ext.py EqFilter): SIG_FILT_EQ_BANDPASS .. SIG_FILT_EQ_HIGHSHELF ---------------------
+// design_resonant2's bilinear transform, s -> (1 - 1/z) / (k (1 + 1/z)), of the cookbook's analogue prototypes with THREE free
+// numerator taps: band-pass (constant 0 dB peak), notch, all-pass, and -- with A = exp(gain ln(10) / 40), g = sqrt(A) d -- peaking,
+// low shelf, high shelf (include/signals_amd.h has the table; tests/eq_reference.py restates it with the same operator order).
+// `resonance` / `gain` null: unplugged, d = sqrt2 itself / A = 1 (gain is not read for the three types without one).  Returns 0 or
+// the status bits of what was refused (the coefficients are then NaN): SIG_STATUS_BAD_CUTOFF and SIG_STATUS_BAD_RESONANCE as
+// design_resonant2, SIG_STATUS_BAD_GAIN for a gain that is not finite.  `tan_half_pi` as for design_band2.
+constexpr double kLn10Over40 = 0.05756462732485115;        // log(10) / 40 in double arithmetic
+template <typename Tan = LibmTan>
+__device__ __forceinline__ int design_eq2(int type, double cutoff, const double* resonance, const double* gain, double rate, Biquad& q,
+                                          Tan tan_half_pi = Tan{}) {
+    double wn = cutoff / (rate * 0.5);
+    wn = (wn < 0.0) ? 0.0 : ((wn > 1.0) ? 1.0 : wn);
+    int bad = !(wn > 0.0 && wn < 1.0) ? SIG_STATUS_BAD_CUTOFF : 0;
+    double d = kSqrt2;
+    if (resonance) {
+        const double r = *resonance;
+        if (!(r > 0.0 && r < __builtin_inf())) bad |= SIG_STATUS_BAD_RESONANCE;     // 0, negative, NaN, +-inf
+        d = 1.0 / r;
+    }
+    double A = 1.0;
+    if (gain && type >= SIG_FILT_EQ_PEAKING) {
+        const double db = *gain;
+        if (!(fabs(db) < __builtin_inf())) bad |= SIG_STATUS_BAD_GAIN;              // NaN, +-inf
+        A = exp(db * kLn10Over40);
+    }
+    const double k = tan_half_pi(kPi * wn / 2.0);
+    const double k2 = k * k;
+    double a0, a1, a2;
+    if (type <= SIG_FILT_EQ_ALLPASS) {
+        a0 = 1.0 + d * k + k2; a1 = 2.0 * (k2 - 1.0); a2 = 1.0 - d * k + k2;
+        if (type == SIG_FILT_EQ_BANDPASS)   { q.b0 = d * k;    q.b1 = 0.0; q.b2 = -(d * k); }
+        else if (type == SIG_FILT_EQ_NOTCH) { q.b0 = 1.0 + k2; q.b1 = a1;  q.b2 = 1.0 + k2; }
+        else                                { q.b0 = a2;       q.b1 = a1;  q.b2 = a0; }
+    } else if (type == SIG_FILT_EQ_PEAKING) {
+        a0 = 1.0 + (d / A) * k + k2; a1 = 2.0 * (k2 - 1.0); a2 = 1.0 - (d / A) * k + k2;
+        q.b0 = 1.0 + d * A * k + k2; q.b1 = a1; q.b2 = 1.0 - d * A * k + k2;
+    } else {
+        const double g = sqrt(A) * d;
+        if (type == SIG_FILT_EQ_LOWSHELF) {
+            a0 = A + g * k + k2; a1 = 2.0 * (k2 - A); a2 = A - g * k + k2;
+            q.b0 = A * (1.0 + g * k + A * k2); q.b1 = A * (2.0 * (A * k2 - 1.0)); q.b2 = A * (1.0 - g * k + A * k2);
+        } else {
+            a0 = 1.0 + g * k + A * k2; a1 = 2.0 * (A * k2 - 1.0); a2 = 1.0 - g * k + A * k2;
+            q.b0 = A * (A + g * k + k2); q.b1 = A * (2.0 * (k2 - A)); q.b2 = A * (A - g * k + k2);
+        }
+    }
+    const double nrm = 1.0 / a0;
+    q.b0 *= nrm; q.b1 *= nrm; q.b2 *= nrm;
+    q.a1 = a1 * nrm; q.a2 = a2 * nrm;
+    if (bad) { q.b0 = q.b1 = q.b2 = q.a1 = q.a2 = __builtin_nan(""); }
+    return bad;
+}
+
 }  // namespace sig_biquad

@@ -64,5 +64,7 @@ extern template struct VpLaunch<vp_family::resonant>;
 extern template struct VpLaunch<vp_family::unison>;
 extern template struct VpLaunch<vp_family::blep>;
 extern template struct VpLaunch<vp_family::mixed>;
+extern template struct VpLaunch<vp_family::resonant_eq>;
+extern template struct VpLaunch<vp_family::mixed_eq>;
 
 }  // namespace sig_vp

@@ -174,6 +174,12 @@ __device__ __forceinline__ int vp_design_res(bool lowpass, double cutoff, double
     return bad;
 }
 
+// The equaliser designs of a FilterEq slot (sig_biquad.h design_eq2 with the light tangent): all five coefficients, the numerator's
+// three taps free.  `has_q` / `has_gain`: the control is plugged (else d = sqrt2 / 0 dB).  Returns 0 or the status bits.
+__device__ __forceinline__ int vp_design_eq(int type, double cutoff, bool has_q, double qv, bool has_gain, double db, double rate, Biquad& q) {
+    return sig_biquad::design_eq2(type, cutoff, has_q ? &qv : nullptr, has_gain ? &db : nullptr, rate, q, VpTan{});
+}
+
 __device__ __noinline__ double vp_amp(double x, double e) { return copysign(pow(x, e), x); }   // fx.py:60 (kept out of line: pow is long)
 
 // Register-file sizes per variant (the host picks the smallest variant a program fits).  SMALL: two filter slots, three
@@ -211,6 +217,11 @@ template <bool SMALL> struct VpLimits {
 // variant has (VpTables, VpUnison) or VpNoTables
 // BLP: the OscBlep instruction (band-limited oscillators, ext.py BlepOsc) on top of UNI, whose copies and operands it shares: a flag
 // of its own, so that programs with OscUni alone keep the UNI variant's code (vp_family::blep has both handlers)
+// EQ: the FilterEq instruction (the RBJ equaliser biquads, ext.py EqFilter) on top of RES, whose q scan and exclusions it shares:
+// slots of type SIG_FILT_EQ_* with three free numerator taps (fb0 and eb1 / eb2; xb0 / xb1 / xb2 for the next block's chain) and a third
+// block-rate control, the gain, from the parameter rows the word's b names.  A flag of its own -- a second set of kernels, RES+EQ
+// (vp_family::resonant_eq) and MIXED+EQ (vp_family::mixed_eq), which the launch picks exactly when the program has the word -- so
+// that programs without it keep the code of the RES and MIXED variants (the taps cost 5 x NF x VPT doubles of state)
 // The "never with" above is the single-family variants'.  The MIXED variant (vp_family::mixed, reached only through
 // sig_voice_program_mixed) has all seven flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
 //   * RES on: every LowPass / HighPass slot is designed by vp_design_res at d = sqrt2 (`single` is off), which are vp_design's bits;
@@ -226,11 +237,12 @@ namespace sig_vp {
 
 // One interpreter variant: the flags above, and `Extra`, the second kernel parameter that follows from them (two or more of the
 // five families: both the tables and the copies).
-template <bool BAND_, bool PM_, bool TAB_, bool SHP_, bool RES_, bool UNI_, bool BLP_>
+template <bool BAND_, bool PM_, bool TAB_, bool SHP_, bool RES_, bool UNI_, bool BLP_, bool EQ_>
 struct VpFamily {
-    static constexpr bool BAND = BAND_, PM = PM_, TAB = TAB_, SHP = SHP_, RES = RES_, UNI = UNI_, BLP = BLP_;
+    static constexpr bool BAND = BAND_, PM = PM_, TAB = TAB_, SHP = SHP_, RES = RES_, UNI = UNI_, BLP = BLP_, EQ = EQ_;
     static_assert(TAB || !SHP, "Shape sits on top of TAB");
     static_assert(UNI || !BLP, "OscBlep sits on top of UNI");
+    static_assert(RES || !EQ, "FilterEq sits on top of RES");
     static constexpr int families = (int)BAND + (int)PM + (int)TAB + (int)RES + (int)UNI;
     using Extra = std::conditional_t<(families >= 2), VpMixed,
                   std::conditional_t<TAB, VpTables, std::conditional_t<UNI, VpUnison, VpNoTables>>>;
@@ -238,16 +250,19 @@ struct VpFamily {
 
 // the nine variants the interpreter is built in, in the order of SIG_VP_FAMILY_* (include/signals_amd.h)
 namespace vp_family {
-//                       BAND   PM     TAB    SHP    RES    UNI    BLP
-using plain    = VpFamily<false, false, false, false, false, false, false>;
-using band     = VpFamily<true,  false, false, false, false, false, false>;
-using pm       = VpFamily<false, true,  false, false, false, false, false>;
-using table    = VpFamily<false, false, true,  false, false, false, false>;
-using shape    = VpFamily<false, false, true,  true,  false, false, false>;
-using resonant = VpFamily<false, false, false, false, true,  false, false>;
-using unison   = VpFamily<false, false, false, false, false, true,  false>;
-using blep     = VpFamily<false, false, false, false, false, true,  true>;
-using mixed    = VpFamily<true,  true,  true,  true,  true,  true,  true>;
+//                       BAND   PM     TAB    SHP    RES    UNI    BLP    EQ
+using plain    = VpFamily<false, false, false, false, false, false, false, false>;
+using band     = VpFamily<true,  false, false, false, false, false, false, false>;
+using pm       = VpFamily<false, true,  false, false, false, false, false, false>;
+using table    = VpFamily<false, false, true,  false, false, false, false, false>;
+using shape    = VpFamily<false, false, true,  true,  false, false, false, false>;
+using resonant = VpFamily<false, false, false, false, true,  false, false, false>;
+using unison   = VpFamily<false, false, false, false, false, true,  false, false>;
+using blep     = VpFamily<false, false, false, false, false, true,  true,  false>;
+using mixed    = VpFamily<true,  true,  true,  true,  true,  true,  true,  false>;
+// the second set of RESONANT and MIXED, for programs with a FilterEq word (no SIG_VP_FAMILY_* of their own: the launch picks them)
+using resonant_eq = VpFamily<false, false, false, false, true, false, false, true>;
+using mixed_eq    = VpFamily<true,  true,  true,  true,  true, true,  true,  true>;
 }  // namespace vp_family
 
 }  // namespace sig_vp
@@ -259,7 +274,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                                         [[maybe_unused]] const float* tab)
 {
     // (the body reads the family's flags by their bare names)
-    [[maybe_unused]] constexpr bool BAND = FAM::BAND, PM = FAM::PM, TAB = FAM::TAB, SHP = FAM::SHP, RES = FAM::RES, UNI = FAM::UNI, BLP = FAM::BLP;
+    [[maybe_unused]] constexpr bool BAND = FAM::BAND, PM = FAM::PM, TAB = FAM::TAB, SHP = FAM::SHP, RES = FAM::RES, UNI = FAM::UNI, BLP = FAM::BLP, EQ = FAM::EQ;
     constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
     constexpr bool BUS = C > 0;
     constexpr int CC = BUS ? C : 1;
@@ -285,6 +300,15 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
     double acc[RG][VPT], T[NT > 0 ? NT : 1][RG][VPT], pr[NP][VPT], ohz[NO][VPT], oph[NO][VPT];
     double z0[NF][VPT], z1[NF][VPT], w0[NF][VPT], w1[NF][VPT], na1[NF][VPT], na2[NF][VPT], fb0[NF][VPT], xa1[NF][VPT], xa2[NF][VPT];
     double s2[NF];
+    // EQ: the numerator of a FilterEq slot is b0 = fb0, b1 = eb1, b2 = eb2 (not b0 [1, +-2, 1]); xb0 / xb1 / xb2: the next block's chain
+    constexpr int NE = EQ ? NF : 1;
+    [[maybe_unused]] double eb1[NE][VPT], eb2[NE][VPT], xb0[NE][VPT], xb1[NE][VPT], xb2[NE][VPT];
+    if constexpr (EQ) {
+#pragma unroll
+        for (int f = 0; f < NE; ++f)
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) eb1[f][i] = eb2[f][i] = xb0[f][i] = xb1[f][i] = xb2[f][i] = 0.0;
+    }
     // band filters (Band): two consecutive slots f, f + 1 -- the sections of butter(2, [low, high]) -- whose middle taps vary per
     // voice and block: beta of the first section (current and next chains) in bq / xbq[f / 2]; the second's is -beta (bp) or beta
     // (bs); the band's gain is the second slot's fb0.  A run of band slots pairs up from its start (the host emits them that way,
@@ -321,16 +345,27 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 
     // RES: the parameter slot that holds filter slot f's q rows (-1: a Butterworth slot, or q unplugged), from the FilterQ words
     [[maybe_unused]] int qreg[NF];
+    [[maybe_unused]] int greg[NE];                                             // EQ: likewise the slot's gain rows, from the FilterEq words' b
     if constexpr (RES) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) qreg[f] = -1;
+        if constexpr (EQ) {
+#pragma unroll
+            for (int f = 0; f < NE; ++f) greg[f] = -1;
+        }
         for (int k = 0; k < a.n_ins; ++k) {
             const uint32_t w = a.code[k];                                      // (wave-uniform: the argument block)
-            if ((w & 31u) != (uint32_t)SIG_VP_FILTERQ) continue;
+            if ((w & 31u) != (uint32_t)SIG_VP_FILTERQ && !(EQ && (w & 31u) == (uint32_t)SIG_VP_FILTEREQ)) continue;
             const int slot = (int)((w >> 8) & 15u), reg = (int)((w >> 16) & 15u);
 #pragma unroll
             for (int f = 0; f < NF; ++f)
                 if (f == slot) qreg[f] = (reg < a.n_params) ? reg : -1;        // (15: unplugged)
+            if constexpr (EQ) {
+                const int gr = (int)((w >> 12) & 15u);                         // (FilterQ's b is 0: its slot is no equaliser slot, greg is not read)
+#pragma unroll
+                for (int f = 0; f < NE; ++f)
+                    if (f == slot) greg[f] = ((w & 31u) == (uint32_t)SIG_VP_FILTEREQ && gr < a.n_params) ? gr : -1;
+            }
         }
     }
 
@@ -406,6 +441,27 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                         if (!NEXT && !designed) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; }
                     }
                     if (bad && a.status) atomicOr(a.status, bad);
+                }
+                if constexpr (EQ) {                                            // an equaliser slot: all five coefficients, q and gain from the word's rows
+                    const bool eq = f < a.n_filters && a.ftype[f] >= SIG_FILT_EQ_BANDPASS && a.ftype[f] <= SIG_FILT_EQ_HIGHSHELF;
+                    const bool has_q = eq && qreg[f] >= 0, has_gain = eq && greg[f] >= 0;
+                    const bool swept_eq = (has_q && a.params[has_q ? qreg[f] : 0].rows > 1) || (has_gain && a.params[has_gain ? greg[f] : 0].rows > 1);
+                    if (eq && a.flevel[f] >= min_level && (!designed || a.cutoff[f].rows > 1 || swept_eq)) {
+                        int bad = 0;
+#pragma unroll
+                        for (int i = 0; i < VPT; ++i) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            const double qv = has_q ? row_at(a.params[qreg[f]], cri, voice(i)) : 0.0;
+                            const double db = has_gain ? row_at(a.params[greg[f]], cri, voice(i)) : 0.0;
+                            Biquad q;
+                            const int got = vp_design_eq(a.ftype[f], row_at(a.cutoff[f], cri, voice(i)), has_q, qv, has_gain, db, a.rate, q);
+                            bad |= (v0 + i < a.voices) ? got : 0;              // a dead (padding) lane never reports
+                            if (NEXT) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; xb0[f][i] = q.b0; xb1[f][i] = q.b1; xb2[f][i] = q.b2; }
+                            else { na1[f][i] = -q.a1; na2[f][i] = -q.a2; fb0[f][i] = q.b0; eb1[f][i] = q.b1; eb2[f][i] = q.b2; }
+                            if (!NEXT && !designed) { xa1[f][i] = -q.a1; xa2[f][i] = -q.a2; xb0[f][i] = q.b0; xb1[f][i] = q.b1; xb2[f][i] = q.b2; }
+                        }
+                        if (bad && a.status) atomicOr(a.status, bad);
+                    }
                 }
             }
             const bool single = !RES && f < a.n_filters && (a.ftype[f] == SIG_FILT_LOWPASS || a.ftype[f] == SIG_FILT_HIGHPASS);
@@ -578,6 +634,39 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
             }
         }
     };
+    // EQ: the section of an equaliser slot F, the general transposed direct form II y = b0 x + z0; z0 = b1 x - a1 y + z1; z1 = b2 x - a2 y
+    // (the state is not b0-normalised: b0 may be 0, an all-pass at d k = 1 + k k)
+    [[maybe_unused]] auto section_eq = [&](auto I, int warm_r, auto rows_tag) {
+        constexpr int F = decltype(I)::value;
+        constexpr int R = decltype(rows_tag)::value;
+        if constexpr (EQ) {
+            if (warm_r < R) {                                                  // wave-uniform: the next block's chain, on the same input rows
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (r >= warm_r) {
+#pragma unroll
+                        for (int i = 0; i < VPT; ++i) {
+                            const double x = acc[r][i];
+                            const double yw = fma(xb0[F][i], x, w0[F][i]);
+                            w0[F][i] = fma(xa1[F][i], yw, fma(xb1[F][i], x, w1[F][i]));
+                            w1[F][i] = fma(xa2[F][i], yw, xb2[F][i] * x);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double x = acc[r][i];
+                    const double y = fma(fb0[F][i], x, z0[F][i]);
+                    z0[F][i] = fma(na1[F][i], y, fma(eb1[F][i], x, z1[F][i]));
+                    z1[F][i] = fma(na2[F][i], y, eb2[F][i] * x);
+                    acc[r][i] = y;
+                }
+            }
+        }
+    };
     auto group = [&](int64_t n, int warm_r, bool out, auto rows_tag) {        // warm_r: the first row of the group that also advances the next chains (R: none)
         constexpr int R = decltype(rows_tag)::value;
         if (!q_valid || n < qbase || n + R > qbase + SIG_WAVE) {                // n / rate (IEEE divide) for 64 rows at a time, one per lane
@@ -618,6 +707,12 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                         constexpr int F = decltype(I)::value;
                         section(I, warm_r, rows_tag, [&](int) { return s2[F]; }, [&](int) { return s2[F]; }, true);
                     });
+                    continue;
+                }
+            }
+            if constexpr (EQ) {                                                // FilterEq: an equaliser slot's section, in front of the switch likewise
+                if (op == SIG_VP_FILTEREQ) {
+                    with_index<NF>(ia, [&](auto I) { section_eq(I, warm_r, rows_tag); });
                     continue;
                 }
             }

@@ -37,7 +37,10 @@ constexpr bool vp_static_has(int op) {
 #define SIG_VP_S_MIXED 0                   // 1: the program combines two or more of Band, OscPM, OscTable / Shape, FilterQ, OscUni; the kernel takes a VpMixed
 #endif
 #ifndef SIG_VP_S_RES
-#define SIG_VP_S_RES 0                     // 1: the program has a FilterQ word (the resonant design)
+#define SIG_VP_S_RES 0                     // 1: the program has a FilterQ or a FilterEq word (the resonant design)
+#endif
+#ifndef SIG_VP_S_EQ
+#define SIG_VP_S_EQ 0                      // 1: the program has a FilterEq word (with -DSIG_VP_S_RES=1: the general numerator on top of it)
 #endif
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIG_VP_STATIC_WAVES, 8)))
 #if SIG_VP_S_MIXED
@@ -52,8 +55,10 @@ void sig_vp_specialised(VpArgs a)
 {
     constexpr bool kBand = vp_static_has(SIG_VP_BAND), kPm = vp_static_has(SIG_VP_OSCPM), kShape = vp_static_has(SIG_VP_SHAPE);
     constexpr bool kTab = vp_static_has(SIG_VP_OSCTABLE) || kShape;
-    constexpr bool kRes = vp_static_has(SIG_VP_FILTERQ);
-    static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ word is built with -DSIG_VP_S_RES=1, any other without");
+    constexpr bool kEq = vp_static_has(SIG_VP_FILTEREQ);
+    constexpr bool kRes = vp_static_has(SIG_VP_FILTERQ) || kEq;                // (one family: FilterEq reads FilterQ's q rows)
+    static_assert(kRes == (SIG_VP_S_RES != 0), "a program with a FilterQ or a FilterEq word is built with -DSIG_VP_S_RES=1, any other without");
+    static_assert(kEq == (SIG_VP_S_EQ != 0), "a program with a FilterEq word is built with -DSIG_VP_S_EQ=1, any other without");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
     constexpr bool kBlep = vp_static_has(SIG_VP_OSCBLEP);
     constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI) || kBlep;               // (one family: OscBlep reads OscUni's copies)
@@ -66,7 +71,7 @@ void sig_vp_specialised(VpArgs a)
     static_assert(!(kUni && (kTab || kBand || kPm || kRes)), "OscUni with Band, OscPM, OscTable, Shape or FilterQ: no variant has both");
     static_assert(!(kBand && kPm) && !(kTab && (kBand || kPm)), "Band, OscPM and OscTable / Shape: no variant has two of them");
 #endif
-    using F = VpFamily<kBand, kPm, kTab, kShape, kRes, kUni, kBlep>;           // exactly the families the program has
+    using F = VpFamily<kBand, kPm, kTab, kShape, kRes, kUni, kBlep, kEq>;           // exactly the families the program has
 #if SIG_VP_S_MIXED || SIG_VP_S_TAB || SIG_VP_S_UNI
     static_assert(std::is_same_v<F::Extra, decltype(extra)>, "the second kernel parameter is the one the program's families take");
     vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, F>(a, extra);
@@ -99,8 +104,11 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 // ---- the two rules about words, each written once
 // may this word's c be -1?  (no select / no q / no spread; encoded as 15, a slot number no register file has)
 constexpr bool vp_c_optional(int op) {
-    return op == SIG_VP_OSCTABLE || op == SIG_VP_SHAPE || op == SIG_VP_FILTERQ || op == SIG_VP_OSCUNI || op == SIG_VP_OSCBLEP;
+    return op == SIG_VP_OSCTABLE || op == SIG_VP_SHAPE || op == SIG_VP_FILTERQ || op == SIG_VP_OSCUNI || op == SIG_VP_OSCBLEP ||
+           op == SIG_VP_FILTEREQ;
 }
+// ... and its b?  (FilterEq alone: no gain)
+constexpr bool vp_b_optional(int op) { return op == SIG_VP_FILTEREQ; }
 // the variant that has this word's handler and no other extension word's (SIG_VP_FAMILY_*; PLAIN: every variant has it)
 constexpr int vp_word_family(int op) {
     switch (op) {
@@ -109,6 +117,7 @@ constexpr int vp_word_family(int op) {
         case SIG_VP_OSCTABLE: return SIG_VP_FAMILY_TABLE;
         case SIG_VP_SHAPE: return SIG_VP_FAMILY_SHAPE;
         case SIG_VP_FILTERQ: return SIG_VP_FAMILY_RESONANT;
+        case SIG_VP_FILTEREQ: return SIG_VP_FAMILY_RESONANT;                   // (the same family and exclusions; its kernels: VpNeeds::eq)
         case SIG_VP_OSCUNI: return SIG_VP_FAMILY_UNISON;
         case SIG_VP_OSCBLEP: return SIG_VP_FAMILY_BLEP;
         default: return SIG_VP_FAMILY_PLAIN;
@@ -116,7 +125,8 @@ constexpr int vp_word_family(int op) {
 }
 
 bool vp_word_ok(const sig_vp_ins& x) {
-    return x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCBLEP && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 && x.b >= 0 && x.b <= 15 &&
+    return x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTEREQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 &&
+           x.b >= (vp_b_optional(x.op) ? -1 : 0) && x.b <= 15 &&
            x.c >= (vp_c_optional(x.op) ? -1 : 0) && x.c <= 15;
 }
 
@@ -124,7 +134,7 @@ bool vp_encode(const sig_voice_program_t& P, uint32_t* code) {
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
         if (!vp_word_ok(x)) return false;
-        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)x.b << 12) | ((uint32_t)(x.c & 15) << 16);
+        code[k] = (uint32_t)x.op | ((uint32_t)x.kind << 5) | ((uint32_t)x.a << 8) | ((uint32_t)(x.b & 15) << 12) | ((uint32_t)(x.c & 15) << 16);
     }
     return true;
 }
@@ -143,6 +153,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
 // has a word of family f (vp_word_family).
 struct VpNeeds {
     int oscs, params, temps, filters; bool ext, adsr; unsigned words;
+    bool eq;                                                                   // a FilterEq word: the RES+EQ / MIXED+EQ kernels (vp_family::resonant_eq, mixed_eq)
     bool has(int family) const { return (words >> family) & 1u; }
     bool table() const { return has(SIG_VP_FAMILY_TABLE) || has(SIG_VP_FAMILY_SHAPE); }      // (Shape sits on top of the table family)
     bool uni() const { return has(SIG_VP_FAMILY_UNISON) || has(SIG_VP_FAMILY_BLEP); }        // (OscBlep: the unison family, the same copies, the same exclusions)
@@ -151,11 +162,12 @@ struct VpNeeds {
 };
 
 VpNeeds vp_needs(const sig_voice_program_t& P) {              // (n_ins was checked; any op may stand in a word)
-    VpNeeds n{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, 0u};
+    VpNeeds n{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, 0u, false};
     for (int k = 0; k < P.n_ins; ++k) {
         const int op = P.ins[k].op;
         if (op == SIG_VP_AMP || op == SIG_VP_ADSR || op == SIG_VP_NOISE) n.ext = true;
         if (op == SIG_VP_ADSR) n.adsr = true;
+        if (op == SIG_VP_FILTEREQ) n.eq = true;
         n.words |= 1u << vp_word_family(op);
     }
     return n;
@@ -286,6 +298,7 @@ int vp_check(const VpRequest& r, VpCall& c)
             case SIG_VP_OSCPM: SIG_CHECK_ARG(x.a < P.n_oscs && x.b < P.n_params && x.kind <= SIG_OSC_TRIANGLE); break;
             case SIG_VP_FILTER: SIG_CHECK_ARG(x.a < P.n_filters); break;
             case SIG_VP_FILTERQ: SIG_CHECK_ARG(x.a < P.n_filters && x.c < P.n_params); break;
+            case SIG_VP_FILTEREQ: SIG_CHECK_ARG(x.a < P.n_filters && x.b < P.n_params && x.c < P.n_params); break;
             case SIG_VP_OSCUNI:
                 SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params && x.kind <= SIG_OSC_TRIANGLE);
                 break;
@@ -338,7 +351,7 @@ int vp_check(const VpRequest& r, VpCall& c)
     }
     // filter slots: a Filter instruction runs a LowPass / HighPass slot; a Band instruction at slot f runs the pair f, f + 1 (its
     // low and high rows), of one band type and one level, which the kernel finds by pairing every run of band slots from its start
-    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second, 4: resonant (one FilterQ word)
+    int role[SIG_VP_MAX_FILTERS] = {0};                                        // 1: single, 2: first of a band, 3: second, 4: resonant (one FilterQ word), 5: equaliser (one FilterEq word)
     for (int k = 0; k < P.n_ins; ++k) {
         const sig_vp_ins& x = P.ins[k];
         if (x.op == SIG_VP_FILTER) {
@@ -347,6 +360,9 @@ int vp_check(const VpRequest& r, VpCall& c)
         } else if (x.op == SIG_VP_FILTERQ) {
             SIG_CHECK_ARG(role[x.a] == 0);
             role[x.a] = 4;
+        } else if (x.op == SIG_VP_FILTEREQ) {
+            SIG_CHECK_ARG(role[x.a] == 0);
+            role[x.a] = 5;
         } else if (x.op == SIG_VP_BAND) {
             SIG_CHECK_ARG((role[x.a] == 0 || role[x.a] == 2) && (role[x.a + 1] == 0 || role[x.a + 1] == 3));
             role[x.a] = 2; role[x.a + 1] = 3;
@@ -361,9 +377,11 @@ int vp_check(const VpRequest& r, VpCall& c)
         else if (role[k] == 3) SIG_CHECK_ARG(band && run % 2 == 0);
         const bool resonant = P.filter_type[k] == SIG_FILT_RES_LOWPASS || P.filter_type[k] == SIG_FILT_RES_HIGHPASS;
         SIG_CHECK_ARG(resonant == (role[k] == 4));                             // a resonant slot and its FilterQ word go together
+        const bool eq = P.filter_type[k] >= SIG_FILT_EQ_BANDPASS && P.filter_type[k] <= SIG_FILT_EQ_HIGHSHELF;
+        SIG_CHECK_ARG(eq == (role[k] == 5));                                   // ... an equaliser slot and its FilterEq word
     }
     for (int k = 0; k < P.n_filters; ++k) {
-        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_RES_HIGHPASS);
+        SIG_CHECK_ARG(rows_ok(P.cutoff[k], false) && P.filter_type[k] >= SIG_FILT_LOWPASS && P.filter_type[k] <= SIG_FILT_EQ_HIGHSHELF);
         a.cutoff[k] = Rows{P.cutoff[k].ptr, P.cutoff[k].col_stride, P.cutoff[k].rows};
         a.ftype[k] = P.filter_type[k];
         SIG_CHECK_ARG(P.filter_level[k] >= 1 && P.filter_level[k] <= P.depth);
@@ -414,6 +432,12 @@ int vp_launch_call(const VpRequest& r, VpCall& c)
         err = (int)hipModuleLaunchKernel(fn, nwg, 1, 1, 256, 1, 1, (unsigned)c.table_lds, s, params, nullptr);
     } else if (vpt == 4) {
         return (int)hipErrorInvalidValue;                                      // (forced by the tuning hook after the image was switched off)
+    } else if (c.need.eq) {
+        // a FilterEq word: the second set of the resonant or the mixed variant (vp_variant answers one of the two: the word is of the
+        // resonant family), chosen here and only here, so that every program without the word gets the kernels it always got
+        err = vp_variant(c.need) == SIG_VP_FAMILY_MIXED
+            ? VpLaunch<vp_family::mixed_eq>::run(a, std::get<VpMixed>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s)
+            : VpLaunch<vp_family::resonant_eq>::run(a, std::get<VpNoTables>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s);
     } else {
         err = vp_with_family(vp_variant(c.need), [&](auto family) {
             using F = decltype(family);

@@ -397,6 +397,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.right]
     if isinstance(node, fx.Mix):
         return [node.mix]
+    if isinstance(node, ext.EqFilter) and node.gain_port() is not None:
+        return [node.cutoff, node.resonance, node.gain_port()]
     if isinstance(node, ext.ResonantFilter):
         return [node.cutoff, node.resonance]
     if isinstance(node, fx.SingleCritFilter):
@@ -1331,9 +1333,25 @@ class _Batch:
                 if not q.is_contiguous():
                     q = q.contiguous()
             swept = cutoff.shape[0] > 1 or (q is not None and q.shape[0] > 1)
-            o._launch(f'biquad_coldstart_q[{btype}{",blocks" if swept else ""}]',
-                      lambda: _native.biquad_coldstart_q(btype, self.rate, pos, N, K, CONTEXT, cutoff, q, window, c0, main, status=status),
-                      units=N * K * channels)
+            if isinstance(node, ext.EqFilter):
+                # the equaliser biquads: a third control row for the three gain classes, per block on its own like the other two
+                gp = node.gain_port()
+                gain = None if gp is None or _ctl_unplugged(gp) else self._control(gp, 'gain')
+                if gain is not None:
+                    if gain.shape[1] < channels:
+                        raise IndexError(f'index {gain.shape[1]} is out of bounds for axis 1 with size {gain.shape[1]}')
+                    gain = gain[:, :channels]
+                    if not gain.is_contiguous():
+                        gain = gain.contiguous()
+                    swept = swept or gain.shape[0] > 1
+                o._launch(f'biquad_coldstart_eq[{btype}{",blocks" if swept else ""}]',
+                          lambda: _native.biquad_coldstart_eq(btype, self.rate, pos, N, K, CONTEXT, cutoff, q, gain, window, c0, main,
+                                                              status=status),
+                          units=N * K * channels)
+            else:
+                o._launch(f'biquad_coldstart_q[{btype}{",blocks" if swept else ""}]',
+                          lambda: _native.biquad_coldstart_q(btype, self.rate, pos, N, K, CONTEXT, cutoff, q, window, c0, main, status=status),
+                          units=N * K * channels)
         else:
             o._launch(f'biquad_coldstart[{btype}{",env" if envelope else ""}]',
                       lambda: _native.biquad_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, window, c0, main,
@@ -1887,7 +1905,7 @@ class _ProgramRows:
 class _VoiceProgram:
     """The per-voice graph under a node as ONE launch of sig_voice_program (voice_program.hip): oscillators, LowPass / HighPass / BandPass / BandStop,
     Gain / Amp / Mix / RingMod, Fixed rows, ADSR, White, phase-modulation carriers (ext.PMOsc), wavetable oscillators (ext.Wavetable), waveshapers (ext.Shaper),
-    resonant low-pass / high-pass filters (ext.ResonantFilter), unison oscillators (ext.UnisonOsc), in any arrangement in which every voice is computed from its own
+    resonant low-pass / high-pass filters (ext.ResonantFilter), equaliser biquads (ext.EqFilter), unison oscillators (ext.UnisonOsc), in any arrangement in which every voice is computed from its own
     parameters only (nothing mixes channels in front of the sink) and no inner node has a reader outside the graph.  Compiled
     here into straight-line code for the kernel's accumulator machine: a binary node parks its left operand in a temporary, a
     node with several readers is computed once and kept in one.  Control ports driven by computed block-rate signals become
@@ -1907,6 +1925,7 @@ class _VoiceProgram:
         self.filters: list = []                  # (cutoff control index, type, level, node); a band filter: two slots, low then high
         self.bands: list = []                    # the band filter nodes
         self.resonant: list = []                 # (resonant filter node, the parameter register of its q rows | -1)
+        self.gains: list = []                    # (equaliser filter node, the parameter register of its gain rows | -1)
         self.controls: list = []                 # (port | None, constant tensor | None, filters between the node and the sink)
         self.adsr = None
         self.seeds: list = []
@@ -2096,7 +2115,17 @@ class _VoiceProgram:
             edges = (n.low, n.high) if band else (n.cutoff,)
             if len(self.filters) + len(edges) > _native.VP_MAX_FILTERS:
                 raise _NoProgram('more filters than the machine has slots')
-            if isinstance(n, ext.ResonantFilter):
+            if isinstance(n, ext.EqFilter):
+                # a resonant slot of an equaliser type: q as below, the gain rows in a second parameter register the FilterEq word's b
+                # names (-1: unplugged = 0 dB, and for the three classes without the port)
+                self.filters.append((self._control(n.cutoff, below), str(n.type()), depth, n))
+                q = -1 if _ctl_unplugged(n.resonance) else self._param(self._control(n.resonance, below))
+                gp = n.gain_port()
+                gain = -1 if gp is None or _ctl_unplugged(gp) else self._param(self._control(gp, below))
+                self.code.append(('FilterEq', 0, len(self.filters) - 1, gain, q))
+                self.resonant.append((n, q))
+                self.gains.append((n, gain))
+            elif isinstance(n, ext.ResonantFilter):
                 # one slot like LowPass / HighPass, of a type of its own; q in a parameter register the FilterQ word names (read per
                 # block with the cutoff, where the slot is designed), -1: unplugged = 1/sqrt2
                 self.filters.append((self._control(n.cutoff, below), 'r' + str(n.type()), depth, n))
@@ -2181,7 +2210,7 @@ class _VoiceProgram:
         for cut, _, _, _ in self.filters:
             if tensors[cut].shape[1] != v and v != 1:
                 raise IndexError(f'index {tensors[cut].shape[1]} is out of bounds for axis 1 with size {tensors[cut].shape[1]}')   # fx.py:99
-        for _, q in self.resonant:
+        for _, q in self.resonant + self.gains:
             if q >= 0 and tensors[self.params[q]].shape[1] != v and v != 1:
                 width = tensors[self.params[q]].shape[1]
                 raise IndexError(f'index {width} is out of bounds for axis 1 with size {width}')
@@ -2254,6 +2283,8 @@ class _VoiceProgram:
         front of the shaper (tools/time_shaper.py).
         Resonant filters (FilterQ) take the program under the same rule; the q rows cost one parameter register each
         (tools/time_resonant.py).
+        Equaliser biquads (FilterEq) keep FilterQ's rule, a gain costing one register more; their throughput is not measured yet
+        (tools/time_eq.py).
         Unison oscillators (OscUni) take the program under the same rule: seven saws per voice under a bus run at 0.33 T interpreted
         against 0.28 T per node, 0.27 against 0.19 T behind a LowPass (tools/time_unison.py) -- a narrower
         margin than the other oscillators', since U copies of f64 work per sample bound both routes.

@@ -51,12 +51,14 @@ class StatusWord:
 
 def check_status() -> None:
     """Raise what the reference would have raised inside the block (scipy's ValueError for a
-    critical frequency outside (0, 1), fx.py:99-121; for a resonant filter's q that is not finite and > 0 the build's own).  Costs one device sync per live status word:
+    critical frequency outside (0, 1), fx.py:99-121; for a resonant filter's q that is not finite and > 0 and an equaliser filter's gain that is not finite the build's own).  Costs one device sync per live status word:
     call at the sink edge, not per node."""
-    from signals_amd._native import STATUS_BAD_CUTOFF, STATUS_BAD_RESONANCE
+    from signals_amd._native import STATUS_BAD_CUTOFF, STATUS_BAD_GAIN, STATUS_BAD_RESONANCE
     for word in list(_status_words):
         bits = word.poll()
         if bits & STATUS_BAD_CUTOFF:
             raise ValueError(f'{word.owner_name}: Digital filter critical frequencies must be 0 < Wn < 1')
         if bits & STATUS_BAD_RESONANCE:                   # (build-defined: chain/ext.py ResonantFilter)
             raise ValueError(f'{word.owner_name}: filter resonance must be finite and > 0')
+        if bits & STATUS_BAD_GAIN:                        # (build-defined: chain/ext.py EqFilter)
+            raise ValueError(f'{word.owner_name}: filter gain must be finite')

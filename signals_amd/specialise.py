@@ -53,7 +53,8 @@ def flags(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, 
     words = ','.join(f'0x{w:x}' for w in _native.voice_program_words(code))
     ext = int(any(op in _native.VP_EXT_OPS for op, *_ in code))                  # Amp, Adsr, Noise: the extended handlers
     more = ['-DSIG_VP_S_TAB=1'] if any(op in _native.VP_TABLE_OPS for op, *_ in code) else []   # (the tables: a second kernel parameter)
-    more += ['-DSIG_VP_S_RES=1'] if any(op in _native.VP_RES_OPS for op, *_ in code) else []    # (FilterQ: the resonant design)
+    more += ['-DSIG_VP_S_RES=1'] if any(op in _native.VP_RES_OPS + _native.VP_EQ_OPS for op, *_ in code) else []    # (FilterQ, FilterEq: the resonant design)
+    more += ['-DSIG_VP_S_EQ=1'] if any(op in _native.VP_EQ_OPS for op, *_ in code) else []      # (FilterEq: the general numerator on top of it)
     more += ['-DSIG_VP_S_UNI=1'] if any(op in _native.VP_UNI_OPS + _native.VP_BLEP_OPS for op, *_ in code) else []    # (OscUni, OscBlep: the copies, a second kernel parameter; run-time values)
     more += ['-DSIG_VP_S_BLEP=1'] if any(op in _native.VP_BLEP_OPS for op, *_ in code) else []   # (OscBlep: the band-limited handler)
     # two or more families: the second kernel parameter carries tables and copies together, the kernel has exactly the families of the
