@@ -157,6 +157,31 @@ int sig_osc_bank_blep(int kind, int64_t position, int64_t position_step, int32_t
                       int32_t copies, const double* detune, const double* offsets,
                       void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Hard-sync oscillator, chain/ext.py SyncSawtooth / SyncSquare: sig_osc_bank_blep's arguments, checks and phase with one more
+ * parameter row, `ratio` ((1|P, V|1) f64 like spread; NULL: unplugged = 0): a slave oscillator at R = max(ratio, 1) times the pitch,
+ * reset at every cycle of the master.  kind is SIG_OSC_SAWTOOTH or SIG_OSC_SQUARE; SIG_OSC_SINE and SIG_OSC_TRIANGLE (whose reset
+ * changes the slope too) are hipErrorInvalidValue.  With r_u, h_u, q_u, t_u, d and step(m) (at d) as there, per copy, voice and
+ * parameter row  ds = min(d R, 0.5)  and  g = R - (ceil(R) - 1),  and per sample  m = mod(t, 1), s = m R, k = floor(s), f = s - k,
+ *   estep(p, lo_ok, hi_ok) = 2x - x*x - 1, x = p / ds  if p < ds and lo_ok  |  y*y + 2y + 1, y = (p - 1) / ds  if p > 1 - ds and hi_ok  |  0
+ *   Sawtooth: w = (2f - 1) - estep(f, k >= 1, k + 1 < R) - g step(m)
+ *   Square:   sb = s + 0.5, kb = floor(sb), fb = sb - kb
+ *             w = (f < 0.5 ? 1 : -1) + estep(f, k >= 1, k + 1 < R) - estep(fb, kb >= 1, kb + 0.5 < R) + (g <= 0.5 ? 0 : 1) step(m)
+ *   out[n,v] = (((w_0 + w_1) + w_2) + ...) / copies
+ * The kernel multiplies by a rounded 1 / d and 1 / ds (divides per copy, voice and parameter row, none per sample): the float64 value
+ * in front of the store is within 1e-14 of the expression evaluated in numpy's order.  A ratio that is not finite gives NaN rows for
+ * that voice; ratio <= 1 is the band-limited oscillator (the Sawtooth's at phase + 0.5).  d == 0 selects no window; a non-finite t
+ * gives NaN.  Where the last interior edge lies closer to the reset than one window (g < ds; Square: 0 < g mod 0.5 < ds) its trailing
+ * window is cut at the reset: the expression is the definition there too.  Above ds = 0.5 it no longer band-limits.  Position-pure.
+ * Argument errors: hipErrorInvalidValue before any HIP call. */
+int sig_osc_bank_sync(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                      int32_t voices, int32_t rows_per_param,
+                      const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                      const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                      const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+                      const double* ratio, int32_t ratio_stride, int64_t ratio_row_stride,
+                      int32_t copies, const double* detune, const double* offsets,
+                      void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Table-lookup waveshaper, chain/ext.py Shaper (build-defined: the reference has no memoryless non-linearity but Amp).  `table`
  * float32 (T, W) row-major in device memory: W transfer curves of T points each, spanning input -1 .. +1; T >= 2 (any integer: 2^k + 1
  * points put a knot at x = 0), W >= 1, T * W <= SIG_TABLE_MAX_POINTS.  For every row n and voice v, in f64, every operation rounded:
@@ -689,6 +714,12 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
  *          program.  A word of the resonant family: refused wherever FILTERQ is, and launched by kernels of its own (the resonant and
  *          the mixed variant once more with the general numerator), so that programs without the word run the code they ran before;
  *          sig_voice_program_variant still answers RESONANT or MIXED
+ *   OSCSYNC acc = hard-sync oscillator (sig_osc_bank_sync's expression, m = t - floor(t) as one v_fract_f64) of kind `kind`
+ *          (SIG_OSC_SAWTOOTH or SIG_OSC_SQUARE) with OSCBLEP's operands -- oscillator slot a, the copies of the `unison` argument,
+ *          spread = params[c], c == -1: unplugged = 0 -- and ratio = params[b] read per block, b == -1: unplugged (R = 1).  A word of
+ *          the unison family: refused wherever OSCUNI is, and launched by kernels of its own (the band-limited and the mixed variant
+ *          once more with this handler), so that programs without the word run the code they ran before; sig_voice_program_variant
+ *          still answers BLEP or MIXED.  Refused together with FILTEREQ by every entry (no kernel set has both)
  * The accumulator after the last instruction is the voice's sample of that row.  Rows (sig_vp_rows) are float64 (rows, voices | 1)
  * arrays, col_stride 1 | 0: rows == 1 holds for every block; otherwise rows == control_rows, one row per block:
  *   block_frames >= context:  [the block in front of the first history block | hist_blocks history blocks | nblocks blocks],
@@ -713,10 +744,10 @@ int sig_fused_voice_bus(int osc_kind, int filt_type, int32_t rate, int64_t posit
 enum { SIG_VP_OSC = 0, SIG_VP_FILTER = 1, SIG_VP_GAIN = 2, SIG_VP_MUL = 3, SIG_VP_MIX = 4, SIG_VP_SAVE = 5, SIG_VP_LOAD = 6,
        SIG_VP_CONST = 7, SIG_VP_AMP = 8, SIG_VP_ADSR = 9, SIG_VP_NOISE = 10, SIG_VP_BAND = 11, SIG_VP_OSCPM = 12,
        SIG_VP_OSCTABLE = 13, SIG_VP_SHAPE = 14, SIG_VP_FILTERQ = 15, SIG_VP_OSCUNI = 16, SIG_VP_OSCBLEP = 17,
-       SIG_VP_FILTEREQ = 18 };
+       SIG_VP_FILTEREQ = 18, SIG_VP_OSCSYNC = 19 };
 enum { SIG_VP_MAX_TABLES = 2, SIG_VP_MAX_UNISON = 1 };
 enum { SIG_VP_MAX_INS = 32, SIG_VP_MAX_OSCS = 4, SIG_VP_MAX_PARAMS = 8, SIG_VP_MAX_FILTERS = 4, SIG_VP_MAX_TEMPS = 4, SIG_VP_MAX_HIST = 3 };
-typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI, OSCBLEP: c may be -1; FILTEREQ: c and b may */
+typedef struct { int32_t op, kind, a, b, c; } sig_vp_ins;                          /* a, b, c in 0..15; OSCTABLE, SHAPE, FILTERQ, OSCUNI, OSCBLEP: c may be -1; FILTEREQ, OSCSYNC: c and b may */
 typedef struct { const double* ptr; int32_t col_stride; int32_t rows; } sig_vp_rows;
 typedef struct {
     int32_t n_ins; sig_vp_ins ins[SIG_VP_MAX_INS];
@@ -749,7 +780,8 @@ int sig_voice_program_ex(const sig_voice_program_t* program, int32_t rate, int64
  * instruction: sig_voice_program_ex is this call with NULL.  Refused before any device work, hipErrorInvalidValue: copies out of
  * range, NULL with an OSCUNI word in the program, an OSCUNI word with b != 0, a >= n_oscs, c >= n_params or a kind above
  * SIG_OSC_TRIANGLE, and OSCUNI together with BAND, OSCPM, OSCTABLE, SHAPE or FILTERQ.  An OSCBLEP word reads the same copies and
- * is refused in the same cases, and with kind SIG_OSC_SINE. */
+ * is refused in the same cases, and with kind SIG_OSC_SINE; an OSCSYNC word likewise, and with kind SIG_OSC_TRIANGLE, b >= n_params
+ * (its b is a parameter slot or -1, not a unison slot) or a FILTEREQ word in the program. */
 typedef struct { int32_t copies; double detune[SIG_UNISON_MAX_COPIES], offset[SIG_UNISON_MAX_COPIES]; } sig_vp_unison_t;
 int sig_voice_program_unison(const sig_voice_program_t* program, int32_t rate, int64_t position, int32_t block_frames,
                              int32_t nblocks, int32_t context, int32_t voices, int32_t control_rows,

@@ -53,7 +53,7 @@ CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 # ---- sig_voice_program: the per-voice graph as code for the accumulator machine of voice_program.hip
 VP_OPS = {'Osc': 0, 'Filter': 1, 'Gain': 2, 'Mul': 3, 'Mix': 4, 'Save': 5, 'Load': 6, 'Const': 7, 'Amp': 8, 'Adsr': 9, 'Noise': 10,
-          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15, 'OscUni': 16, 'OscBlep': 17, 'FilterEq': 18}
+          'Band': 11, 'OscPM': 12, 'OscTable': 13, 'Shape': 14, 'FilterQ': 15, 'OscUni': 16, 'OscBlep': 17, 'FilterEq': 18, 'OscSync': 19}
 VP_EXT_OPS = ('Amp', 'Adsr', 'Noise')       # the instructions of the extended handlers (the full register file, or SIG_VP_S_EXT)
 VP_MAX_INS, VP_MAX_OSCS, VP_MAX_PARAMS, VP_MAX_FILTERS, VP_MAX_TEMPS, VP_MAX_HIST = 32, 4, 8, 4, 4, 3
 VP_MAX_TABLES = 2
@@ -62,6 +62,7 @@ VP_RES_OPS = ('FilterQ',)                   # the instruction of the resonant va
 VP_EQ_OPS = ('FilterEq',)                   # FilterQ on an equaliser slot (ext.py EqFilter; SIG_VP_S_RES and SIG_VP_S_EQ): gain = parameter slot b | -1 too; the same family
 VP_UNI_OPS = ('OscUni',)                    # the instruction of the unison variant (SIG_VP_S_UNI): oscillator slot a, unison slot b = 0, spread = parameter slot c | -1
 VP_BLEP_OPS = ('OscBlep',)                  # OscUni with the band-limited waveforms (ext.py BlepOsc; SIG_VP_S_UNI and SIG_VP_S_BLEP): the same operands, the same family
+VP_SYNC_OPS = ('OscSync',)                  # OscBlep with a slave oscillator reset by the master (ext.py SyncOsc; SIG_VP_S_UNI and SIG_VP_S_SYNC): ratio = parameter slot b | -1 too; the same family
 VP_MAX_UNISON = 1                           # SIG_VP_MAX_UNISON: unison slots of a voice program (one `copies` array per launch)
 # the families of which a single-family interpreter variant (and sig_voice_program, _ex, _unison) has at most one; a program with two
 # or more of them is a MIXED program (sig_voice_program_mixed, SIG_VP_S_MIXED)
@@ -132,6 +133,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
         'sig_osc_bank_unison': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_osc_bank_blep': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
+        'sig_osc_bank_sync': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
@@ -455,6 +457,24 @@ def osc_bank_blep(kind: str, position: int, rate: int, hertz: torch.Tensor, phas
     with each copy's waveform corrected by a two-sample polynomial step around its edges (ext.py BlepOsc), the window d =
     min(|hertz * (1 + spread * d_u)| / rate, 0.5) per copy.  Same arguments."""
     return _osc_bank_copies('sig_osc_bank_blep', kind, position, rate, hertz, phase, spread, copies, out, step, rows_per_param)
+
+
+def osc_bank_sync(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, spread: torch.Tensor | None,
+                  ratio: torch.Tensor | None, copies, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- hard-sync oscillator `kind` ('Sawtooth' | 'Square'; sig_osc_bank_sync): `osc_bank_blep` with a slave
+    oscillator at max(ratio, 1) times the pitch, reset at every cycle of the master (ext.py SyncOsc).  ratio: (1|P, V|1) f64 like
+    spread; None: unplugged = 0, the band-limited oscillator."""
+    _gpu(hertz, phase, spread, ratio, out)
+    _audio(out, 'osc out')
+    rows, voices = out.shape
+    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'), (ratio, 'ratio'), form=_ctrl_rows)
+    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'spread'),
+                                     (params[15], 'ratio'))
+    U, detune, offsets = _copies(copies)
+    _check(lib().sig_osc_bank_sync(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
+                                   *params[0:3], *params[4:7], *params[8:11], *params[12:15], U, detune, offsets,
+                                   out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_sync')
+    return out
 
 
 def shaper_table(x: torch.Tensor, select: torch.Tensor | None, table: torch.Tensor, out: torch.Tensor,
@@ -1120,7 +1140,7 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
                   adsr: dict | None = None, noise_seeds: tuple = (0, 0), workspace: torch.Tensor | None = None,
                   status: torch.Tensor | None = None, blocks_before: int = 0, tables: list | None = None,
                   unison=None) -> torch.Tensor:
-    """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison, or -- a program of two or more families, `vp_families` -- sig_voice_program_mixed; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni and OscBlep words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
+    """One launch for a whole per-voice graph (sig_voice_program_ex, or with `unison` sig_voice_program_unison, or -- a program of two or more families, `vp_families` -- sig_voice_program_mixed; `tables`: the float32 (T, W) tables of its OscTable and Shape words; `unison`: the host (U, 2) copies array of its OscUni, OscBlep and OscSync words, by value).  `code`: (op name, kind, a, b, c) tuples; `oscs`: (hertz,
     phase | None) row tensors per oscillator slot; `params`: row tensors per parameter register; `filters`: (cutoff rows,
     'lp' | 'hp' ('rlp' | 'rhp': a resonant slot, run by a FilterQ word whose c names the parameter register of its q rows; 'eqbp' ... 'eqhs': an equaliser slot, run by a FilterEq word whose c names the q rows and whose b the gain rows), level = 1 + the filters in series in front of it) per filter slot.  Rows are float64 (1 | control_rows, 1 | voices).  out (nblocks * block_frames, voices) float32,
     or with `bus` (.., C) = the sum over voices weighted by bus_gains."""
@@ -1186,13 +1206,13 @@ def voice_program(code: list, oscs: list, params: list, filters: list, n_temps: 
 
 def vp_families(code: list) -> tuple:
     """the families (keys of VP_FAMILIES) a program given as (op name, kind, a, b, c) tuples has words of"""
-    ops = {'OscUni' if op in VP_BLEP_OPS else 'FilterQ' if op in VP_EQ_OPS else op for op, *_ in code}   # (OscBlep: a word of the unison family; FilterEq: of the resonant family)
+    ops = {'OscUni' if op in VP_BLEP_OPS + VP_SYNC_OPS else 'FilterQ' if op in VP_EQ_OPS else op for op, *_ in code}   # (OscBlep, OscSync: words of the unison family; FilterEq: of the resonant family)
     return tuple(name for name, words in VP_FAMILIES.items() if ops & set(words))
 
 
 def voice_program_words(code: list) -> list:
     """the machine words of a program given as (op name, kind, a, b, c) tuples: op | kind << 5 | a << 8 | b << 12 | c << 16"""
-    return [VP_OPS[op] | (kind << 5) | (a << 8) | ((b & 15) << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's, FilterQ's, OscUni's, OscBlep's and FilterEq's c = -1: 15; FilterEq's b too)
+    return [VP_OPS[op] | (kind << 5) | (a << 8) | ((b & 15) << 12) | ((c & 15) << 16) for op, kind, a, b, c in code]   # (OscTable's, Shape's, FilterQ's, OscUni's, OscBlep's, FilterEq's and OscSync's c = -1: 15; FilterEq's and OscSync's b too)
 
 
 def voice_program_geometry(voices: int, block_frames: int, nblocks: int, context: int, depth: int, bus_channels: int,

@@ -394,6 +394,65 @@ class BlepTriangle(BlepOsc):
         return 'Triangle'
 
 
+class SyncOsc(BlepOsc, abc.ABC):
+    """Oscillator hard sync, band-limited: a slave sawtooth or square running at `ratio` times the pitch is reset at every cycle of a
+    master at `hertz` -- the sync lead, and with a swept ratio the formant-like "tearing" sweep.  `BlepOsc` -- the same ports hertz,
+    phase and spread, the same `copies` state, validator and default of one copy, the same master phase t_u per copy bit for bit --
+    with one more block-rate port, `ratio` (dimensionless).  Unplugged means zeros, like every port, and a ratio <= 1 means 1: the
+    node is then an ordinary band-limited oscillator (the Sawtooth `BlepSawtooth` at phase + 0.5, the Square `BlepSquare`).  There is
+    no Sine or Triangle: their reset also changes the slope.  The slave's value is a pure function of the master's phase:
+    position-pure, no carried phase, no table.  For copy u, row n and voice v, in float64 and every operation rounded:
+        r_u, h_u, q_u, t_u, d and step(m) (at d) as BlepOsc
+        R  = max(ratio[v], 1.0)                                          (a ratio that is not finite: NaN rows for that voice)
+        m  = mod(t, 1);  s = m * R;  k = floor(s);  f = s - k            (the slave's phase f in its k-th cycle since the reset)
+        ds = min(d * R, 0.5)                                             (the slave's increment per sample)
+        g  = R - (ceil(R) - 1)                                           (the length of the last, cut slave cycle, in (0, 1])
+        estep(p, lo_ok, hi_ok) = 2x - x*x - 1    with x = p / ds         if p < ds      and lo_ok
+                               = y*y + 2y + 1    with y = (p - 1) / ds   if p > 1 - ds  and hi_ok
+                               = 0                                       otherwise
+        Sawtooth: w = (2f - 1) - estep(f, k >= 1, k + 1 < R) - g * step(m)
+        Square:   sb = s + 0.5;  kb = floor(sb);  fb = sb - kb
+                  w  = (f < 0.5 ? 1 : -1) + estep(f, k >= 1, k + 1 < R) - estep(fb, kb >= 1, kb + 0.5 < R) + (g <= 0.5 ? 0 : 1) * step(m)
+        out = (sum over u ascending of w_u) / U
+    (kernel: sig_osc_bank_sync, which multiplies by a rounded 1 / d and 1 / ds where this divides: within 1e-14; restated in numpy
+    by tests/sync_reference.py).  The slave's edges strictly inside the master's cycle take the residual at the slave's rate; the
+    reset at m = 0 -- of height 2 g for the Sawtooth, 0 or 2 for the Square -- takes the one at the master's.  Every choice is a
+    select: d = 0 (0 Hz) selects no window, a non-finite t gives NaN, hertz < 0 uses |h|.
+    The definition is continuous in t everywhere but for one case: where the last interior edge lies closer to the reset than one
+    window -- the Sawtooth: g < ds; the Square: the distance g mod 0.5 < ds where it is not 0 -- that edge's trailing window is cut at
+    the reset, and the sample jumps there by what the window had left.  The formula is the definition there too.  Above ds = 0.5
+    (ratio * hertz above rate / 2) ds is clamped and the formula no longer band-limits (at 1734 Hz and ratio 13.9 the fold-back is
+    +12 dB over the harmonics).  Well below that the slave's own partials already fold: at ratio 5 and 1734 Hz, where the naive
+    wave's fold-back is at -5 dB of the harmonics' power, the correction leaves -18 dB (-24 .. -28 dB at ratios 1.5 .. 3.3).
+    Out of scope: what BlepOsc leaves out; a frame-rate ratio; soft sync and reversing sync; a synced Sine or Triangle; a combination
+    with an equaliser biquad (`EqFilter`) in one voice program (such a graph stays one kernel per node)."""
+    ratio: Receiver.BoundPort = port('ratio')
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        phase = as_control(self.phase.forward_at_block_rate(request))
+        hertz = as_control(self.hertz.forward_at_block_rate(request))
+        spread = as_control(self.spread.forward_at_block_rate(request))
+        ratio = as_control(self.ratio.forward_at_block_rate(request))          # unplugged: zeros((1, 1)), R = 1
+        loc = request.loc
+        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, spread.shape, ratio.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
+        return _native.osc_bank_sync(self.kind(), loc.position, loc.rate, hertz, phase, spread, ratio, self.host_copies(), out)
+
+
+class SyncSawtooth(SyncOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Sawtooth'
+
+
+class SyncSquare(SyncOsc):
+
+    @classmethod
+    def kind(cls) -> str:
+        return 'Square'
+
+
 def _validate_curves(instance, attribute, new_value):
     ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
           and new_value.shape[0] >= 2 and new_value.shape[1] >= 1

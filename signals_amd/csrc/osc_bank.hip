@@ -574,7 +574,151 @@ int dispatch_blep_kind(int kind, const OscArgs& a, const UniArgs& un, OUT* out, 
     return (int)hipErrorInvalidValue;                              // (Sine: it has no edge to correct)
 }
 
+// ---- hard sync (chain/ext.py SyncOsc): osc_bank_blep_kernel's tiling, pieces and loops with sig_osc::osc_sync as the waveform and
+// one more parameter row, the ratio.  Block-invariant and hoisted like d and 1 / d: per voice and piece R, g and the reset's weight
+// (sig_osc::sync_ratio), per copy, voice and piece ds and 1 / ds -- a third IEEE divide there, none per sample.  Every lane evaluates every
+// residual and selects.  No table, no LDS, no carried state.
+struct SyncArgs { const double* ratio; int rs; int64_t rrs; };      // (1|P, V|1) f64 like hertz / phase; NULL: unplugged = 0 (R = 1)
+
+template <int KIND, int VEC, typename OUT>
+__global__ __launch_bounds__(256) void osc_bank_sync_kernel(OscArgs a, UniArgs un, SyncArgs sy, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int vt = blockIdx.x % voice_tiles;
+    const int64_t rt = blockIdx.x / voice_tiles;
+    const int v0 = (vt * SIG_WAVE + lane) * VEC;
+    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    if (r0 >= a.rows) return;                                      // wave-uniform
+    const int nrows = (int)((a.rows - r0 < (int64_t)kRowsPerWave) ? a.rows - r0 : (int64_t)kRowsPerWave);
+
+    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const int copies = un.copies;                                  // 1 .. SIG_UNISON_MAX_COPIES (checked by the entry)
+
+    double s[kRowsPerWave][VEC];
+#pragma unroll
+    for (int j = 0; j < kRowsPerWave; ++j)
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) s[j][i] = 0.0;
+    for (int j0 = 0; j0 < nrows;) {                                // pieces of one parameter row each (wave-uniform bounds)
+        const int64_t prow = a.rpp ? (r0 + j0) / a.rpp : 0;
+        const int64_t left = a.rpp ? (prow + 1) * a.rpp - r0 : (int64_t)nrows;
+        const int j1 = (left < (int64_t)nrows) ? (int)left : nrows;
+        double hz[VEC], ph[VEC], sp[VEC];
+        sig_osc::SyncRatio ra[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const int v = v0 + i;
+            hz[i] = (v < a.voices) ? a.hertz[prow * a.hrs + (int64_t)v * a.hs] : 0.0;
+            ph[i] = (v < a.voices && a.phase) ? a.phase[prow * a.prs + (int64_t)v * a.ps] : 0.0;
+            sp[i] = (v < a.voices && un.spread) ? un.spread[prow * un.srs + (int64_t)v * un.ss] : 0.0;
+            ra[i] = sig_osc::sync_ratio<KIND>((v < a.voices && sy.ratio) ? sy.ratio[prow * sy.rrs + (int64_t)v * sy.rs] : 0.0);
+        }
+        for (int u = 0; u < copies; ++u) {                         // wave-uniform trip count
+            const double du = un.detune[u], pu = un.offset[u];     // (scalar loads from the argument block)
+            double h[VEC], qu[VEC], d[VEC], inv_d[VEC], ds[VEC], inv_ds[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const double r = 1.0 + sp[i] * du;
+                h[i] = hz[i] * r;
+                qu[i] = ph[i] + pu;
+                sig_osc::blep_increment(h[i], a.rate, d[i], inv_d[i]);
+                sig_osc::sync_increment(d[i], ra[i].R, ds[i], inv_ds[i]);
+            }
+#pragma unroll
+            for (int j = 0; j < kRowsPerWave; ++j) {
+                if (j >= j0 && j < j1) {                           // wave-uniform
+                    const double q = sig_readlane_f64(q_lane, j);
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        const double w = sig_osc::osc_sync<KIND>(q * h[i] + qu[i], d[i], inv_d[i], ra[i], ds[i], inv_ds[i]);
+                        s[j][i] = (u == 0) ? w : s[j][i] + w;
+                    }
+                }
+            }
+        }
+        j0 = j1;
+    }
+    const double count = (double)copies;
+#pragma unroll
+    for (int j = 0; j < kRowsPerWave; ++j) {
+        if (j < nrows) {                                           // wave-uniform: row r0 + j < a.rows
+            OUT y[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) y[i] = (OUT)(s[j][i] / count);
+            OUT* dst = out + (r0 + j) * ld + v0;
+            if (VEC == 4) {
+                if (v0 < a.voices) {                               // voices % 4 == 0 on this path
+                    typename sig_vec4<OUT>::type o;
+                    o.x = y[0]; o.y = y[1]; o.z = y[2]; o.w = y[3];
+                    *reinterpret_cast<typename sig_vec4<OUT>::type*>(dst) = o;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    if (v0 + i < a.voices) dst[i] = y[i];
+            }
+        }
+    }
+}
+
+template <int KIND, typename OUT>
+int launch_sync(const OscArgs& a, const UniArgs& un, const SyncArgs& sy, OUT* out, int64_t ld, hipStream_t stream)
+{
+    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
+                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
+    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
+    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
+    const int span = SIG_WAVE * (vec4 ? 4 : 1);
+    const int voice_tiles = (a.voices + span - 1) / span;
+    const int64_t nwg = row_tiles * voice_tiles;
+    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    if (vec4)
+        osc_bank_sync_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, sy, out, ld, voice_tiles);
+    else
+        osc_bank_sync_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, sy, out, ld, voice_tiles);
+    return sig_launch_status();
+}
+
+template <typename OUT>
+int dispatch_sync_kind(int kind, const OscArgs& a, const UniArgs& un, const SyncArgs& sy, OUT* out, int64_t ld, hipStream_t stream)
+{
+    switch (kind) {
+        case SIG_OSC_SQUARE: return launch_sync<SIG_OSC_SQUARE, OUT>(a, un, sy, out, ld, stream);
+        case SIG_OSC_SAWTOOTH: return launch_sync<SIG_OSC_SAWTOOTH, OUT>(a, un, sy, out, ld, stream);
+    }
+    return (int)hipErrorInvalidValue;                              // (Sine, Triangle: their reset changes the slope too)
+}
+
 }  // namespace
+
+extern "C" int sig_osc_bank_sync(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                                 int32_t voices, int32_t rows_per_param,
+                                 const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                                 const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                                 const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+                                 const double* ratio, int32_t ratio_stride, int64_t ratio_row_stride,
+                                 int32_t copies, const double* detune, const double* offsets,
+                                 void* out, int32_t out_dtype, int64_t out_ld, void* stream)
+{
+    SIG_CHECK_ARG(kind == SIG_OSC_SQUARE || kind == SIG_OSC_SAWTOOTH);
+    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
+    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
+                  (spread_stride == 0 || spread_stride == 1) && (ratio_stride == 0 || ratio_stride == 1));
+    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && spread_row_stride >= 0 && ratio_row_stride >= 0);
+    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
+    if (rows == 0 || voices == 0) return 0;
+    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
+                    phase, phase_stride, phase_row_stride, rows_per_param};
+    UniArgs un{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
+    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
+    const SyncArgs sy{ratio, ratio_stride, ratio_row_stride};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_dtype == SIG_F32) return dispatch_sync_kind<float>(kind, a, un, sy, static_cast<float*>(out), out_ld, s);
+    return dispatch_sync_kind<double>(kind, a, un, sy, static_cast<double*>(out), out_ld, s);
+}
 
 extern "C" int sig_osc_bank_blep(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
                                  int32_t voices, int32_t rows_per_param,

@@ -202,6 +202,57 @@ __device__ __forceinline__ void blep_increment(double h, double rate, double& d,
     inv_d = 1.0 / d;
 }
 
+// ---- hard-sync Sawtooth / Square (chain/ext.py SyncOsc): a slave oscillator at R = max(ratio, 1) times the master's pitch, reset at
+// every cycle of the master; on top of the band-limited forms above.  With m = mod(t, 1) the master's phase, the slave's is
+// s = m R, k = floor(s) its cycle since the reset and f = s - k (exact) its phase.  The slave's own edges, those strictly inside the
+// master's cycle, take the residual at the slave's increment ds = min(d R, 0.5) (sync_residual: blep_residual<2> whose two sides are
+// each switched by a condition on k); the reset at m = 0, of height 2 g for the Sawtooth (g = R - (ceil(R) - 1), the length of the
+// last, cut slave cycle) and 0 | 2 for the Square (g <= 0.5 | g > 0.5), takes blep_residual<2> at the master's d, weighted.
+// Block-invariant, hoisted by the caller: per voice R, g and the reset's weight (sync_ratio), per copy ds and 1 / ds
+// (sync_increment).  A ratio that is not finite makes R a NaN (a select: fmax would drop it), and with it s, f and the sample; the
+// Square's naive part passes a NaN f on like osc_blep's.  d == 0: ds == 0, no window, as above.  Where the last interior edge lies
+// closer to the reset than one window (g < ds; the Square: 0 < g mod 0.5 < ds) its trailing window is cut at the reset: the
+// definition's own discontinuity (ext.py), the same selects here.
+struct SyncRatio { double R, g, reset; };
+template <int KIND> __device__ __forceinline__ SyncRatio sync_ratio(double ratio) {
+    static_assert(KIND == SIG_OSC_SQUARE || KIND == SIG_OSC_SAWTOOTH, "hard sync: Sawtooth and Square (a reset of Sine or Triangle changes the slope too)");
+    SyncRatio p;
+    p.R = (fabs(ratio) < __builtin_inf()) ? fmax(ratio, 1.0) : __builtin_nan("");
+    p.g = p.R - (ceil(p.R) - 1.0);
+    p.reset = (KIND == SIG_OSC_SAWTOOTH) ? p.g : ((p.g <= 0.5) ? 0.0 : 1.0);
+    return p;
+}
+
+__device__ __forceinline__ void sync_increment(double d, double R, double& ds, double& inv_ds) {
+    ds = fmin(d * R, 0.5);                                                     // (a NaN R: the sample is NaN anyway)
+    inv_ds = 1.0 / ds;
+}
+
+__device__ __forceinline__ double sync_residual(double p, double ds, double inv_ds, bool lo_ok, bool hi_ok) {
+    const bool low = p < ds;
+    const bool below = low & lo_ok, above = (p > 1.0 - ds) & hi_ok;            // (they exclude each other for ds <= 0.5)
+    const double z = low ? p * inv_ds - 1.0 : (p - 1.0) * inv_ds + 1.0;
+    const double q = z * z;
+    return below ? -q : (above ? q : 0.0);
+}
+
+// FUSED: m by v_fract_f64 (the program handlers), else numpy's mod (the per-node kernel: s, k and f are then the restatement's bits)
+template <int KIND, bool FUSED = false>
+__device__ __forceinline__ double osc_sync(double t, double d, double inv_d, const SyncRatio& r, double ds, double inv_ds) {
+    static_assert(KIND == SIG_OSC_SQUARE || KIND == SIG_OSC_SAWTOOTH, "hard sync: Sawtooth and Square");
+    const double m = blep_mod1<FUSED>(t);
+    const double s = m * r.R;
+    const double k = floor(s);
+    const double f = s - k;
+    const double edge = sync_residual(f, ds, inv_ds, k >= 1.0, k + 1.0 < r.R);
+    const double reset = r.reset * blep_residual<2>(m, d, inv_d);
+    if (KIND == SIG_OSC_SAWTOOTH) return (fma(f, 2.0, -1.0) - edge) - reset;   // (2f is exact: the single rounding of 2 * f - 1)
+    const double sb = s + 0.5;
+    const double kb = floor(sb);
+    const double naive = (f < 0.5) ? 1.0 : ((f >= 0.5) ? -1.0 : f);
+    return ((naive + edge) - sync_residual(sb - kb, ds, inv_ds, kb >= 1.0, kb + 0.5 < r.R)) + reset;
+}
+
 template <int KIND, typename OUT> __device__ __forceinline__ OUT osc_wave(double t) {
     if (KIND == SIG_OSC_SINE) {
         if (sizeof(OUT) == 4) return (OUT)osc_sine_f32(t);

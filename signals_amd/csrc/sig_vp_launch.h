@@ -66,5 +66,7 @@ extern template struct VpLaunch<vp_family::blep>;
 extern template struct VpLaunch<vp_family::mixed>;
 extern template struct VpLaunch<vp_family::resonant_eq>;
 extern template struct VpLaunch<vp_family::mixed_eq>;
+extern template struct VpLaunch<vp_family::sync>;
+extern template struct VpLaunch<vp_family::mixed_sync>;
 
 }  // namespace sig_vp

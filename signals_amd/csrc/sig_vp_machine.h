@@ -222,6 +222,10 @@ template <bool SMALL> struct VpLimits {
 // block-rate control, the gain, from the parameter rows the word's b names.  A flag of its own -- a second set of kernels, RES+EQ
 // (vp_family::resonant_eq) and MIXED+EQ (vp_family::mixed_eq), which the launch picks exactly when the program has the word -- so
 // that programs without it keep the code of the RES and MIXED variants (the taps cost 5 x NF x VPT doubles of state)
+// SYN: the OscSync instruction (hard-sync oscillators, ext.py SyncOsc) on top of BLP, whose copies, operands and residual it shares,
+// with a fourth block-rate control, the ratio, from the parameter rows the word's b names.  A flag of its own and a second set of
+// kernels once more -- BLP+SYN (vp_family::sync) and MIXED+SYN (vp_family::mixed_sync), picked by the launch exactly when the
+// program has the word -- so that programs without it keep the code of the BLEP and MIXED variants.  Never with EQ
 // The "never with" above is the single-family variants'.  The MIXED variant (vp_family::mixed, reached only through
 // sig_voice_program_mixed) has all seven flags on and a VpMixed as `tb`.  What the flags share then, and why it holds:
 //   * RES on: every LowPass / HighPass slot is designed by vp_design_res at d = sqrt2 (`single` is off), which are vp_design's bits;
@@ -237,9 +241,10 @@ namespace sig_vp {
 
 // One interpreter variant: the flags above, and `Extra`, the second kernel parameter that follows from them (two or more of the
 // five families: both the tables and the copies).
-template <bool BAND_, bool PM_, bool TAB_, bool SHP_, bool RES_, bool UNI_, bool BLP_, bool EQ_>
+template <bool BAND_, bool PM_, bool TAB_, bool SHP_, bool RES_, bool UNI_, bool BLP_, bool EQ_, bool SYN_>
 struct VpFamily {
-    static constexpr bool BAND = BAND_, PM = PM_, TAB = TAB_, SHP = SHP_, RES = RES_, UNI = UNI_, BLP = BLP_, EQ = EQ_;
+    static constexpr bool BAND = BAND_, PM = PM_, TAB = TAB_, SHP = SHP_, RES = RES_, UNI = UNI_, BLP = BLP_, EQ = EQ_, SYN = SYN_;
+    static_assert(BLP || !SYN, "OscSync sits on top of BLP");
     static_assert(TAB || !SHP, "Shape sits on top of TAB");
     static_assert(UNI || !BLP, "OscBlep sits on top of UNI");
     static_assert(RES || !EQ, "FilterEq sits on top of RES");
@@ -250,19 +255,22 @@ struct VpFamily {
 
 // the nine variants the interpreter is built in, in the order of SIG_VP_FAMILY_* (include/signals_amd.h)
 namespace vp_family {
-//                       BAND   PM     TAB    SHP    RES    UNI    BLP    EQ
-using plain    = VpFamily<false, false, false, false, false, false, false, false>;
-using band     = VpFamily<true,  false, false, false, false, false, false, false>;
-using pm       = VpFamily<false, true,  false, false, false, false, false, false>;
-using table    = VpFamily<false, false, true,  false, false, false, false, false>;
-using shape    = VpFamily<false, false, true,  true,  false, false, false, false>;
-using resonant = VpFamily<false, false, false, false, true,  false, false, false>;
-using unison   = VpFamily<false, false, false, false, false, true,  false, false>;
-using blep     = VpFamily<false, false, false, false, false, true,  true,  false>;
-using mixed    = VpFamily<true,  true,  true,  true,  true,  true,  true,  false>;
+//                       BAND   PM     TAB    SHP    RES    UNI    BLP    EQ     SYN
+using plain    = VpFamily<false, false, false, false, false, false, false, false, false>;
+using band     = VpFamily<true,  false, false, false, false, false, false, false, false>;
+using pm       = VpFamily<false, true,  false, false, false, false, false, false, false>;
+using table    = VpFamily<false, false, true,  false, false, false, false, false, false>;
+using shape    = VpFamily<false, false, true,  true,  false, false, false, false, false>;
+using resonant = VpFamily<false, false, false, false, true,  false, false, false, false>;
+using unison   = VpFamily<false, false, false, false, false, true,  false, false, false>;
+using blep     = VpFamily<false, false, false, false, false, true,  true,  false, false>;
+using mixed    = VpFamily<true,  true,  true,  true,  true,  true,  true,  false, false>;
 // the second set of RESONANT and MIXED, for programs with a FilterEq word (no SIG_VP_FAMILY_* of their own: the launch picks them)
-using resonant_eq = VpFamily<false, false, false, false, true, false, false, true>;
-using mixed_eq    = VpFamily<true,  true,  true,  true,  true, true,  true,  true>;
+using resonant_eq = VpFamily<false, false, false, false, true, false, false, true, false>;
+using mixed_eq    = VpFamily<true,  true,  true,  true,  true, true,  true,  true, false>;
+// the second set of BLEP and MIXED, for programs with an OscSync word (likewise picked by the launch; never together with FilterEq)
+using sync       = VpFamily<false, false, false, false, false, true, true, false, true>;
+using mixed_sync = VpFamily<true,  true,  true,  true,  true,  true, true, false, true>;
 }  // namespace vp_family
 
 }  // namespace sig_vp
@@ -274,7 +282,7 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
                                         [[maybe_unused]] const float* tab)
 {
     // (the body reads the family's flags by their bare names)
-    [[maybe_unused]] constexpr bool BAND = FAM::BAND, PM = FAM::PM, TAB = FAM::TAB, SHP = FAM::SHP, RES = FAM::RES, UNI = FAM::UNI, BLP = FAM::BLP, EQ = FAM::EQ;
+    [[maybe_unused]] constexpr bool BAND = FAM::BAND, PM = FAM::PM, TAB = FAM::TAB, SHP = FAM::SHP, RES = FAM::RES, UNI = FAM::UNI, BLP = FAM::BLP, EQ = FAM::EQ, SYN = FAM::SYN;
     constexpr int RG = SMALL ? kRowGroup : kRowGroup / 2;                      // rows per instruction dispatch (the full register file: four temporaries of a row group each)
     constexpr bool BUS = C > 0;
     constexpr int CC = BUS ? C : 1;
@@ -817,6 +825,66 @@ __device__ __forceinline__ void vp_wave(const VpArgs& a, double* tile, int lane,
 #pragma unroll
                             for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
                     });
+                    continue;
+                }
+            }
+            if constexpr (SYN) {                                               // OscSync: OscBlep's operands and copies, the ratio in params[b], sig_osc_bank_sync's waveforms
+                if (op == SIG_VP_OSCSYNC) {
+                    // the OscBlep handler with sig_osc::osc_sync (m by v_fract_f64).  R, g and the reset's weight per voice, ds and
+                    // 1 / ds per copy and voice are block-invariant like d and 1 / d: recomputed per group, three divides per copy and
+                    // voice for the group's R rows; the rows multiply
+                    double sp[VPT], ratio[VPT];
+#pragma unroll
+                    for (int i = 0; i < VPT; ++i) { sp[i] = 0.0; ratio[i] = 0.0; }     // (15: spread / ratio unplugged)
+                    if (ic < NP) {
+                        with_index<NP>(ic, [&](auto I) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) sp[i] = pr[decltype(I)::value][i];
+                        });
+                    }
+                    if (ib < NP) {
+                        with_index<NP>(ib, [&](auto I) {
+#pragma unroll
+                            for (int i = 0; i < VPT; ++i) ratio[i] = pr[decltype(I)::value][i];
+                        });
+                    }
+                    const int copies = tb.copies;
+                    auto run = [&](auto kind_tag) {
+                        constexpr int KIND = decltype(kind_tag)::value;
+                        sig_osc::SyncRatio ra[VPT];
+#pragma unroll
+                        for (int i = 0; i < VPT; ++i) ra[i] = sig_osc::sync_ratio<KIND>(ratio[i]);
+                        with_index<NO>(ia, [&](auto I) {
+                            constexpr int S = decltype(I)::value;
+                            for (int u = 0; u < copies; ++u) {
+                                const double du = tb.detune[u], pu = tb.offset[u];
+                                double h[VPT], qu[VPT], d[VPT], inv_d[VPT], ds[VPT], inv_ds[VPT];
+#pragma unroll
+                                for (int i = 0; i < VPT; ++i) {
+                                    h[i] = ohz[S][i] * (1.0 + sp[i] * du);
+                                    qu[i] = oph[S][i] + pu;
+                                    sig_osc::blep_increment(h[i], a.rate, d[i], inv_d[i]);
+                                    sig_osc::sync_increment(d[i], ra[i].R, ds[i], inv_ds[i]);
+                                }
+#pragma unroll
+                                for (int r = 0; r < R; ++r) {
+                                    const double qr = vp_pin(q[r]);
+#pragma unroll
+                                    for (int i = 0; i < VPT; ++i) {
+                                        const double w = sig_osc::osc_sync<KIND, true>(qr * h[i] + qu[i], d[i], inv_d[i], ra[i], ds[i], inv_ds[i]);
+                                        acc[r][i] = (u == 0) ? w : acc[r][i] + w;
+                                    }
+                                }
+                            }
+                            const double count = (double)copies;
+#pragma unroll
+                            for (int r = 0; r < R; ++r)
+#pragma unroll
+                                for (int i = 0; i < VPT; ++i) acc[r][i] = acc[r][i] / count;
+                        });
+                    };
+                    if (kind == SIG_OSC_SAWTOOTH) run(std::integral_constant<int, SIG_OSC_SAWTOOTH>{});    // (Sine and Triangle are refused by the entry)
+                    else run(std::integral_constant<int, SIG_OSC_SQUARE>{});
                     continue;
                 }
             }

@@ -33,6 +33,9 @@ constexpr bool vp_static_has(int op) {
 #ifndef SIG_VP_S_BLEP
 #define SIG_VP_S_BLEP 0                    // 1: the program has an OscBlep word (with -DSIG_VP_S_UNI=1: the same copies parameter)
 #endif
+#ifndef SIG_VP_S_SYNC
+#define SIG_VP_S_SYNC 0                    // 1: the program has an OscSync word (with -DSIG_VP_S_UNI=1: the same copies parameter; the band-limited residual comes with it)
+#endif
 #ifndef SIG_VP_S_MIXED
 #define SIG_VP_S_MIXED 0                   // 1: the program combines two or more of Band, OscPM, OscTable / Shape, FilterQ, OscUni; the kernel takes a VpMixed
 #endif
@@ -61,9 +64,12 @@ void sig_vp_specialised(VpArgs a)
     static_assert(kEq == (SIG_VP_S_EQ != 0), "a program with a FilterEq word is built with -DSIG_VP_S_EQ=1, any other without");
     static_assert(kTab == (SIG_VP_S_TAB != 0), "a program with an OscTable or a Shape word is built with -DSIG_VP_S_TAB=1, any other without");
     constexpr bool kBlep = vp_static_has(SIG_VP_OSCBLEP);
-    constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI) || kBlep;               // (one family: OscBlep reads OscUni's copies)
-    static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni or an OscBlep word is built with -DSIG_VP_S_UNI=1, any other without");
+    constexpr bool kSync = vp_static_has(SIG_VP_OSCSYNC);
+    constexpr bool kUni = vp_static_has(SIG_VP_OSCUNI) || kBlep || kSync;      // (one family: OscBlep and OscSync read OscUni's copies)
+    static_assert(kUni == (SIG_VP_S_UNI != 0), "a program with an OscUni, an OscBlep or an OscSync word is built with -DSIG_VP_S_UNI=1, any other without");
     static_assert(kBlep == (SIG_VP_S_BLEP != 0), "a program with an OscBlep word is built with -DSIG_VP_S_BLEP=1, any other without");
+    static_assert(kSync == (SIG_VP_S_SYNC != 0), "a program with an OscSync word is built with -DSIG_VP_S_SYNC=1, any other without");
+    static_assert(!(kSync && kEq), "OscSync with FilterEq: no kernel set has both");
     constexpr int kFamilies = (int)kBand + (int)kPm + (int)kTab + (int)kRes + (int)kUni;
     static_assert((kFamilies >= 2) == (SIG_VP_S_MIXED != 0), "a program with two or more of Band, OscPM, OscTable / Shape, FilterQ and OscUni is built with -DSIG_VP_S_MIXED=1, any other without");
 #if !SIG_VP_S_MIXED
@@ -71,7 +77,7 @@ void sig_vp_specialised(VpArgs a)
     static_assert(!(kUni && (kTab || kBand || kPm || kRes)), "OscUni with Band, OscPM, OscTable, Shape or FilterQ: no variant has both");
     static_assert(!(kBand && kPm) && !(kTab && (kBand || kPm)), "Band, OscPM and OscTable / Shape: no variant has two of them");
 #endif
-    using F = VpFamily<kBand, kPm, kTab, kShape, kRes, kUni, kBlep, kEq>;           // exactly the families the program has
+    using F = VpFamily<kBand, kPm, kTab, kShape, kRes, kUni, kBlep || kSync, kEq, kSync>;   // exactly the families the program has (SYN sits on top of BLP)
 #if SIG_VP_S_MIXED || SIG_VP_S_TAB || SIG_VP_S_UNI
     static_assert(std::is_same_v<F::Extra, decltype(extra)>, "the second kernel parameter is the one the program's families take");
     vp_kernel_body<SIG_VP_STATIC_VPT, true, SIG_VP_STATIC_C, F>(a, extra);
@@ -105,10 +111,10 @@ std::mutex& vp_specials_lock() { static std::mutex m; return m; }
 // may this word's c be -1?  (no select / no q / no spread; encoded as 15, a slot number no register file has)
 constexpr bool vp_c_optional(int op) {
     return op == SIG_VP_OSCTABLE || op == SIG_VP_SHAPE || op == SIG_VP_FILTERQ || op == SIG_VP_OSCUNI || op == SIG_VP_OSCBLEP ||
-           op == SIG_VP_FILTEREQ;
+           op == SIG_VP_FILTEREQ || op == SIG_VP_OSCSYNC;
 }
-// ... and its b?  (FilterEq alone: no gain)
-constexpr bool vp_b_optional(int op) { return op == SIG_VP_FILTEREQ; }
+// ... and its b?  (FilterEq: no gain; OscSync: no ratio)
+constexpr bool vp_b_optional(int op) { return op == SIG_VP_FILTEREQ || op == SIG_VP_OSCSYNC; }
 // the variant that has this word's handler and no other extension word's (SIG_VP_FAMILY_*; PLAIN: every variant has it)
 constexpr int vp_word_family(int op) {
     switch (op) {
@@ -120,12 +126,13 @@ constexpr int vp_word_family(int op) {
         case SIG_VP_FILTEREQ: return SIG_VP_FAMILY_RESONANT;                   // (the same family and exclusions; its kernels: VpNeeds::eq)
         case SIG_VP_OSCUNI: return SIG_VP_FAMILY_UNISON;
         case SIG_VP_OSCBLEP: return SIG_VP_FAMILY_BLEP;
+        case SIG_VP_OSCSYNC: return SIG_VP_FAMILY_BLEP;                        // (the same family and exclusions; its kernels: VpNeeds::sync)
         default: return SIG_VP_FAMILY_PLAIN;
     }
 }
 
 bool vp_word_ok(const sig_vp_ins& x) {
-    return x.op >= SIG_VP_OSC && x.op <= SIG_VP_FILTEREQ && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 &&
+    return x.op >= SIG_VP_OSC && x.op <= SIG_VP_OSCSYNC && x.kind >= 0 && x.kind <= 7 && x.a >= 0 && x.a <= 15 &&
            x.b >= (vp_b_optional(x.op) ? -1 : 0) && x.b <= 15 &&
            x.c >= (vp_c_optional(x.op) ? -1 : 0) && x.c <= 15;
 }
@@ -154,6 +161,7 @@ hipFunction_t vp_find_special(const VpArgs& a, const sig_voice_program_t& P, int
 struct VpNeeds {
     int oscs, params, temps, filters; bool ext, adsr; unsigned words;
     bool eq;                                                                   // a FilterEq word: the RES+EQ / MIXED+EQ kernels (vp_family::resonant_eq, mixed_eq)
+    bool sync;                                                                 // an OscSync word: the BLP+SYN / MIXED+SYN kernels (vp_family::sync, mixed_sync)
     bool has(int family) const { return (words >> family) & 1u; }
     bool table() const { return has(SIG_VP_FAMILY_TABLE) || has(SIG_VP_FAMILY_SHAPE); }      // (Shape sits on top of the table family)
     bool uni() const { return has(SIG_VP_FAMILY_UNISON) || has(SIG_VP_FAMILY_BLEP); }        // (OscBlep: the unison family, the same copies, the same exclusions)
@@ -162,12 +170,13 @@ struct VpNeeds {
 };
 
 VpNeeds vp_needs(const sig_voice_program_t& P) {              // (n_ins was checked; any op may stand in a word)
-    VpNeeds n{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, 0u, false};
+    VpNeeds n{P.n_oscs, P.n_params, P.n_temps, P.n_filters, false, false, 0u, false, false};
     for (int k = 0; k < P.n_ins; ++k) {
         const int op = P.ins[k].op;
         if (op == SIG_VP_AMP || op == SIG_VP_ADSR || op == SIG_VP_NOISE) n.ext = true;
         if (op == SIG_VP_ADSR) n.adsr = true;
         if (op == SIG_VP_FILTEREQ) n.eq = true;
+        if (op == SIG_VP_OSCSYNC) n.sync = true;
         n.words |= 1u << vp_word_family(op);
     }
     return n;
@@ -306,6 +315,10 @@ int vp_check(const VpRequest& r, VpCall& c)
                 SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < SIG_VP_MAX_UNISON && x.c < P.n_params &&
                               x.kind >= SIG_OSC_SQUARE && x.kind <= SIG_OSC_TRIANGLE);
                 break;
+            case SIG_VP_OSCSYNC:                                               // OscBlep's operands, b: the ratio's parameter slot | -1; Sawtooth and Square
+                SIG_CHECK_ARG(unison != nullptr && x.a < P.n_oscs && x.b < P.n_params && x.c < P.n_params &&
+                              (x.kind == SIG_OSC_SAWTOOTH || x.kind == SIG_OSC_SQUARE));
+                break;
             case SIG_VP_BAND: SIG_CHECK_ARG(x.a + 1 < P.n_filters); break;
             case SIG_VP_GAIN: case SIG_VP_CONST: case SIG_VP_AMP: SIG_CHECK_ARG(x.a < P.n_params); break;
             case SIG_VP_MUL: case SIG_VP_SAVE: case SIG_VP_LOAD: SIG_CHECK_ARG(x.a < P.n_temps); break;
@@ -315,6 +328,7 @@ int vp_check(const VpRequest& r, VpCall& c)
         }
     }
     const VpNeeds need = c.need = vp_needs(P);
+    SIG_CHECK_ARG(!(need.sync && need.eq));                                    // (no kernel set has both handlers: the engine keeps such a graph per node)
     if (!r.allow_mixed) {
         const bool band = need.has(SIG_VP_FAMILY_BAND), pm = need.has(SIG_VP_FAMILY_PM), res = need.has(SIG_VP_FAMILY_RESONANT);
         SIG_CHECK_ARG(!(need.uni() && (band || pm || need.table() || res)));
@@ -438,6 +452,11 @@ int vp_launch_call(const VpRequest& r, VpCall& c)
         err = vp_variant(c.need) == SIG_VP_FAMILY_MIXED
             ? VpLaunch<vp_family::mixed_eq>::run(a, std::get<VpMixed>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s)
             : VpLaunch<vp_family::resonant_eq>::run(a, std::get<VpNoTables>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s);
+    } else if (c.need.sync) {
+        // an OscSync word: the second set of the band-limited or the mixed variant, chosen here and only here likewise
+        err = vp_variant(c.need) == SIG_VP_FAMILY_MIXED
+            ? VpLaunch<vp_family::mixed_sync>::run(a, std::get<VpMixed>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s)
+            : VpLaunch<vp_family::sync>::run(a, std::get<VpUnison>(c.extra), vpt, fits_small(c.need), C, nwg, c.table_lds, s);
     } else {
         err = vp_with_family(vp_variant(c.need), [&](auto family) {
             using F = decltype(family);

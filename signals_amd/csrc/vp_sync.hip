@@ -1,0 +1,4 @@
+// The voice-program interpreter (sig_vp_machine.h), family `sync` (BLEP + the OscSync word): its 12 kernels and their launch.
+#include "sig_vp_launch.h"
+
+SIG_VP_INSTANTIATE(sync)

@@ -389,6 +389,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.hertz, node.phase, node.index]
     if isinstance(node, ext.Wavetable):
         return [node.hertz, node.phase, node.select]
+    if isinstance(node, ext.SyncOsc):
+        return [node.hertz, node.phase, node.spread, node.ratio]
     if isinstance(node, ext.UnisonOsc):
         return [node.hertz, node.phase, node.spread]
     if isinstance(node, ext.Shaper):
@@ -889,9 +891,16 @@ class _Batch:
 
     def _sched_unison(self, node, channels, hist, rows):
         """a unison oscillator: one sig_osc_bank_unison launch (sig_osc_bank_blep for a band-limited one, ext.BlepOsc), per-block
-        hertz / phase / spread rows when one is modulated; the copies go with the launch by value, as the node's state holds them now"""
+        hertz / phase / spread rows when one is modulated; the copies go with the launch by value, as the node's state holds them now.
+        A hard-sync one (ext.SyncOsc): one sig_osc_bank_sync launch, the ratio rows with the other three"""
         hertz, phase, spread = (self._control(p, p.name) for p in (node.hertz, node.phase, node.spread))
         copies = node.host_copies()
+        if isinstance(node, ext.SyncOsc):
+            ratio = self._control(node.ratio, 'ratio')
+
+            def sync_bank(kind, position, rate, hertz, phase, spread, ratio, out, **kw):
+                return _native.osc_bank_sync(kind, position, rate, hertz, phase, spread, ratio, copies, out, **kw)
+            return self._osc_launch(node, 'osc_bank_sync', sync_bank, (hertz, phase, spread, ratio), hist, rows)
         label = 'osc_bank_blep' if node.bandlimited() else 'osc_bank_unison'
         entry = getattr(_native, label)
 
@@ -1944,6 +1953,9 @@ class _VoiceProgram:
         if len(self.code) > _native.VP_MAX_INS:
             raise _NoProgram('program too long')
         self.families = _native.vp_families(self.code)
+        words = {op for op, *_ in self.code}
+        if words & set(_native.VP_SYNC_OPS) and words & set(_native.VP_EQ_OPS):
+            raise _NoProgram('a hard-sync oscillator and an equaliser filter: no interpreter kernel set has both')
         if len(self.families) >= 2 and not mixed:
             has = set(self.families)
             if has >= {'band', 'pm'}:
@@ -2063,8 +2075,13 @@ class _VoiceProgram:
                 raise _NoProgram('two unison oscillators with distinct copies arrays: the launch carries one')
             self.unison = self.unison or n
             spread = -1 if _ctl_unplugged(n.spread) else self._param(self._control(n.spread, below))
-            word = 'OscBlep' if n.bandlimited() else 'OscUni'                  # (ext.BlepOsc: the same operands, the band-limited waveforms)
-            self.code.append((word, _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, spread))
+            if isinstance(n, ext.SyncOsc):
+                # OscBlep's operands and the ratio rows in a parameter register the word's b names (-1: unplugged, R = 1)
+                ratio = -1 if _ctl_unplugged(n.ratio) else self._param(self._control(n.ratio, below))
+                self.code.append(('OscSync', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), ratio, spread))
+            else:
+                word = 'OscBlep' if n.bandlimited() else 'OscUni'              # (ext.BlepOsc: the same operands, the band-limited waveforms)
+                self.code.append((word, _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), 0, spread))
             depth = 0
         elif isinstance(n, ext.Shaper):
             depth = self._emit(n.input.sig, below)                             # the input's sample: in the accumulator
@@ -2291,6 +2308,8 @@ class _VoiceProgram:
         Band-limited oscillators (OscBlep) keep OscUni's rule: one copy under a bus 0.46 T interpreted against 0.43 T per node, 0.35
         against 0.24 T behind a LowPass; seven copies 0.132 against 0.122 T behind a LowPass, but 0.155 against 0.156-0.158 T under a
         bare bus (three runs): there the rule costs 1-2 %, which is accepted (tools/time_blep.py).
+        Hard-sync oscillators (OscSync) keep OscUni's rule too; their throughput is not measured yet (tools/time_sync.py, DESIGN.md
+        section 7).
         Mixed programs (two or more of the families of _native.VP_FAMILIES; only compiled with `mixed_programs=True`) take the program
         under the same rule: measured (tools/time_mixed.py, 1024 voices, stereo bus, N = 256, three routes in alternation, median of 7
         windows of 0.5 s, attached kernels switched off for the interpreter) the interpreter's mixed variant runs UnisonSawtooth ->

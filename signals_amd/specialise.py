@@ -55,8 +55,9 @@ def flags(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, 
     more = ['-DSIG_VP_S_TAB=1'] if any(op in _native.VP_TABLE_OPS for op, *_ in code) else []   # (the tables: a second kernel parameter)
     more += ['-DSIG_VP_S_RES=1'] if any(op in _native.VP_RES_OPS + _native.VP_EQ_OPS for op, *_ in code) else []    # (FilterQ, FilterEq: the resonant design)
     more += ['-DSIG_VP_S_EQ=1'] if any(op in _native.VP_EQ_OPS for op, *_ in code) else []      # (FilterEq: the general numerator on top of it)
-    more += ['-DSIG_VP_S_UNI=1'] if any(op in _native.VP_UNI_OPS + _native.VP_BLEP_OPS for op, *_ in code) else []    # (OscUni, OscBlep: the copies, a second kernel parameter; run-time values)
+    more += ['-DSIG_VP_S_UNI=1'] if any(op in _native.VP_UNI_OPS + _native.VP_BLEP_OPS + _native.VP_SYNC_OPS for op, *_ in code) else []    # (OscUni, OscBlep, OscSync: the copies, a second kernel parameter; run-time values)
     more += ['-DSIG_VP_S_BLEP=1'] if any(op in _native.VP_BLEP_OPS for op, *_ in code) else []   # (OscBlep: the band-limited handler)
+    more += ['-DSIG_VP_S_SYNC=1'] if any(op in _native.VP_SYNC_OPS for op, *_ in code) else []   # (OscSync: the hard-sync handler; the ratio is a run-time row)
     # two or more families: the second kernel parameter carries tables and copies together, the kernel has exactly the families of the
     # program.  (Appended last, and only then: the list -- and with it the cache key -- of every other program is what it was)
     more += ['-DSIG_VP_S_MIXED=1'] if len(_native.vp_families(code)) >= 2 else []
