@@ -21,7 +21,9 @@ edges are hit exactly; a negative pitch, 0 Hz, 1e-3 Hz, 30 kHz, 13 kHz, then mus
 3.25 and 7.77 across the voices, unplugged is a launch of its own, and with several blocks every row changes per block.
 
 The interpreter's sync kernel sets have the OscSync handler and the earlier sets do not: a program with the word that reached another
-set would skip the word and miss every bound here, so the route tests also show that the launch picks the sync set for the word;
+set would skip the word and miss every bound here, so the route tests also show that the launch picks the sync set for the word
+-- in the one or two kernels of each set that 97 voices and these sinks reach; tests/test_gpu_vp_variants.py renders all twelve of
+`sync` and of `mixed_sync` (both register files, one and two voices per lane, the three sinks), and their short-block mode;
 that programs without the word keep their kernels is what tools/compare_kernels.py shows at build time."""
 import contextlib
 import functools

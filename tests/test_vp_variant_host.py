@@ -1,7 +1,11 @@
 """Which interpreter kernel a voice program gets, without a GPU: sig_voice_program_variant answers with the selection function the
 launch itself calls (voice_program.hip vp_variant / fits_small), so the family and the register file of a program can be pinned on
 the host.  The programs are those of the families' host tests (test_specialise_build.py, test_band_program_host.py, test_pm_host.py,
-test_shaper_host.py, test_resonant_host.py, test_unison_host.py, test_blep_host.py, test_mixed_host.py)."""
+test_shaper_host.py, test_resonant_host.py, test_unison_host.py, test_blep_host.py, test_mixed_host.py).
+
+The last part keeps the cell table of tests/test_gpu_vp_variants.py complete: its family list against the VpLaunch instantiations
+declared in sig_vp_launch.h, and the voices it renders for the second kernel sets (resonant_eq, mixed_eq, sync, mixed_sync) -- their
+programs, variants, register files and the oracle's own distance to the cells' tolerance."""
 import itertools
 
 import pytest
@@ -110,6 +114,68 @@ def test_the_mixed_patches_are_mixed(lib, which):
 def test_shape_and_blep_on_top_of_another_family_are_mixed(lib):
     assert variant([('Osc', 0, 0, 0, 0), ('Shape', 0, 0, 0, -1), ('FilterQ', 0, 0, 0, -1)], (1, 0, 1, 0)) == ('mixed', True)
     assert variant([('OscBlep', SAW, 0, 0, -1), ('Band', 0, 0, 0, 0)], (1, 0, 2, 0)) == ('mixed', True)
+
+
+# ---------------------------------------------------------------------------------------------- the cell table of test_gpu_vp_variants.py
+@pytest.fixture
+def cpu_device():
+    from signals_amd import runtime
+    old = runtime._device
+    runtime.set_device('cpu')
+    yield
+    runtime._device = old
+
+
+def test_the_cell_table_has_every_instantiated_family():
+    """a family added to sig_vp_launch.h without its 12 cells (and its short-block cells) fails here, on every machine"""
+    import re
+    import test_gpu_vp_variants as CELLS
+    header = (_native.LIB_PATH.parent / 'sig_vp_launch.h').read_text()
+    names = re.findall(r'^extern template struct VpLaunch<vp_family::(\w+)>;', header, flags=re.M)
+    assert len(names) == len(set(names)) == 13, names
+    assert set(names) == set(CELLS.FAMILIES) and len(CELLS.FAMILIES) == len(names), (names, CELLS.FAMILIES)
+    assert CELLS.FAMILIES[:len(_native.VP_VARIANTS)] == _native.VP_VARIANTS                 # the nine the C ABI names, in its order
+    rest = CELLS.FAMILIES[len(_native.VP_VARIANTS):]
+    assert set(rest) == set(CELLS.BASE) == set(CELLS.WORDS) and set(CELLS.BASE.values()) <= set(_native.VP_VARIANTS)
+
+
+#                family: (words of the small-file voice, (oscs, params, filters, temps))
+SECOND_SETS = {
+    'resonant_eq': ([('Osc', SAW, 0, 0, 0), ('Gain', 0, 0, 0, 0), ('FilterEq', 0, 0, 2, 1)], (1, 3, 1, 0)),
+    'mixed_eq': ([('OscUni', SAW, 0, 0, 0), ('Gain', 0, 1, 0, 0), ('FilterEq', 0, 0, 3, 2)], (1, 4, 1, 0)),
+    'sync': ([('OscSync', SAW, 0, 1, 0), ('Filter', 0, 0, 0, 0)], (1, 2, 1, 0)),
+    'mixed_sync': ([('OscSync', SAW, 0, 1, 0), ('FilterQ', 0, 0, 0, 2)], (1, 3, 1, 0)),
+}
+
+
+@pytest.mark.parametrize('full', [False, True], ids=['small', 'full'])
+@pytest.mark.parametrize('family', list(SECOND_SETS))
+def test_the_second_sets_voices(lib, cpu_device, family, full):
+    """the eight voices the cell table adds for the _eq and _sync kernel sets: each compiles as a mixed-enabled program with the
+    word that selects its set, lands in the base variant and the register file its cell claims, has a filter in series (the
+    short-block cells need depth > 0), and its oracle alone stays inside the cells' tolerance at both block lengths: finite, below
+    4 in magnitude (0.25 into +12 dB is 1; a resonance of 2 and the shelf's overshoot stay well under 4 times that), and the
+    float32 rounding of the oracle -- half an ulp, 2^-24 |x| < 2.4e-7 for |x| < 4 -- is below 1e-6 max(1, max|oracle|)"""
+    import numpy as np
+    import test_gpu_vp_variants as CELLS
+    from helpers import f32
+    code, counts, depth = CELLS.program(family, full)
+    if not full:
+        assert (code, counts) == SECOND_SETS[family], (code, counts)
+    else:
+        assert code[:len(SECOND_SETS[family][0])] == SECOND_SETS[family][0] and 'Adsr' in [op for op, *_ in code], code
+    assert depth == 1
+    assert variant(code, counts) == (CELLS.BASE[family], not full)
+    words = [op for op, *_ in code]
+    have, have_not = CELLS.WORDS[family]
+    assert all(w in words for w in have) and not any(w in words for w in have_not), words
+    for frames in (CELLS.N, CELLS.SHORT_N):
+        want = CELLS.wanted(family, full, frames)
+        assert want.shape == (CELLS.K * frames, CELLS.V) and np.isfinite(want).all()
+        peak, tol = float(np.abs(want).max()), CELLS.tolerance(want)
+        rounding = float(np.abs(f32(want).astype(np.float64) - want).max())
+        print('second set oracle', family, 'full' if full else 'small', frames, 'max|oracle|', peak, 'float32 rounding', rounding, 'tol', tol)
+        assert peak < 4.0 and rounding < tol, (family, full, frames, peak, rounding, tol)
 
 
 def test_bad_calls_are_refused(lib):
