@@ -351,22 +351,28 @@ def _parameter_rows(rows: int, rows_per_param: int, *counts) -> int:
     return rows_per_param
 
 
+def _osc_launch(out: torch.Tensor, position: int, step: int, rate: int, rows_per_param: int, *named, also=()):
+    """what every oscillator launch marshals the same way, from `out` and the (tensor | None, name) parameter rows, each (1|P, V|1) f64:
+    (head, rows, tail) -- head = (position, step, rate, rows, voices, rows_per_param) as the entries take them, rows = one
+    [ptr, stride, row_stride] per parameter, tail = (out, dtype, ld, stream); `also`: further tensors that must be on the GPU"""
+    _gpu(*(t for t, _ in named), *also, out)
+    _audio(out, 'osc out')
+    rows, voices = out.shape
+    flat = _voice_rows(voices, *named, form=_ctrl_rows)
+    rows_per_param = _parameter_rows(rows, rows_per_param, *((flat[4 * i + 3], name) for i, (_, name) in enumerate(named)))
+    return ((position, step, rate, rows, voices, rows_per_param), [flat[4 * i:4 * i + 3] for i in range(len(named))],
+            (out.data_ptr(), _dt(out), out.stride(0), _stream(out)))
+
+
 def osc_bank(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None,
              out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
     """out[(rows, voices)] <- oscillator `kind`; row r is absolute frame `position + r*step`.
     hertz/phase: (1|P, V|1) f64; with P > 1 parameter rows, output row r uses row r // rows_per_param."""
-    _gpu(hertz, phase, out)
-    _audio(out, 'osc out')
-    rows, voices = out.shape
-    hp, hs, hrs, hrows, pp, ps, prs, prows = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), form=_ctrl_rows)
-    if step == 1 and hrows == 1 and prows == 1:
-        _check(lib().sig_osc_bank(OSC_KINDS[kind], position, rate, rows, voices, hp, hs, pp, ps,
-                                  out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank')
+    head, ((hp, hs, hrs), (pp, ps, prs)), tail = _osc_launch(out, position, step, rate, rows_per_param, (hertz, 'hertz'), (phase, 'phase'))
+    if step == 1 and head[5] == 0:                      # one parameter row, consecutive frames
+        _check(lib().sig_osc_bank(OSC_KINDS[kind], position, rate, *head[3:5], hp, hs, pp, ps, *tail), 'sig_osc_bank')
         return out
-    rows_per_param = _parameter_rows(rows, rows_per_param, (hrows, 'hertz'), (prows, 'phase'))
-    _check(lib().sig_osc_bank_mod(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
-                                  hp, hs, hrs, pp, ps, prs, out.data_ptr(), _dt(out), out.stride(0), _stream(out)),
-           'sig_osc_bank_mod')
+    _check(lib().sig_osc_bank_mod(OSC_KINDS[kind], *head, hp, hs, hrs, pp, ps, prs, *tail), 'sig_osc_bank_mod')
     return out
 
 
@@ -375,11 +381,9 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
                 rows_per_param: int = 0) -> torch.Tensor:
     """out[(rows, voices)] <- phase-modulation oscillator `kind` (sig_osc_bank_pm): t = (n / rate * hertz + phase) + index * mod.
     hertz / phase / index: (1|P, V|1) f64 like `osc_bank`; mod: float32 | float64 (rows|1, V|1), row n modulates output row n."""
-    _gpu(hertz, phase, index, mod, out)
-    _audio(out, 'osc out')
+    head, (h, p, i), tail = _osc_launch(out, position, step, rate, rows_per_param, (hertz, 'hertz'), (phase, 'phase'), (index, 'index'),
+                                        also=(mod,))
     rows, voices = out.shape
-    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (index, 'index'), form=_ctrl_rows)
-    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'index'))
     mp, mdt, mld, mcs = None, F32, 0, 0
     if mod is not None:
         _audio(mod, 'modulator')
@@ -387,9 +391,7 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
             raise NativeError(f'modulator {tuple(mod.shape)} does not broadcast to {(rows, voices)}')
         mp, mdt = mod.data_ptr(), _dt(mod)
         mld, mcs = (0 if mod.shape[0] == 1 else mod.stride(0)), (0 if mod.shape[1] == 1 else 1)
-    _check(lib().sig_osc_bank_pm(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
-                                 *params[0:3], *params[4:7], *params[8:11], mp, mdt, mld, mcs,
-                                 out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_pm')
+    _check(lib().sig_osc_bank_pm(OSC_KINDS[kind], *head, *h, *p, *i, mp, mdt, mld, mcs, *tail), 'sig_osc_bank_pm')
     return out
 
 
@@ -408,14 +410,9 @@ def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.T
                    table: torch.Tensor, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
     """out[(rows, voices)] <- wavetable oscillator (sig_osc_bank_table): the (T, W) float32 `table` read with linear interpolation at
     np.mod(n / rate * hertz + phase, 1) * T, column clip(floor(select), 0, W - 1).  hertz / phase / select: (1|P, V|1) f64 like `osc_bank`."""
-    _gpu(hertz, phase, select, table, out)
-    _audio(out, 'osc out')
-    rows, voices = out.shape
-    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (select, 'select'), form=_ctrl_rows)
-    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'select'))
-    _check(lib().sig_osc_bank_table(position, step, rate, rows, voices, rows_per_param,
-                                    *params[0:3], *params[4:7], *params[8:11], *_table(table),
-                                    out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_table')
+    head, (h, p, s), tail = _osc_launch(out, position, step, rate, rows_per_param, (hertz, 'hertz'), (phase, 'phase'), (select, 'select'),
+                                        also=(table,))
+    _check(lib().sig_osc_bank_table(*head, *h, *p, *s, *_table(table), *tail), 'sig_osc_bank_table')
     return out
 
 
@@ -429,17 +426,10 @@ def _copies(copies) -> tuple:
     return U, (ctypes.c_double * U)(*c[:, 0].tolist()), (ctypes.c_double * U)(*c[:, 1].tolist())
 
 
-def _osc_bank_copies(entry: str, kind: str, position: int, rate: int, hertz, phase, spread, copies, out, step: int, rows_per_param: int):
-    """the one call of sig_osc_bank_unison and sig_osc_bank_blep: the same arguments, the same marshalling"""
-    _gpu(hertz, phase, spread, out)
-    _audio(out, 'osc out')
-    rows, voices = out.shape
-    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'), form=_ctrl_rows)
-    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'spread'))
-    U, detune, offsets = _copies(copies)
-    _check(getattr(lib(), entry)(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
-                                 *params[0:3], *params[4:7], *params[8:11], U, detune, offsets,
-                                 out.data_ptr(), _dt(out), out.stride(0), _stream(out)), entry)
+def _osc_bank_copies(entry: str, kind: str, position: int, rate: int, copies, out, step: int, rows_per_param: int, *named):
+    """the one call of sig_osc_bank_unison, sig_osc_bank_blep and sig_osc_bank_sync: the parameter rows, then the copies"""
+    head, rows, tail = _osc_launch(out, position, step, rate, rows_per_param, *named)
+    _check(getattr(lib(), entry)(OSC_KINDS[kind], *head, *(x for row in rows for x in row), *_copies(copies), *tail), entry)
     return out
 
 
@@ -448,7 +438,8 @@ def osc_bank_unison(kind: str, position: int, rate: int, hertz: torch.Tensor, ph
     """out[(rows, voices)] <- unison oscillator `kind` (sig_osc_bank_unison): the mean over the U rows (d, p) of `copies` (a host
     (U, 2) array, by value) of wave(n / rate * (hertz * (1 + spread * d)) + (phase + p)).  hertz / phase / spread: (1|P, V|1) f64 like
     `osc_bank`; spread None: unplugged = 0."""
-    return _osc_bank_copies('sig_osc_bank_unison', kind, position, rate, hertz, phase, spread, copies, out, step, rows_per_param)
+    return _osc_bank_copies('sig_osc_bank_unison', kind, position, rate, copies, out, step, rows_per_param,
+                            (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'))
 
 
 def osc_bank_blep(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, spread: torch.Tensor | None,
@@ -456,7 +447,8 @@ def osc_bank_blep(kind: str, position: int, rate: int, hertz: torch.Tensor, phas
     """out[(rows, voices)] <- band-limited oscillator `kind` ('Square' | 'Sawtooth' | 'Triangle'; sig_osc_bank_blep): `osc_bank_unison`
     with each copy's waveform corrected by a two-sample polynomial step around its edges (ext.py BlepOsc), the window d =
     min(|hertz * (1 + spread * d_u)| / rate, 0.5) per copy.  Same arguments."""
-    return _osc_bank_copies('sig_osc_bank_blep', kind, position, rate, hertz, phase, spread, copies, out, step, rows_per_param)
+    return _osc_bank_copies('sig_osc_bank_blep', kind, position, rate, copies, out, step, rows_per_param,
+                            (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'))
 
 
 def osc_bank_sync(kind: str, position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, spread: torch.Tensor | None,
@@ -464,17 +456,8 @@ def osc_bank_sync(kind: str, position: int, rate: int, hertz: torch.Tensor, phas
     """out[(rows, voices)] <- hard-sync oscillator `kind` ('Sawtooth' | 'Square'; sig_osc_bank_sync): `osc_bank_blep` with a slave
     oscillator at max(ratio, 1) times the pitch, reset at every cycle of the master (ext.py SyncOsc).  ratio: (1|P, V|1) f64 like
     spread; None: unplugged = 0, the band-limited oscillator."""
-    _gpu(hertz, phase, spread, ratio, out)
-    _audio(out, 'osc out')
-    rows, voices = out.shape
-    params = _voice_rows(voices, (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'), (ratio, 'ratio'), form=_ctrl_rows)
-    rows_per_param = _parameter_rows(rows, rows_per_param, (params[3], 'hertz'), (params[7], 'phase'), (params[11], 'spread'),
-                                     (params[15], 'ratio'))
-    U, detune, offsets = _copies(copies)
-    _check(lib().sig_osc_bank_sync(OSC_KINDS[kind], position, step, rate, rows, voices, rows_per_param,
-                                   *params[0:3], *params[4:7], *params[8:11], *params[12:15], U, detune, offsets,
-                                   out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_osc_bank_sync')
-    return out
+    return _osc_bank_copies('sig_osc_bank_sync', kind, position, rate, copies, out, step, rows_per_param,
+                            (hertz, 'hertz'), (phase, 'phase'), (spread, 'spread'), (ratio, 'ratio'))
 
 
 def shaper_table(x: torch.Tensor, select: torch.Tensor | None, table: torch.Tensor, out: torch.Tensor,

@@ -8,6 +8,8 @@
 // v_readlane, so the per-sample cost is mul + add + waveform.
 //
 // Roofline: 4 B written per voice-sample (f32), no reads beyond 2 x 8 B per voice per wave.
+#include <type_traits>
+
 #include "sig_osc.h"
 #include "sig_table.h"
 
@@ -27,20 +29,34 @@ struct OscArgs {
     const double* hertz; int hs; int64_t hrs; const double* phase; int ps; int64_t prs; int rpp;
 };
 
-template <int KIND, int VEC, typename OUT>
-__global__ __launch_bounds__(256) void osc_bank_kernel(OscArgs a, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+// A thread's place in the mapping above: lane, first voice, first row.  1-D grid: consecutive workgroups cover adjacent voice
+// tiles of the same rows; a workgroup owns `waves` consecutive 16-row tiles, its wave w the w-th.  (The wavetable kernel, whose
+// waves walk several row groups, keeps its own form of these lines: through this helper it compiled to other registers.)
+struct Tile { int lane, v0; int64_t r0; };
+
+template <int VEC>
+__device__ __forceinline__ Tile tile_of(int voice_tiles, int waves)
 {
-    // 1-D grid: consecutive workgroups cover adjacent voice tiles of the same 64 rows
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int vt = blockIdx.x % voice_tiles;
     const int64_t rt = blockIdx.x / voice_tiles;
-    const int v0 = (vt * SIG_WAVE + lane) * VEC;
-    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    return {lane, (vt * SIG_WAVE + lane) * VEC, (rt * waves + wave) * kRowsPerWave};
+}
+
+// osc.py:32  frame_range / rate : int64 -> f64, IEEE divide, one per row: lane l holds the quotient of row r0 + (l & 15)
+__device__ __forceinline__ double row_quotients(const OscArgs& a, int64_t r0, int lane)
+{
+    return (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+}
+
+template <int KIND, int VEC, typename OUT>
+__global__ __launch_bounds__(256) void osc_bank_kernel(OscArgs a, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    const auto [lane, v0, r0] = tile_of<VEC>(voice_tiles, kWavesPerWg);
     if (r0 >= a.rows) return;                                      // wave-uniform
 
-    // osc.py:32  frame_range / rate : int64 -> f64, IEEE divide, one per row
-    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const double q_lane = row_quotients(a, r0, lane);
 
     double hz[VEC], ph[VEC];
     int64_t loaded = -1;                                           // parameter row currently in registers
@@ -80,46 +96,8 @@ __global__ __launch_bounds__(256) void osc_bank_kernel(OscArgs a, OUT* __restric
     }
 }
 
-template <int KIND, typename OUT>
-int launch_osc(const OscArgs& a, OUT* out, int64_t ld, hipStream_t stream)
-{
-    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
-    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t nwg = row_tiles * voice_tiles;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    if (vec4)
-        osc_bank_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, out, ld, voice_tiles);
-    else
-        osc_bank_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, out, ld, voice_tiles);
-    return sig_launch_status();
-}
-
-template <typename OUT>
-int dispatch_kind(int kind, const OscArgs& a, OUT* out, int64_t ld, hipStream_t stream)
-{
-    switch (kind) {
-        case SIG_OSC_SINE: return launch_osc<SIG_OSC_SINE, OUT>(a, out, ld, stream);
-        case SIG_OSC_SQUARE: return launch_osc<SIG_OSC_SQUARE, OUT>(a, out, ld, stream);
-        case SIG_OSC_SAWTOOTH: return launch_osc<SIG_OSC_SAWTOOTH, OUT>(a, out, ld, stream);
-        case SIG_OSC_TRIANGLE: return launch_osc<SIG_OSC_TRIANGLE, OUT>(a, out, ld, stream);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-int run_osc(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t out_ld, void* stream)
-{
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return dispatch_kind<float>(kind, a, static_cast<float*>(out), out_ld, s);
-    if (out_dtype == SIG_F64) return dispatch_kind<double>(kind, a, static_cast<double*>(out), out_ld, s);
-    return (int)hipErrorInvalidValue;
-}
-
 // ---- phase modulation: t = (n / rate * hertz + phase) + index * mod[n, v], the modulator a frame-rate buffer.
-// Same mapping as osc_bank_kernel (a wave = 64 * VEC voices x 16 rows, n / rate once per row), plus one read per
+// Same mapping as osc_bank_kernel (tile_of), plus one read per
 // voice-sample: with VEC == 4 and MVEC a lane loads its four float32 modulator samples as one 16-byte access, like its store.
 // Roofline: 4 B read + 4 B written per voice-sample (f32 modulator and store).
 struct PmArgs {
@@ -130,15 +108,10 @@ struct PmArgs {
 template <int KIND, int VEC, typename OUT, typename MOD, bool MVEC>
 __global__ __launch_bounds__(256) void osc_bank_pm_kernel(OscArgs a, PmArgs m, OUT* __restrict__ out, int64_t ld, int voice_tiles)
 {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int vt = blockIdx.x % voice_tiles;
-    const int64_t rt = blockIdx.x / voice_tiles;
-    const int v0 = (vt * SIG_WAVE + lane) * VEC;
-    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    const auto [lane, v0, r0] = tile_of<VEC>(voice_tiles, kWavesPerWg);
     if (r0 >= a.rows) return;                                      // wave-uniform
 
-    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const double q_lane = row_quotients(a, r0, lane);
     const MOD* __restrict__ mod = static_cast<const MOD*>(m.mod);
 
     double hz[VEC], ph[VEC], ix[VEC];
@@ -192,52 +165,6 @@ __global__ __launch_bounds__(256) void osc_bank_pm_kernel(OscArgs a, PmArgs m, O
     }
 }
 
-template <int KIND, typename OUT, typename MOD>
-int launch_pm(const OscArgs& a, const PmArgs& m, OUT* out, int64_t ld, hipStream_t stream)
-{
-    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const bool mvec = vec4 && sizeof(MOD) == 4 && m.mod && m.mcs == 1 && m.mld > 0 && m.mld % 4 == 0 &&
-                      (reinterpret_cast<uintptr_t>(m.mod) % 16) == 0;
-    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
-    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t nwg = row_tiles * voice_tiles;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    if constexpr (sizeof(MOD) == 4) {                              // (the 16-byte modulator load exists for float32 only)
-        if (mvec) {
-            osc_bank_pm_kernel<KIND, 4, OUT, MOD, true><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
-            return sig_launch_status();
-        }
-    }
-    if (vec4)
-        osc_bank_pm_kernel<KIND, 4, OUT, MOD, false><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
-    else
-        osc_bank_pm_kernel<KIND, 1, OUT, MOD, false><<<(unsigned)nwg, 256, 0, stream>>>(a, m, out, ld, voice_tiles);
-    return sig_launch_status();
-}
-
-template <typename OUT, typename MOD>
-int dispatch_pm_kind(int kind, const OscArgs& a, const PmArgs& m, OUT* out, int64_t ld, hipStream_t stream)
-{
-    switch (kind) {
-        case SIG_OSC_SINE: return launch_pm<SIG_OSC_SINE, OUT, MOD>(a, m, out, ld, stream);
-        case SIG_OSC_SQUARE: return launch_pm<SIG_OSC_SQUARE, OUT, MOD>(a, m, out, ld, stream);
-        case SIG_OSC_SAWTOOTH: return launch_pm<SIG_OSC_SAWTOOTH, OUT, MOD>(a, m, out, ld, stream);
-        case SIG_OSC_TRIANGLE: return launch_pm<SIG_OSC_TRIANGLE, OUT, MOD>(a, m, out, ld, stream);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
-template <typename MOD>
-int run_pm(int kind, const OscArgs& a, const PmArgs& m, void* out, int32_t out_dtype, int64_t out_ld, hipStream_t s)
-{
-    if (out_dtype == SIG_F32) return dispatch_pm_kind<float, MOD>(kind, a, m, static_cast<float*>(out), out_ld, s);
-    if (out_dtype == SIG_F64) return dispatch_pm_kind<double, MOD>(kind, a, m, static_cast<double*>(out), out_ld, s);
-    return (int)hipErrorInvalidValue;
-}
-
 // ---- wavetable: out = lerp of a (T, W) float32 table (W single-cycle waveforms of T points, T a power of two) at
 // m = np.mod(n / rate * hertz + phase, 1), column w = clip(floor(select), 0, W - 1) per voice (chain/ext.py Wavetable).
 // A 512-thread workgroup stages the whole table in LDS once -- column-major, T + 1 floats per column, the guard entry
@@ -279,7 +206,7 @@ __global__ __launch_bounds__(64 * kTableWaves) void osc_bank_table_kernel(OscArg
     for (int g = 0; g < tb.groups; ++g) {
         const int64_t r0 = ((rt * tb.groups + g) * kTableWaves + wave) * kRowsPerWave;
         if (r0 >= a.rows) break;                                   // wave-uniform
-        const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+        const double q_lane = row_quotients(a, r0, lane);
         for (int j = 0; j < kRowsPerWave; ++j) {
             const int64_t row = r0 + j;
             if (row >= a.rows) break;                              // wave-uniform
@@ -324,28 +251,6 @@ __global__ __launch_bounds__(64 * kTableWaves) void osc_bank_table_kernel(OscArg
     }
 }
 
-template <typename OUT>
-int launch_table(const OscArgs& a, TableArgs tb, OUT* out, int64_t ld, hipStream_t stream)
-{
-    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t rows_per_pass = (int64_t)kRowsPerWave * kTableWaves;
-    const int64_t passes = (a.rows + rows_per_pass - 1) / rows_per_pass;
-    // as many row groups per wave as still leave two workgroups for every CU of an MI355X (the staging is paid per workgroup)
-    tb.groups = 8;
-    while (tb.groups > 1 && ((passes + tb.groups - 1) / tb.groups) * voice_tiles < 512) tb.groups >>= 1;
-    const int64_t nwg = ((passes + tb.groups - 1) / tb.groups) * voice_tiles;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    const size_t lds = sig_table::lds_bytes(tb.T, tb.W);
-    if (vec4)
-        osc_bank_table_kernel<4, OUT><<<(unsigned)nwg, 64 * kTableWaves, lds, stream>>>(a, tb, out, ld, voice_tiles);
-    else
-        osc_bank_table_kernel<1, OUT><<<(unsigned)nwg, 64 * kTableWaves, lds, stream>>>(a, tb, out, ld, voice_tiles);
-    return sig_launch_status();
-}
-
 // ---- unison: the mean of `copies` detuned copies of one waveform per voice (chain/ext.py UnisonOsc),
 //   r_u = 1 + spread * d[u];  h_u = hertz * r_u;  q_u = phase + p[u];  t_u = n / rate * h_u + q_u;  out = (sum_u w(t_u)) / copies
 // every operation rounded in that order, the sum in u ascending.  Same mapping as osc_bank_kernel (a wave = 64 * VEC voices x 16
@@ -367,15 +272,10 @@ template <int KIND, typename OUT> __device__ __forceinline__ double unison_wave(
 template <int KIND, int VEC, typename OUT>
 __global__ __launch_bounds__(256) void osc_bank_unison_kernel(OscArgs a, UniArgs un, OUT* __restrict__ out, int64_t ld, int voice_tiles)
 {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int vt = blockIdx.x % voice_tiles;
-    const int64_t rt = blockIdx.x / voice_tiles;
-    const int v0 = (vt * SIG_WAVE + lane) * VEC;
-    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    const auto [lane, v0, r0] = tile_of<VEC>(voice_tiles, kWavesPerWg);
     if (r0 >= a.rows) return;                                      // wave-uniform
 
-    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const double q_lane = row_quotients(a, r0, lane);
     const int copies = un.copies;                                  // 1 .. SIG_UNISON_MAX_COPIES (checked by the entry)
     const double count = (double)copies;
 
@@ -428,36 +328,6 @@ __global__ __launch_bounds__(256) void osc_bank_unison_kernel(OscArgs a, UniArgs
     }
 }
 
-template <int KIND, typename OUT>
-int launch_unison(const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
-{
-    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
-    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t nwg = row_tiles * voice_tiles;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    if (vec4)
-        osc_bank_unison_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
-    else
-        osc_bank_unison_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
-    return sig_launch_status();
-}
-
-template <typename OUT>
-int dispatch_unison_kind(int kind, const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
-{
-    switch (kind) {
-        case SIG_OSC_SINE: return launch_unison<SIG_OSC_SINE, OUT>(a, un, out, ld, stream);
-        case SIG_OSC_SQUARE: return launch_unison<SIG_OSC_SQUARE, OUT>(a, un, out, ld, stream);
-        case SIG_OSC_SAWTOOTH: return launch_unison<SIG_OSC_SAWTOOTH, OUT>(a, un, out, ld, stream);
-        case SIG_OSC_TRIANGLE: return launch_unison<SIG_OSC_TRIANGLE, OUT>(a, un, out, ld, stream);
-    }
-    return (int)hipErrorInvalidValue;
-}
-
 // ---- band-limited unison (chain/ext.py BlepOsc): osc_bank_unison_kernel's expression and tiling with sig_osc::osc_blep as the
 // waveform, which wants d = min(|h_u| / rate, 0.5) and 1 / d per copy and voice: two IEEE divides that must not be paid per sample.
 // So the loops are turned round: the tile's rows are cut where the parameter row changes (once, for the whole tile, unless a block
@@ -469,16 +339,11 @@ int dispatch_unison_kind(int kind, const OscArgs& a, const UniArgs& un, OUT* out
 template <int KIND, int VEC, typename OUT>
 __global__ __launch_bounds__(256) void osc_bank_blep_kernel(OscArgs a, UniArgs un, OUT* __restrict__ out, int64_t ld, int voice_tiles)
 {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int vt = blockIdx.x % voice_tiles;
-    const int64_t rt = blockIdx.x / voice_tiles;
-    const int v0 = (vt * SIG_WAVE + lane) * VEC;
-    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    const auto [lane, v0, r0] = tile_of<VEC>(voice_tiles, kWavesPerWg);
     if (r0 >= a.rows) return;                                      // wave-uniform
     const int nrows = (int)((a.rows - r0 < (int64_t)kRowsPerWave) ? a.rows - r0 : (int64_t)kRowsPerWave);
 
-    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const double q_lane = row_quotients(a, r0, lane);
     const int copies = un.copies;                                  // 1 .. SIG_UNISON_MAX_COPIES (checked by the entry)
 
     double s[kRowsPerWave][VEC];
@@ -545,35 +410,6 @@ __global__ __launch_bounds__(256) void osc_bank_blep_kernel(OscArgs a, UniArgs u
     }
 }
 
-template <int KIND, typename OUT>
-int launch_blep(const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
-{
-    const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
-    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t nwg = row_tiles * voice_tiles;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    if (vec4)
-        osc_bank_blep_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
-    else
-        osc_bank_blep_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, out, ld, voice_tiles);
-    return sig_launch_status();
-}
-
-template <typename OUT>
-int dispatch_blep_kind(int kind, const OscArgs& a, const UniArgs& un, OUT* out, int64_t ld, hipStream_t stream)
-{
-    switch (kind) {
-        case SIG_OSC_SQUARE: return launch_blep<SIG_OSC_SQUARE, OUT>(a, un, out, ld, stream);
-        case SIG_OSC_SAWTOOTH: return launch_blep<SIG_OSC_SAWTOOTH, OUT>(a, un, out, ld, stream);
-        case SIG_OSC_TRIANGLE: return launch_blep<SIG_OSC_TRIANGLE, OUT>(a, un, out, ld, stream);
-    }
-    return (int)hipErrorInvalidValue;                              // (Sine: it has no edge to correct)
-}
-
 // ---- hard sync (chain/ext.py SyncOsc): osc_bank_blep_kernel's tiling, pieces and loops with sig_osc::osc_sync as the waveform and
 // one more parameter row, the ratio.  Block-invariant and hoisted like d and 1 / d: per voice and piece R, g and the reset's weight
 // (sig_osc::sync_ratio), per copy, voice and piece ds and 1 / ds -- a third IEEE divide there, none per sample.  Every lane evaluates every
@@ -583,16 +419,11 @@ struct SyncArgs { const double* ratio; int rs; int64_t rrs; };      // (1|P, V|1
 template <int KIND, int VEC, typename OUT>
 __global__ __launch_bounds__(256) void osc_bank_sync_kernel(OscArgs a, UniArgs un, SyncArgs sy, OUT* __restrict__ out, int64_t ld, int voice_tiles)
 {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int vt = blockIdx.x % voice_tiles;
-    const int64_t rt = blockIdx.x / voice_tiles;
-    const int v0 = (vt * SIG_WAVE + lane) * VEC;
-    const int64_t r0 = (rt * kWavesPerWg + wave) * kRowsPerWave;
+    const auto [lane, v0, r0] = tile_of<VEC>(voice_tiles, kWavesPerWg);
     if (r0 >= a.rows) return;                                      // wave-uniform
     const int nrows = (int)((a.rows - r0 < (int64_t)kRowsPerWave) ? a.rows - r0 : (int64_t)kRowsPerWave);
 
-    const double q_lane = (double)(a.position + (r0 + (lane & (kRowsPerWave - 1))) * a.step) / a.rate;
+    const double q_lane = row_quotients(a, r0, lane);
     const int copies = un.copies;                                  // 1 .. SIG_UNISON_MAX_COPIES (checked by the entry)
 
     double s[kRowsPerWave][VEC];
@@ -662,33 +493,156 @@ __global__ __launch_bounds__(256) void osc_bank_sync_kernel(OscArgs a, UniArgs u
     }
 }
 
-template <int KIND, typename OUT>
-int launch_sync(const OscArgs& a, const UniArgs& un, const SyncArgs& sy, OUT* out, int64_t ld, hipStream_t stream)
+// ---- host: the launch geometry, the kind and store-type dispatch, the entries' common arguments
+
+template <int N> using Const = std::integral_constant<int, N>;
+
+// Voices per lane and voice tiles of a launch: four voices and one 16-byte store per lane where every row of `out` allows it
+struct VoiceTiling { bool vec4; int voice_tiles; };
+
+template <typename OUT>
+VoiceTiling voice_tiling(const OscArgs& a, const OUT* out, int64_t ld)
 {
     const bool vec4 = (a.voices % 4 == 0) && (ld % 4 == 0) &&
                       ((reinterpret_cast<uintptr_t>(out) % (4 * sizeof(OUT))) == 0);
-    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
-    const int64_t row_tiles = (a.rows + rows_per_wg - 1) / rows_per_wg;
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (a.voices + span - 1) / span;
-    const int64_t nwg = row_tiles * voice_tiles;
+    return {vec4, sig_voice_tiles(a.voices, vec4 ? 4 : 1)};
+}
+
+// launch(Const<VEC>, workgroups, voice_tiles) over `row_tiles` workgroup rows; refuses more workgroups than a grid dimension holds
+template <typename LAUNCH>
+int launch_tiles(const VoiceTiling& vt, int64_t row_tiles, LAUNCH&& launch)
+{
+    const int64_t nwg = row_tiles * vt.voice_tiles;
     if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-    if (vec4)
-        osc_bank_sync_kernel<KIND, 4, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, sy, out, ld, voice_tiles);
+    if (vt.vec4)
+        launch(Const<4>{}, (unsigned)nwg, vt.voice_tiles);
     else
-        osc_bank_sync_kernel<KIND, 1, OUT><<<(unsigned)nwg, 256, 0, stream>>>(a, un, sy, out, ld, voice_tiles);
+        launch(Const<1>{}, (unsigned)nwg, vt.voice_tiles);
     return sig_launch_status();
 }
 
-template <typename OUT>
-int dispatch_sync_kind(int kind, const OscArgs& a, const UniArgs& un, const SyncArgs& sy, OUT* out, int64_t ld, hipStream_t stream)
+// the same for the kernels whose workgroup is kWavesPerWg waves of kRowsPerWave rows
+template <typename OUT, typename LAUNCH>
+int launch_bank(const OscArgs& a, OUT* out, int64_t ld, LAUNCH&& launch)
 {
-    switch (kind) {
-        case SIG_OSC_SQUARE: return launch_sync<SIG_OSC_SQUARE, OUT>(a, un, sy, out, ld, stream);
-        case SIG_OSC_SAWTOOTH: return launch_sync<SIG_OSC_SAWTOOTH, OUT>(a, un, sy, out, ld, stream);
-    }
-    return (int)hipErrorInvalidValue;                              // (Sine, Triangle: their reset changes the slope too)
+    const int64_t rows_per_wg = (int64_t)kRowsPerWave * kWavesPerWg;
+    return launch_tiles(voice_tiling(a, out, ld), (a.rows + rows_per_wg - 1) / rows_per_wg, launch);
 }
+
+// f(Const<KIND>) for a `kind` among KINDS..., hipErrorInvalidValue without a call for any other
+template <int... KINDS, typename F>
+int dispatch_kind(int kind, F&& f)
+{
+    constexpr unsigned allowed = ((1u << KINDS) | ...);
+    switch (kind) {
+#define SIG_KIND_CASE(K) case K: if constexpr ((allowed >> K) & 1u) return f(Const<K>{}); break;
+        SIG_KIND_CASE(SIG_OSC_SINE)
+        SIG_KIND_CASE(SIG_OSC_SQUARE)
+        SIG_KIND_CASE(SIG_OSC_SAWTOOTH)
+        SIG_KIND_CASE(SIG_OSC_TRIANGLE)
+#undef SIG_KIND_CASE
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// f(out as float* | double*), hipErrorInvalidValue without a call for any other `out_dtype`
+template <typename F>
+int dispatch_out(void* out, int32_t out_dtype, F&& f)
+{
+    if (out_dtype == SIG_F32) return f(static_cast<float*>(out));
+    if (out_dtype == SIG_F64) return f(static_cast<double*>(out));
+    return (int)hipErrorInvalidValue;
+}
+
+int run_osc(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t ld, void* stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return dispatch_out(out, out_dtype, [&](auto* o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        return dispatch_kind<SIG_OSC_SINE, SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH, SIG_OSC_TRIANGLE>(kind, [&](auto k) {
+            return launch_bank(a, o, ld, [&](auto vec, unsigned nwg, int voice_tiles) {
+                osc_bank_kernel<decltype(k)::value, decltype(vec)::value, OUT><<<nwg, 256, 0, s>>>(a, o, ld, voice_tiles);
+            });
+        });
+    });
+}
+
+template <typename MOD>
+int run_pm(int kind, const OscArgs& a, const PmArgs& m, void* out, int32_t out_dtype, int64_t ld, hipStream_t s)
+{
+    return dispatch_out(out, out_dtype, [&](auto* o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        return dispatch_kind<SIG_OSC_SINE, SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH, SIG_OSC_TRIANGLE>(kind, [&](auto k) {
+            return launch_bank(a, o, ld, [&](auto vec, unsigned nwg, int voice_tiles) {
+                constexpr int KIND = decltype(k)::value, VEC = decltype(vec)::value;
+                if constexpr (VEC == 4 && sizeof(MOD) == 4) {      // (the 16-byte modulator load exists for float32 only)
+                    if (m.mod && m.mcs == 1 && m.mld > 0 && m.mld % 4 == 0 && (reinterpret_cast<uintptr_t>(m.mod) % 16) == 0) {
+                        osc_bank_pm_kernel<KIND, 4, OUT, MOD, true><<<nwg, 256, 0, s>>>(a, m, o, ld, voice_tiles);
+                        return;
+                    }
+                }
+                osc_bank_pm_kernel<KIND, VEC, OUT, MOD, false><<<nwg, 256, 0, s>>>(a, m, o, ld, voice_tiles);
+            });
+        });
+    });
+}
+
+int run_table(const OscArgs& a, TableArgs tb, void* out, int32_t out_dtype, int64_t ld, hipStream_t s)
+{
+    return dispatch_out(out, out_dtype, [&](auto* o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        const VoiceTiling vt = voice_tiling(a, o, ld);
+        const int64_t rows_per_pass = (int64_t)kRowsPerWave * kTableWaves;
+        const int64_t passes = (a.rows + rows_per_pass - 1) / rows_per_pass;
+        // as many row groups per wave as still leave two workgroups for every CU of an MI355X (the staging is paid per workgroup)
+        tb.groups = 8;
+        while (tb.groups > 1 && ((passes + tb.groups - 1) / tb.groups) * vt.voice_tiles < 512) tb.groups >>= 1;
+        const size_t lds = sig_table::lds_bytes(tb.T, tb.W);
+        return launch_tiles(vt, (passes + tb.groups - 1) / tb.groups, [&](auto vec, unsigned nwg, int voice_tiles) {
+            osc_bank_table_kernel<decltype(vec)::value, OUT><<<nwg, 64 * kTableWaves, lds, s>>>(a, tb, o, ld, voice_tiles);
+        });
+    });
+}
+
+// the three launches of (OscArgs, UniArgs[, SyncArgs]) kernels: LAUNCH(Const<KIND>, Const<VEC>, out, workgroups, voice_tiles)
+template <int... KINDS, typename LAUNCH>
+int run_copies(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t ld, LAUNCH&& launch)
+{
+    return dispatch_out(out, out_dtype, [&](auto* o) {
+        return dispatch_kind<KINDS...>(kind, [&](auto k) {
+            return launch_bank(a, o, ld, [&](auto vec, unsigned nwg, int voice_tiles) { launch(k, vec, o, nwg, voice_tiles); });
+        });
+    });
+}
+
+// One parameter's strides as every entry takes them
+bool row_strides_ok(int32_t stride, int64_t row_stride) { return (stride == 0 || stride == 1) && row_stride >= 0; }
+
+// The arguments common to the entries, checked, as OscArgs
+int osc_args(OscArgs& a, int64_t position, int64_t position_step, int32_t rate, int64_t rows, int32_t voices, int32_t rows_per_param,
+             const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+             const double* phase, int32_t phase_stride, int64_t phase_row_stride, const void* out, int64_t out_ld)
+{
+    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
+    SIG_CHECK_ARG(row_strides_ok(hertz_stride, hertz_row_stride) && row_strides_ok(phase_stride, phase_row_stride));
+    a = OscArgs{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
+                phase, phase_stride, phase_row_stride, rows_per_param};
+    return 0;
+}
+
+// The spread row and the copies of the unison entries, checked, as UniArgs
+int uni_args(UniArgs& un, const double* spread, int32_t spread_stride, int64_t spread_row_stride,
+             int32_t copies, const double* detune, const double* offsets)
+{
+    SIG_CHECK_ARG(row_strides_ok(spread_stride, spread_row_stride));
+    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    un = UniArgs{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
+    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
+    return 0;
+}
+
+#define SIG_TRY(call) do { const int status_ = (call); if (status_ != 0) return status_; } while (0)
 
 }  // namespace
 
@@ -701,23 +655,21 @@ extern "C" int sig_osc_bank_sync(int kind, int64_t position, int64_t position_st
                                  int32_t copies, const double* detune, const double* offsets,
                                  void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
+    OscArgs a;
+    UniArgs un;
     SIG_CHECK_ARG(kind == SIG_OSC_SQUARE || kind == SIG_OSC_SAWTOOTH);
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
-                  (spread_stride == 0 || spread_stride == 1) && (ratio_stride == 0 || ratio_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && spread_row_stride >= 0 && ratio_row_stride >= 0);
-    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_TRY(uni_args(un, spread, spread_stride, spread_row_stride, copies, detune, offsets));
+    SIG_CHECK_ARG(row_strides_ok(ratio_stride, ratio_row_stride));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
-    UniArgs un{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
-    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
     const SyncArgs sy{ratio, ratio_stride, ratio_row_stride};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return dispatch_sync_kind<float>(kind, a, un, sy, static_cast<float*>(out), out_ld, s);
-    return dispatch_sync_kind<double>(kind, a, un, sy, static_cast<double*>(out), out_ld, s);
+    return run_copies<SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH>(                       // (Sine, Triangle: their reset changes the slope too)
+        kind, a, out, out_dtype, out_ld, [&](auto k, auto vec, auto* o, unsigned nwg, int voice_tiles) {
+            osc_bank_sync_kernel<decltype(k)::value, decltype(vec)::value><<<nwg, 256, 0, s>>>(a, un, sy, o, out_ld, voice_tiles);
+        });
 }
 
 extern "C" int sig_osc_bank_blep(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -728,22 +680,19 @@ extern "C" int sig_osc_bank_blep(int kind, int64_t position, int64_t position_st
                                  int32_t copies, const double* detune, const double* offsets,
                                  void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
+    OscArgs a;
+    UniArgs un;
     SIG_CHECK_ARG(kind == SIG_OSC_SQUARE || kind == SIG_OSC_SAWTOOTH || kind == SIG_OSC_TRIANGLE);
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
-                  (spread_stride == 0 || spread_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && spread_row_stride >= 0);
-    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_TRY(uni_args(un, spread, spread_stride, spread_row_stride, copies, detune, offsets));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
-    UniArgs un{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
-    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return dispatch_blep_kind<float>(kind, a, un, static_cast<float*>(out), out_ld, s);
-    return dispatch_blep_kind<double>(kind, a, un, static_cast<double*>(out), out_ld, s);
+    return run_copies<SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH, SIG_OSC_TRIANGLE>(     // (Sine: it has no edge to correct)
+        kind, a, out, out_dtype, out_ld, [&](auto k, auto vec, auto* o, unsigned nwg, int voice_tiles) {
+            osc_bank_blep_kernel<decltype(k)::value, decltype(vec)::value><<<nwg, 256, 0, s>>>(a, un, o, out_ld, voice_tiles);
+        });
 }
 
 extern "C" int sig_osc_bank_unison(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -754,22 +703,19 @@ extern "C" int sig_osc_bank_unison(int kind, int64_t position, int64_t position_
                                    int32_t copies, const double* detune, const double* offsets,
                                    void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
+    OscArgs a;
+    UniArgs un;
     SIG_CHECK_ARG(kind >= SIG_OSC_SINE && kind <= SIG_OSC_TRIANGLE);
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
-                  (spread_stride == 0 || spread_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && spread_row_stride >= 0);
-    SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_TRY(uni_args(un, spread, spread_stride, spread_row_stride, copies, detune, offsets));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
-    UniArgs un{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
-    for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return dispatch_unison_kind<float>(kind, a, un, static_cast<float*>(out), out_ld, s);
-    return dispatch_unison_kind<double>(kind, a, un, static_cast<double*>(out), out_ld, s);
+    return run_copies<SIG_OSC_SINE, SIG_OSC_SQUARE, SIG_OSC_SAWTOOTH, SIG_OSC_TRIANGLE>(
+        kind, a, out, out_dtype, out_ld, [&](auto k, auto vec, auto* o, unsigned nwg, int voice_tiles) {
+            osc_bank_unison_kernel<decltype(k)::value, decltype(vec)::value><<<nwg, 256, 0, s>>>(a, un, o, out_ld, voice_tiles);
+        });
 }
 
 extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -780,21 +726,16 @@ extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32
                                   const float* table, int32_t table_points, int32_t table_waves,
                                   void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
-                  (select_stride == 0 || select_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && select_row_stride >= 0);
+    OscArgs a;
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_CHECK_ARG(row_strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(table != nullptr && table_points >= 2 && (table_points & (table_points - 1)) == 0 && table_waves >= 1 &&
                   (int64_t)table_points * table_waves <= SIG_TABLE_MAX_POINTS);
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
     const TableArgs tb{table, table_points, table_waves, select, select_stride, select_row_stride, 1};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return launch_table<float>(a, tb, static_cast<float*>(out), out_ld, s);
-    return launch_table<double>(a, tb, static_cast<double*>(out), out_ld, s);
+    return run_table(a, tb, out, out_dtype, out_ld, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -805,16 +746,13 @@ extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step
                                const void* mod, int32_t mod_dtype, int64_t mod_ld, int32_t mod_stride,
                                void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1) &&
-                  (index_stride == 0 || index_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0 && index_row_stride >= 0);
+    OscArgs a;
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_CHECK_ARG(row_strides_ok(index_stride, index_row_stride));
     SIG_CHECK_ARG(mod == nullptr || ((mod_dtype == SIG_F32 || mod_dtype == SIG_F64) && (mod_stride == 0 || mod_stride == 1) &&
                                      (mod_ld == 0 || mod_ld >= (mod_stride ? voices : 1))));
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
     const PmArgs m{index, index_stride, index_row_stride, mod, mod_ld, mod_stride};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (mod != nullptr && mod_dtype == SIG_F64) return run_pm<double>(kind, a, m, out, out_dtype, out_ld, s);
@@ -826,11 +764,9 @@ extern "C" int sig_osc_bank(int kind, int64_t position, int32_t rate, int64_t ro
                             const double* phase, int32_t phase_stride,
                             void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1));
+    OscArgs a;                                                     // one parameter row, consecutive frames
+    SIG_TRY(osc_args(a, position, 1, rate, rows, voices, 0, hertz, hertz_stride, 0, phase, phase_stride, 0, out, out_ld));
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, 1, (double)rate, rows, voices, hertz, hertz_stride, 0, phase, phase_stride, 0, 0};
     return run_osc(kind, a, out, out_dtype, out_ld, stream);
 }
 
@@ -840,13 +776,10 @@ extern "C" int sig_osc_bank_mod(int kind, int64_t position, int64_t position_ste
                                 const double* phase, int32_t phase_stride, int64_t phase_row_stride,
                                 void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
-    SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG((hertz_stride == 0 || hertz_stride == 1) && (phase_stride == 0 || phase_stride == 1));
-    SIG_CHECK_ARG(hertz_row_stride >= 0 && phase_row_stride >= 0);
+    OscArgs a;
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
     if (rows == 0 || voices == 0) return 0;
-    const OscArgs a{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
-                    phase, phase_stride, phase_row_stride, rows_per_param};
     return run_osc(kind, a, out, out_dtype, out_ld, stream);
 }
 

@@ -896,17 +896,14 @@ class _Batch:
         hertz, phase, spread = (self._control(p, p.name) for p in (node.hertz, node.phase, node.spread))
         copies = node.host_copies()
         if isinstance(node, ext.SyncOsc):
-            ratio = self._control(node.ratio, 'ratio')
-
-            def sync_bank(kind, position, rate, hertz, phase, spread, ratio, out, **kw):
-                return _native.osc_bank_sync(kind, position, rate, hertz, phase, spread, ratio, copies, out, **kw)
-            return self._osc_launch(node, 'osc_bank_sync', sync_bank, (hertz, phase, spread, ratio), hist, rows)
-        label = 'osc_bank_blep' if node.bandlimited() else 'osc_bank_unison'
+            label, operands = 'osc_bank_sync', (hertz, phase, spread, self._control(node.ratio, 'ratio'))
+        else:
+            label, operands = 'osc_bank_blep' if node.bandlimited() else 'osc_bank_unison', (hertz, phase, spread)
         entry = getattr(_native, label)
 
-        def bank(kind, position, rate, hertz, phase, spread, out, **kw):
-            return entry(kind, position, rate, hertz, phase, spread, copies, out, **kw)
-        return self._osc_launch(node, label, bank, (hertz, phase, spread), hist, rows)
+        def bank(kind, position, rate, *rows_and_out, **kw):       # the copies go between the parameter rows and `out`
+            return entry(kind, position, rate, *rows_and_out[:-1], copies, rows_and_out[-1], **kw)
+        return self._osc_launch(node, label, bank, operands, hist, rows)
 
     def _sched_shaper(self, node, channels, hist, rows):
         """a waveshaper: one sig_shaper_table launch over its input's rows (history rows included when a filter reads it), scheduled
