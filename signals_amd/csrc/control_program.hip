@@ -390,7 +390,7 @@ extern "C" int sig_control_program_windowed(int32_t rate, int64_t position, int3
 
 // ---- specialised builds of this file (see the top): attached at run time, launched through a handle.  The program itself is in
 // device memory, so the library cannot match it against the image: the caller keeps the handle with the program it built the
-// image from (signals_amd/engine.py: _ControlProgram).
+// image from (signals_amd/engine/control.py: _ControlProgram).
 namespace {
 struct CtlSpecial { hipModule_t mod; hipFunction_t fn; };
 std::vector<CtlSpecial>& ctl_specials() { static std::vector<CtlSpecial> v; return v; }

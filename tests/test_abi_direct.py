@@ -57,7 +57,7 @@ def test_c_program_matches_python_engine(blocks, position):
     r = BatchRenderer(bench.build_graph(lcg_params(1024), 0, 1024), 2, 48000)
     r.scan_max_chains = 0
     bus = r.render(position, 256, blocks).cpu().numpy().astype(np.float64)
-    # the engine hands the kernel its voices ordered by cutoff (engine.py: ordered_by_cutoff), the C program in the
+    # the engine hands the kernel its voices ordered by cutoff (engine/voice_chain.py: ordered_by_cutoff), the C program in the
     # order they were drawn: the same bus up to the rounding of the voice sum, i.e. one float32 ulp of a ~0.03 bus
     assert np.abs(bus[0] - np.array(c['first'], dtype=np.float64)).max() <= 4e-9
     assert np.abs(bus[-1] - np.array(c['last'], dtype=np.float64)).max() <= 4e-9

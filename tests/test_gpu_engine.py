@@ -699,12 +699,12 @@ def test_closed_form_constants_are_kept_across_batches_and_follow_parameter_edit
     assert maxerr(r.render(0, N, K).cpu().numpy(), fresh(0)) == 0.0                 # first block has no context: T0 != T
     assert maxerr(r.render(N * K, N, K).cpu().numpy(), fresh(N * K)) == 0.0         # constants re-derived (c0 changed) ...
     assert r._steady_consts is not None
-    key = r._steady_consts[0]
+    key = r._steady_consts.key
     assert maxerr(r.render(2 * N * K, N, K).cpu().numpy(), fresh(2 * N * K)) == 0.0 # ... then reused
-    assert r._steady_consts[0] == key
+    assert r._steady_consts.key == key
     f.cutoff.sig.get_state().value[0, :] *= 0.5                                      # in-place edit of the cutoff array
     assert maxerr(r.render(3 * N * K, N, K).cpu().numpy(), fresh(3 * N * K, scale_cut=0.5)) == 0.0
-    assert r._steady_consts[0] != key
+    assert r._steady_consts.key != key
     f.input.sig.hertz = fix(g['c2/hertz'] * 2.0)                                     # another Fixed plugged in
     assert maxerr(r.render(4 * N * K, N, K).cpu().numpy(), fresh(4 * N * K, scale_hz=2.0, scale_cut=0.5)) == 0.0
 
@@ -1129,5 +1129,5 @@ def test_pipelined_batches_over_alternating_streams_equal_the_plain_render(pipel
     torch.cuda.synchronize()
     for i, (got, want) in enumerate(held):
         assert torch.equal(got, want), i
-    assert piped._pipe is not None and len(piped._pipe['streams']) == pipeline
+    assert piped._pipe is not None and len(piped._pipe.streams) == pipeline
     assert set(timer.summary()) == {'fused_voice_bus[Sine,lp,gain]'}

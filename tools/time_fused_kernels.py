@@ -39,7 +39,7 @@ def timed(f, label, units, warm=20, n=60):
 
 
 def ordered(cut, V, vpt):
-    """engine.py: ordered_by_cutoff"""
+    """engine/voice_chain.py: ordered_by_cutoff"""
     order = np.argsort(cut, kind='stable'); tile = 64 * vpt; tiles = V // tile
     perm = order.copy(); q = np.arange(tiles * tile); group, lane = q // 64, q % 64
     perm[((group % tiles) * 64 + lane) * vpt + group // tiles] = order[q]
