@@ -482,14 +482,30 @@ int sig_advance_position(int64_t* position_dev, int64_t delta, void* stream);
  *    float32 audio), and once more at p in float64; a cold-started Butterworth biquad (sig_biquad.h, transposed direct form
  *    II) steps over the h + 1 rows and its last output is the filter's register.  Window-rate operands other than window-rate
  *    registers must be block-invariant (ROW).  A one-column filter spreads its rows over the workgroup's threads (thread j
- *    evaluates row j); a wider one walks them per column. */
+ *    evaluates row j); a wider one walks them per column.
+ *
+ * Two more run only through sig_control_program_envelope (the same arguments again, a kernel variant of its own that also
+ * runs everything above, so the other two entries keep their kernels):
+ *  - SIG_CTL_ADSR: the ADSR envelope (sig_adsr) read at one frame: for the block evaluated at frame p (after the min_position
+ *    clamp; the front position likewise) its value is the envelope's level at t = (double)p / rate in float64 -- the operations of
+ *    sig_adsr with rows = 1 and a float64 output at that position, so the same bits.  Its six parameters are registers (block
+ *    rate: a ROW or any computed register, column v or column 0 of a one-column one): a, b, c = attack, decay, sustain here and
+ *  - SIG_CTL_ADSRARGS: a, b, c = release, gate_on, gate_off in a carrier instruction IMMEDIATELY IN FRONT of the SIG_CTL_ADSR
+ *    (an instruction has three operand registers).  The carrier computes nothing and nothing else reads its register; it has
+ *    the ADSR's `cols` and `reserved`.  `cols` = the broadcast of the six widths.  With `reserved` = 1 the pair is part of a
+ *    filter's window run (a smoothed envelope): evaluated per window row and rounded to float32 there like every window-rate
+ *    result; its parameters are then block-invariant rows.  A pair that is not formed like this (an ADSR without its carrier
+ *    in front, a carrier without its ADSR behind) is refused with hipErrorInvalidValue where the library can read the structure
+ *    -- sig_control_program_attach's description, which sig_control_program_attached then runs; a `program` in device memory
+ *    it cannot read, and there an ADSR without its carrier reads release = gate_on = gate_off = 0. */
 enum { SIG_CTL_ROW = 0, SIG_CTL_OSC = 1, SIG_CTL_GAIN = 2, SIG_CTL_MIX = 3, SIG_CTL_RINGMOD = 4, SIG_CTL_AMP = 5,
-       SIG_CTL_NOISE = 6, SIG_CTL_FILTER = 7 };
+       SIG_CTL_NOISE = 6, SIG_CTL_FILTER = 7, SIG_CTL_ADSRARGS = 8, SIG_CTL_ADSR = 9 };
 enum { SIG_CTL_MAX_REGS = 48, SIG_CTL_MAX_INS = 48 };
 typedef struct {
     int32_t op;              /* SIG_CTL_* */
     int32_t kind;            /* OSC: SIG_OSC_* */
-    int32_t a, b, c;         /* operand registers.  OSC: a = hertz, b = phase; GAIN / RINGMOD / AMP: a, b; MIX: a, b, c = mix */
+    int32_t a, b, c;         /* operand registers.  OSC: a = hertz, b = phase; GAIN / RINGMOD / AMP: a, b; MIX: a, b, c = mix;
+                                ADSR: attack, decay, sustain; ADSRARGS: release, gate_on, gate_off */
     int32_t dst;             /* result register */
     int32_t stride, rows;    /* ROW: a (rows, cols) float64 array, rows 1 | nblocks, rows contiguous, element v * stride (cols 1: stride 0) */
     int32_t cols;            /* EVERY instruction: columns of its result (1: evaluated once per block; the broadcast of its operands' widths otherwise) */
@@ -505,6 +521,11 @@ int sig_control_program(int32_t rate, int64_t position, int32_t step, int32_t nb
 /* sig_control_program for programs with SIG_CTL_NOISE / SIG_CTL_FILTER instructions (a kernel variant of its own, so the
  * programs without them keep their registers) */
 int sig_control_program_windowed(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position,
+                                 int64_t min_position,
+                                 const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream);
+/* sig_control_program_windowed for programs that also hold SIG_CTL_ADSRARGS / SIG_CTL_ADSR pairs (a third kernel variant, so the
+ * other two keep their code and registers) */
+int sig_control_program_envelope(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position,
                                  int64_t min_position,
                                  const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream);
 

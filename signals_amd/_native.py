@@ -46,8 +46,9 @@ class CtlOut(ctypes.Structure):
     _fields_ = [('reg', ctypes.c_int32), ('cols', ctypes.c_int32), ('out', ctypes.c_void_p), ('front', ctypes.c_void_p)]
 
 
-CTL_OPS = {'Row': 0, 'Osc': 1, 'Gain': 2, 'Mix': 3, 'RingMod': 4, 'Amp': 5, 'Noise': 6, 'Filter': 7}
+CTL_OPS = {'Row': 0, 'Osc': 1, 'Gain': 2, 'Mix': 3, 'RingMod': 4, 'Amp': 5, 'Noise': 6, 'Filter': 7, 'AdsrArgs': 8, 'Adsr': 9}
 CTL_WINDOWED_OPS = (6, 7)      # run only through sig_control_program_windowed
+CTL_ENVELOPE_OPS = (8, 9)      # the ADSR pair: run only through sig_control_program_envelope (which runs the windowed ones too)
 CTL_MAX_REGS, CTL_MAX_INS = 48, 48
 
 
@@ -174,6 +175,7 @@ def _argtypes() -> dict:
         'sig_latency_voice_bus_workspace': [i32, i32, i32],
         'sig_control_program': program,
         'sig_control_program_windowed': program,
+        'sig_control_program_envelope': program,
         'sig_control_program_attach': [p32, i32, ctypes.c_char_p, p32],
         'sig_control_program_attached': [i32] + program,
         'sig_voice_program': [ctypes.POINTER(VoiceProgramT), i32, i64, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64), i32] + bus + out,
@@ -934,12 +936,14 @@ def runtime_device():
 
 
 def control_program(rate: int, position: int, step: int, nblocks: int, cols: int, program: torch.Tensor, n_ins: int,
-                    outs: torch.Tensor, n_outs: int, front_position: int = -1, min_position: int = 0, windowed: bool = False) -> None:
+                    outs: torch.Tensor, n_outs: int, front_position: int = -1, min_position: int = 0, windowed: bool = False,
+                    envelope: bool = False) -> None:
     """run a block-rate control program (sig_control_program): `program` / `outs` are device byte tensors of CtlIns / CtlOut;
     `front_position` >= 0 also evaluates it at that position into the outputs' `front` rows; blocks whose position lies below
-    `min_position` are evaluated there.  `windowed`: the program holds Noise / Filter instructions (sig_control_program_windowed)"""
+    `min_position` are evaluated there.  `windowed`: the program holds Noise / Filter instructions (sig_control_program_windowed);
+    `envelope`: it holds ADSR pairs (sig_control_program_envelope, which runs the windowed ones as well)"""
     _gpu(program, outs)
-    entry = lib().sig_control_program_windowed if windowed else lib().sig_control_program
+    entry = lib().sig_control_program_envelope if envelope else lib().sig_control_program_windowed if windowed else lib().sig_control_program
     _check(entry(rate, position, step, nblocks, cols, front_position, min_position, program.data_ptr(), n_ins,
                                      outs.data_ptr(), n_outs, _stream(program)), 'sig_control_program')
 
@@ -947,6 +951,11 @@ def control_program(rate: int, position: int, step: int, nblocks: int, cols: int
 def control_program_description(ins: list, outs: list) -> list:
     """what a specialised build of control_program.hip is keyed by: [n_ins, n_outs, (op, kind, a, b, c, dst, wide) per
     instruction (wide: bit 0 more than one column, bit 1 window-rate), (reg, wide) per output] -- the program's structure without its pointers (CtlIns / CtlOut lists)"""
+    args_op, adsr_op = CTL_OPS['AdsrArgs'], CTL_OPS['Adsr']
+    for k, x in enumerate(ins):     # (the uploaded program is device memory: the library cannot look, sig_control_program_envelope)
+        if (x.op == adsr_op and (k == 0 or ins[k - 1].op != args_op or (ins[k - 1].cols, ins[k - 1].reserved) != (x.cols, x.reserved))) or \
+                (x.op == args_op and (k + 1 >= len(ins) or ins[k + 1].op != adsr_op)):
+            raise ValueError(f'control program: instruction {k} is half of an AdsrArgs / Adsr pair')
     words = [len(ins), len(outs)]
     for x in ins:
         words += [x.op, x.kind, x.a, x.b, x.c, x.dst, (1 if x.cols > 1 else 0) | (2 if x.reserved else 0)]

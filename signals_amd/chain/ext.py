@@ -77,7 +77,16 @@ class ADSR(BlockCachingEmitter, ImplicitChannels):
     """Position-pure piecewise-linear envelope per voice at frame rate; multiply it into a signal with
     `RingMod` (frame-rate product; `Gain.right` is block-rate, fx.py:52).  Ports (all block-rate, seconds
     except `sustain`, a level): attack, decay, sustain, release, gate_on, gate_off.  Definition:
-    oracle/chain_ref.py:adsr; kernel: sig_adsr."""
+    oracle/chain_ref.py:adsr; kernel: sig_adsr.
+
+    At block rate: plugged into a control port (a filter envelope, `cutoff = Mix(Fixed(peak), Fixed(base), mix=ADSR)`; a pitch
+    envelope on `hertz`; `resonance`, `ratio`, `spread`, `index`, `select`) it answers the one-frame request at the block's
+    position in float64, the level at t = position / rate.  The batched engine evaluates that as one instruction of the block-rate
+    control program (SIG_CTL_ADSR, the same operations, the same bits); its own six ports may then be driven by anything that
+    program covers, an LFO on `release` for instance, and under a control-path LowPass / HighPass (a slewed envelope) they must
+    be Fixed.  One instance may feed a `RingMod` at frame rate and a control port at once -- one envelope for amplitude and
+    cutoff.  The engine computes the two reads separately; this eager path may serve the one-frame read from a cached float32
+    block of the frame-rate read that contains it, a relative difference of 2^-24."""
     attack: Receiver.BoundPort = port('attack')
     decay: Receiver.BoundPort = port('decay')
     sustain: Receiver.BoundPort = port('sustain')

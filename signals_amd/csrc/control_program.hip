@@ -14,6 +14,7 @@
 #include <mutex>
 #include <vector>
 
+#include "sig_adsr.h"
 #include "sig_biquad.h"
 #include "sig_noise.h"
 #include "sig_osc.h"
@@ -39,6 +40,15 @@ static_assert(kSpecThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h
 constexpr int window_start(int k) { int w = k; while (w > 0 && (kIns[w - 1].wide & 2)) --w; return w; }
 constexpr bool has_filter() { for (int k = 0; k < kN; ++k) if (kIns[k].op == SIG_CTL_FILTER) return true; return false; }
 constexpr bool kHasFilter = has_filter();
+// an ADSR's other three registers ride in the ADSRARGS word right in front of it (the header's description)
+constexpr bool pairs_formed() {
+    for (int k = 0; k < kN; ++k) {
+        if (kIns[k].op == SIG_CTL_ADSR && (k == 0 || kIns[k - 1].op != SIG_CTL_ADSRARGS || kIns[k - 1].wide != kIns[k].wide)) return false;
+        if (kIns[k].op == SIG_CTL_ADSRARGS && (k + 1 >= kN || kIns[k + 1].op != SIG_CTL_ADSR)) return false;
+    }
+    return true;
+}
+static_assert(pairs_formed(), "every SIG_CTL_ADSR has its SIG_CTL_ADSRARGS right in front of it");
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(double rate, int64_t position, int64_t step, int nblocks, int cols,
@@ -88,6 +98,13 @@ extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(d
             case SIG_CTL_MIX: { const double c = get(I.c); x = c * get(I.a) + (1.0 - c) * get(I.b); break; }   // fx.py:40
             case SIG_CTL_AMP: { const double a = get(I.a); x = copysign(pow(a, get(I.b)), a); break; }           // fx.py:60
             case SIG_CTL_NOISE: x = sig_noise::noise_value((uint64_t)(uintptr_t)program[k].row, frame, v); break;   // noise.hip
+            case SIG_CTL_ADSRARGS: x = 0.0; break;                                                             // (read by the ADSR behind it)
+            case SIG_CTL_ADSR: {                                                                               // adsr.hip
+                const SIns G = kIns[k > 0 ? k - 1 : 0];
+                const sig_env::Voice p = sig_env::make_voice(get(I.a), get(I.b), get(I.c), get(G.a), get(G.b), get(G.c));
+                x = sig_env::level(p, (double)frame / rate);
+                break;
+            }
             default: x = get(I.a) * get(I.b); break;                                                           // Gain, RingMod: fx.py:46, :52
         }
         if (narrow) x = (double)(float)x;
@@ -187,7 +204,8 @@ static_assert(kThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h + 1
 // column chunk -- a vibrato + sweep + tremolo program over 1024 blocks x 1024 voices took 65 us with every (block, column)
 // thread running all 26 instructions, three f64 sines among them.
 // EXT (sig_control_program_windowed): also NOISE and FILTER with its window-rate instructions (the header's description).
-template <bool EXT>
+// ENV (sig_control_program_envelope): EXT and the ADSRARGS / ADSR pair.
+template <bool EXT, bool ENV = false>
 __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, int64_t position, int64_t step, int nblocks, int cols,
                                                                    int64_t front_position, int64_t min_position,
                                                                    const sig_ctl_ins* __restrict__ program, int n_ins,
@@ -195,6 +213,7 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
 {
     __shared__ sig_ctl_ins prog[SIG_CTL_MAX_INS];
     extern __shared__ double regs[];                                           // [register][thread]
+    static_assert(EXT || !ENV, "the envelope variant is the windowed one and the ADSR pair");
     {
         const int words = n_ins * (int)(sizeof(sig_ctl_ins) / 4);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(program);
@@ -247,6 +266,19 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
             case SIG_CTL_AMP: { const double a = get(ins.a); x = copysign(pow(a, get(ins.b)), a); break; }           // fx.py:60
             case SIG_CTL_NOISE:
                 if (EXT) { x = sig_noise::noise_value((uint64_t)(uintptr_t)ins.row, frame, v); break; }   // noise.hip
+                [[fallthrough]];
+            case SIG_CTL_ADSRARGS:
+                if (ENV) return;                                                        // (read by the ADSR behind it)
+                [[fallthrough]];
+            case SIG_CTL_ADSR:
+                if (ENV) {                                                              // adsr.hip: the level at this one frame
+                    const sig_ctl_ins* g = &ins - 1;                                    // a lone ADSR reads zeros for the carrier's three
+                    const bool paired = &ins != prog && g->op == SIG_CTL_ADSRARGS;
+                    const sig_env::Voice p = sig_env::make_voice(get(ins.a), get(ins.b), get(ins.c), get(paired ? g->a : -1),
+                                                                 get(paired ? g->b : -1), get(paired ? g->c : -1));
+                    x = sig_env::level(p, (double)frame / rate);
+                    break;
+                }
                 [[fallthrough]];
             default: x = get(ins.a) * get(ins.b); break;                                                           // Gain, RingMod: fx.py:46, :52
         }
@@ -355,7 +387,7 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     }
 }
 
-template <bool EXT>
+template <bool EXT, bool ENV = false>
 int launch_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
                            int64_t front_position, int64_t min_position,
                            const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
@@ -367,7 +399,7 @@ int launch_control_program(int32_t rate, int64_t position, int32_t step, int32_t
     // here -- the LDS register file is sized by n_ins, and n_ins <= SIG_CTL_MAX_INS == SIG_CTL_MAX_REGS was checked above
     static_assert(SIG_CTL_MAX_INS <= SIG_CTL_MAX_REGS, "the register file is sized by the instruction count");
     const int n_regs = n_ins > 0 ? n_ins : 1;
-    control_program_kernel<EXT><<<(unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>((double)rate, position, step, nblocks, cols, front_position, min_position,
+    control_program_kernel<EXT, ENV><<<(unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>((double)rate, position, step, nblocks, cols, front_position, min_position,
                                                                                           program, n_ins, outs, n_outs);
     return sig_launch_status();
 }
@@ -388,11 +420,31 @@ extern "C" int sig_control_program_windowed(int32_t rate, int64_t position, int3
     return launch_control_program<true>(rate, position, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, stream);
 }
 
+extern "C" int sig_control_program_envelope(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols,
+                                            int64_t front_position, int64_t min_position,
+                                            const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
+{
+    return launch_control_program<true, true>(rate, position, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, stream);
+}
+
 // ---- specialised builds of this file (see the top): attached at run time, launched through a handle.  The program itself is in
 // device memory, so the library cannot match it against the image: the caller keeps the handle with the program it built the
 // image from (signals_amd/engine/control.py: _ControlProgram).
 namespace {
 struct CtlSpecial { hipModule_t mod; hipFunction_t fn; };
+// the ADSRARGS / ADSR pairs of a description (the header's words): each ADSR right behind its carrier, both of one width and rate
+bool ctl_pairs_formed(const int32_t* description, int32_t n_words)
+{
+    const int n = description[0];
+    if (n < 0 || n > SIG_CTL_MAX_INS || 2 + 7 * n > n_words) return false;
+    auto op = [&](int k) { return description[2 + 7 * k]; };
+    auto wide = [&](int k) { return description[2 + 7 * k + 6]; };
+    for (int k = 0; k < n; ++k) {
+        if (op(k) == SIG_CTL_ADSR && (k == 0 || op(k - 1) != SIG_CTL_ADSRARGS || wide(k - 1) != wide(k))) return false;
+        if (op(k) == SIG_CTL_ADSRARGS && (k + 1 >= n || op(k + 1) != SIG_CTL_ADSR)) return false;
+    }
+    return true;
+}
 std::vector<CtlSpecial>& ctl_specials() { static std::vector<CtlSpecial> v; return v; }
 std::mutex& ctl_specials_lock() { static std::mutex m; return m; }
 }  // namespace
@@ -400,6 +452,7 @@ std::mutex& ctl_specials_lock() { static std::mutex m; return m; }
 extern "C" int sig_control_program_attach(const int32_t* description, int32_t n_words, const void* image, int32_t* handle)
 {
     SIG_CHECK_ARG(description && image && handle && n_words >= 2 && n_words <= 2 + 7 * SIG_CTL_MAX_INS + 2 * 64);
+    SIG_CHECK_ARG(ctl_pairs_formed(description, n_words));
     CtlSpecial e{};
     hipError_t err = hipModuleLoadData(&e.mod, image);
     if (err != hipSuccess) { (void)hipGetLastError(); return (int)err; }

@@ -26,12 +26,11 @@ __device__ __forceinline__ double held(const Voice& p, double t) {
     return (u < 0.0) ? 0.0 : ((v < 0.0) ? a : 1.0 + p.sm1 * d);
 }
 
-__device__ __forceinline__ Voice load_voice(const AdsrRows& in, int v) {
+// the constants from the six parameter values (the loads are the caller's: load_voice below, control_program.hip's registers)
+__device__ __forceinline__ Voice make_voice(double attack, double decay, double sustain, double release, double on, double off) {
     Voice p;
-    const double attack = in.p[0][(int64_t)v * in.s[0]], decay = in.p[1][(int64_t)v * in.s[1]];
-    const double sustain = in.p[2][(int64_t)v * in.s[2]], release = in.p[3][(int64_t)v * in.s[3]];
-    p.on = in.p[4][(int64_t)v * in.s[4]];
-    p.off = in.p[5][(int64_t)v * in.s[5]];
+    p.on = on;
+    p.off = off;
     p.attack = attack;
     p.ia = (attack > 0.0) ? 1.0 / attack : 0.0;
     p.id = (decay > 0.0) ? 1.0 / decay : 0.0;
@@ -41,6 +40,12 @@ __device__ __forceinline__ Voice load_voice(const AdsrRows& in, int v) {
     p.sm1 = sustain - 1.0;
     p.hold_off = held(p, p.off);
     return p;
+}
+
+__device__ __forceinline__ Voice load_voice(const AdsrRows& in, int v) {
+    const double attack = in.p[0][(int64_t)v * in.s[0]], decay = in.p[1][(int64_t)v * in.s[1]];
+    const double sustain = in.p[2][(int64_t)v * in.s[2]], release = in.p[3][(int64_t)v * in.s[3]];
+    return make_voice(attack, decay, sustain, release, in.p[4][(int64_t)v * in.s[4]], in.p[5][(int64_t)v * in.s[5]]);
 }
 
 // envelope level at time t (seconds)

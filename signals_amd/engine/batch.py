@@ -48,7 +48,7 @@ class _Batch:
 
     def _control_many(self, ports: list, front_position: int = -1, channels: int | None = None):
         """the block-rate replies of several control ports, their subgraphs evaluated in one launch where they consist of
-        oscillators, element-wise nodes, Fixed rows, White and LowPass / HighPass over those (else node by node, like `_control`);
+        oscillators, element-wise nodes, Fixed rows, ADSR envelopes, White and LowPass / HighPass over those (else node by node, like `_control`);
         with `front_position` also their one-row replies at that position: (rows, fronts).  `channels`: the request width the
         ports are read with."""
         o = self.owner
@@ -99,6 +99,14 @@ class _Batch:
             if not self._widths:
                 raise NotBatchable(f'{what}: {src.cls_name()} read where the request width is not known')
             width = self._widths[-1]
+            program = o._control_program(('node', id(src), K, width),
+                                         lambda: _ControlProgram((src,), K, channels=width, status=o._status_word))
+            self._check_windowed(program, [])
+            result = program.run(o, self.rate, self.pos, self.N)[0]
+        elif isinstance(src, ext.ADSR):
+            # an envelope read at one frame per block: a control program of its own, its parameters' subgraphs included (as wide
+            # as they broadcast, whatever the request's width)
+            width = self._widths[-1] if self._widths else None
             program = o._control_program(('node', id(src), K, width),
                                          lambda: _ControlProgram((src,), K, channels=width, status=o._status_word))
             self._check_windowed(program, [])
