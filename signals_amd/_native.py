@@ -339,6 +339,25 @@ def _history_input(buf: torch.Tensor, history: int, voices: int, out: torch.Tens
     return buf.data_ptr() + history * buf.stride(0) * buf.element_size()
 
 
+def _coldstart_launch(what: str, rate: int, position: int, block_frames: int, nblocks: int, context: int, buf: torch.Tensor, history: int,
+                      out: torch.Tensor, status: torch.Tensor | None, *also, per_voice: torch.Tensor | None = None,
+                      f32_only: bool = False):
+    """what every cold-start filter launch marshals the same way, from `buf` (`history` context rows, then the input rows) and `out`:
+    (voices, head, window, dst, tail) -- head = (rate, position, block_frames, nblocks, context, voices) behind the entry's filter type,
+    window = (in, in_ld, in_history), dst = (out, out_ld) in front of the entries' buffer dtype, tail = (status, stream).
+    `also`: further tensors that must be on the GPU; `per_voice`: the buffer with one column per voice where that is not `out`;
+    `f32_only`: refuse another `out`"""
+    _gpu(buf, out, status, *also)
+    _audio(buf, f'{what} in')
+    _audio(out, f'{what} out')
+    voices = (out if per_voice is None else per_voice).shape[1]
+    if f32_only and out.dtype != torch.float32:
+        raise NativeError(f'{what} out must be float32, got {out.dtype}')
+    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, what)
+    return (voices, (rate, position, block_frames, nblocks, context, voices), (in_ptr, buf.stride(0), history),
+            (out.data_ptr(), out.stride(0)), (_ptr(status), _stream(out)))
+
+
 def _parameter_rows(rows: int, rows_per_param: int, *counts) -> int:
     """`rows_per_param` as the oscillator launches take it (0: one parameter row for all), checked against the (rows, name) of
     every parameter"""
@@ -488,29 +507,16 @@ def biquad_coldstart(btype: str, rate: int, position: int, block_frames: int, nb
     `out` (nblocks*block_frames, voices) receives the filtered blocks.
     cutoff: f64 (1|nblocks, V|1).  `envelope`: ADSR control rows (name -> (1,V)|(1,1) f64); the stored rows
     are then multiplied by the envelope (float32 buffers only)."""
-    _gpu(cutoff, buf, out, status, *(envelope or {}).values())
-    _audio(buf, 'biquad in')
-    _audio(out, 'biquad out')
-    voices = out.shape[1]
-    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
-    if cutoff.dtype != torch.float64 or cutoff.dim() != 2 or not cutoff.is_contiguous():
-        raise NativeError('cutoff must be a contiguous float64 2-D tensor')
-    if cutoff.shape[0] not in (1, nblocks) or cutoff.shape[1] not in (1, voices):
-        raise NativeError(f'cutoff shape {tuple(cutoff.shape)} vs blocks {nblocks} voices {voices}')
-    if cutoff.shape[1] != voices and voices != 1:
-        # the reference indexes crit[0, i] for every channel i (fx.py:99)
-        raise IndexError(f'index {cutoff.shape[1]} is out of bounds for axis 1 with size {cutoff.shape[1]}')
-    head = (FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-            cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0])
+    voices, head, window, dst, tail = _coldstart_launch('biquad', rate, position, block_frames, nblocks, context, buf, history, out, status,
+                                                cutoff, *(envelope or {}).values())
+    rows = _block_rows(cutoff, 'cutoff', nblocks, voices)                      # (checked before the type is looked up)
+    head = (FILT_TYPES[btype], *head, *rows)
     if envelope is not None:
         if out.dtype != torch.float32:
             raise NativeError('the envelope epilogue is float32 only')
-        _check(lib().sig_biquad_coldstart_env(*head, *_envelope(envelope, voices), in_ptr, buf.stride(0), history,
-                                              out.data_ptr(), out.stride(0), _ptr(status), _stream(out)),
-               'sig_biquad_coldstart_env')
+        _check(lib().sig_biquad_coldstart_env(*head, *_envelope(envelope, voices), *window, *dst, *tail), 'sig_biquad_coldstart_env')
         return out
-    _check(lib().sig_biquad_coldstart(*head, in_ptr, buf.stride(0), history, out.data_ptr(), out.stride(0), _dt(out),
-                                      _ptr(status), _stream(out)), 'sig_biquad_coldstart')
+    _check(lib().sig_biquad_coldstart(*head, *window, *dst, _dt(out), *tail), 'sig_biquad_coldstart')
     return out
 
 
@@ -526,21 +532,22 @@ def _block_rows(t: torch.Tensor, what: str, nblocks: int, voices: int, broadcast
     return t.data_ptr(), 0 if t.shape[1] == 1 else 1, t.shape[0]
 
 
+def _optional_rows(t: torch.Tensor | None, what: str, nblocks: int, voices: int):
+    """`_block_rows` of a control that may be unplugged (None: a null row) and that one column holds for every voice"""
+    return (None, 0, 1) if t is None else _block_rows(t, what, nblocks, voices, broadcast=True)
+
+
 def biquad_coldstart_q(btype: str, rate: int, position: int, block_frames: int, nblocks: int, context: int,
                        cutoff: torch.Tensor, resonance: torch.Tensor | None, buf: torch.Tensor, history: int, out: torch.Tensor,
                        status: torch.Tensor | None = None) -> torch.Tensor:
     """`biquad_coldstart` with a resonance row (sig_biquad_coldstart_q: the resonant low-pass / high-pass of chain/ext.py).
     cutoff: f64 (1|nblocks, V); resonance: f64 (1|nblocks, V|1), a one-column row holds for every voice (the nodes refuse a narrow
     one before they get here); each per block on its own; resonance None: unplugged = 1/sqrt2 (the Butterworth design)."""
-    _gpu(cutoff, resonance, buf, out, status)
-    _audio(buf, 'biquad in')
-    _audio(out, 'biquad out')
-    voices = out.shape[1]
-    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
-    q = (None, 0, 1) if resonance is None else _block_rows(resonance, 'resonance', nblocks, voices, broadcast=True)
-    _check(lib().sig_biquad_coldstart_q(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                        *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, in_ptr, buf.stride(0), history,
-                                        out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), 'sig_biquad_coldstart_q')
+    voices, head, window, dst, tail = _coldstart_launch('biquad', rate, position, block_frames, nblocks, context, buf, history, out, status,
+                                                cutoff, resonance)
+    q = _optional_rows(resonance, 'resonance', nblocks, voices)
+    _check(lib().sig_biquad_coldstart_q(FILT_TYPES[btype], *head, *_block_rows(cutoff, 'cutoff', nblocks, voices), *q,
+                                        *window, *dst, _dt(out), *tail), 'sig_biquad_coldstart_q')
     return out
 
 
@@ -550,16 +557,12 @@ def biquad_coldstart_eq(btype: str, rate: int, position: int, block_frames: int,
     """`biquad_coldstart_q` for the equaliser biquads (sig_biquad_coldstart_eq; btype 'eqbp' | 'eqnotch' | 'eqap' | 'eqpeak' | 'eqls' |
     'eqhs').  cutoff: f64 (1|nblocks, V); resonance and gain (dB): f64 (1|nblocks, V|1), each per block on its own; None: unplugged
     = 1/sqrt2 and 0 dB."""
-    _gpu(cutoff, resonance, gain, buf, out, status)
-    _audio(buf, 'biquad in')
-    _audio(out, 'biquad out')
-    voices = out.shape[1]
-    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad')
-    q = (None, 0, 1) if resonance is None else _block_rows(resonance, 'resonance', nblocks, voices, broadcast=True)
-    g = (None, 0, 1) if gain is None else _block_rows(gain, 'gain', nblocks, voices, broadcast=True)
-    _check(lib().sig_biquad_coldstart_eq(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                         *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, *g, in_ptr, buf.stride(0), history,
-                                         out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), 'sig_biquad_coldstart_eq')
+    voices, head, window, dst, tail = _coldstart_launch('biquad', rate, position, block_frames, nblocks, context, buf, history, out, status,
+                                                cutoff, resonance, gain)
+    q = _optional_rows(resonance, 'resonance', nblocks, voices)
+    g = _optional_rows(gain, 'gain', nblocks, voices)
+    _check(lib().sig_biquad_coldstart_eq(FILT_TYPES[btype], *head, *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, *g,
+                                         *window, *dst, _dt(out), *tail), 'sig_biquad_coldstart_eq')
     return out
 
 
@@ -673,24 +676,16 @@ def biquad_coldstart_bus(btype: str, rate: int, position: int, block_frames: int
                          status: torch.Tensor | None = None) -> torch.Tensor:
     """out (nblocks*block_frames, C) f32 <- sum over voices of bus_gains * [envelope *] Filter(buf); `buf` holds
     `history` context rows followed by the input rows, like `biquad_coldstart`; `envelope`: ADSR control rows"""
-    _gpu(cutoff, buf, out, status, bus_gains, *(envelope or {}).values())
-    _audio(buf, 'biquad bus in')
-    _audio(out, 'biquad bus out')
+    voices, head, window, dst, tail = _coldstart_launch('biquad bus', rate, position, block_frames, nblocks, context, buf, history, out, status,
+                                                cutoff, bus_gains, *(envelope or {}).values(), per_voice=buf, f32_only=True)
     rows, bus = out.shape
-    voices = buf.shape[1]
-    if out.dtype != torch.float32:
-        raise NativeError(f'biquad bus out must be float32, got {out.dtype}')
-    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'biquad bus')
     if cutoff.dtype != torch.float64 or cutoff.shape[1] not in (1, voices) or cutoff.shape[0] not in (1, nblocks) \
             or not cutoff.is_contiguous():
         raise NativeError(f'cutoff must be contiguous float64 (1|{nblocks}, 1|{voices}), got {tuple(cutoff.shape)} {cutoff.dtype}')
     workspace = _bus_workspace(workspace, voices, rows, bus, out.device)
-    _check(lib().sig_biquad_coldstart_bus(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices,
-                                          cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0],
-                                          *_envelope(envelope, voices), in_ptr, buf.stride(0), history,
-                                          *_bus_gains(bus_gains, bus, voices), bus, workspace.data_ptr(),
-                                          out.data_ptr(), out.stride(0), _ptr(status), _stream(out)),
-           'sig_biquad_coldstart_bus')
+    _check(lib().sig_biquad_coldstart_bus(FILT_TYPES[btype], *head, cutoff.data_ptr(), 0 if cutoff.shape[1] == 1 else 1, cutoff.shape[0],
+                                          *_envelope(envelope, voices), *window, *_bus_gains(bus_gains, bus, voices), bus,
+                                          workspace.data_ptr(), *dst, *tail), 'sig_biquad_coldstart_bus')
     return out
 
 
@@ -1067,11 +1062,7 @@ def band_coldstart_blocks(btype: str, rate: int, position: int, block_frames: in
 
 def _band_coldstart(per_block: bool, btype, rate, position, block_frames, nblocks, context, low, high, buf, history, out, status):
     """sig_band_coldstart, or with `per_block` sig_band_coldstart_blocks: the two differ in their band edges' rows"""
-    _gpu(low, high, buf, out, status)
-    _audio(buf, 'band in')
-    _audio(out, 'band out')
-    voices = out.shape[1]
-    in_ptr = _history_input(buf, history, voices, out, block_frames, nblocks, 'band')
+    voices, head, window, dst, tail = _coldstart_launch('band', rate, position, block_frames, nblocks, context, buf, history, out, status, low, high)
     blocks = max(low.shape[0], high.shape[0])
     edges = []
     for row, name in ((low, 'low'), (high, 'high')):
@@ -1091,8 +1082,7 @@ def _band_coldstart(per_block: bool, btype, rate, position, block_frames, nblock
     else:
         name, entry = 'sig_band_coldstart', lib().sig_band_coldstart
         ptrs = _voice_rows(voices, *edges)
-    _check(entry(FILT_TYPES[btype], rate, position, block_frames, nblocks, context, voices, *ptrs, in_ptr, buf.stride(0), history,
-                 out.data_ptr(), out.stride(0), _dt(out), _ptr(status), _stream(out)), name)
+    _check(entry(FILT_TYPES[btype], *head, *ptrs, *window, *dst, _dt(out), *tail), name)
     return out
 
 

@@ -7,26 +7,13 @@
 // registers and 10 coefficients per voice.  HBM-bound: 8 B per voice-sample, 18 f64 ops.
 // `param_blocks` > 1: row b of `low` / `high` holds block b's band (a swept band: an LFO on either edge, read at
 // the block's position like biquad.hip's cutoff rows); the design stays once per wave, a wave being one block.
-#include "sig_biquad.h"
+#include "sig_coldstart.h"
 
 namespace {
 
+using namespace sig_cold;
 using sig_biquad::Biquad;
 using sig_biquad::design_band2;
-
-template <typename T, int VPT> struct RowVec;
-template <> struct RowVec<float, 1> { using type = float; };
-template <> struct RowVec<double, 1> { using type = double; };
-template <> struct RowVec<float, 4> { using type = float4; };
-template <> struct RowVec<double, 4> { using type = double4; };
-
-template <typename V> __device__ __forceinline__ void unpack(const V& v, double (&x)[1]) { x[0] = (double)v; }
-__device__ __forceinline__ void unpack(const float4& v, double (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void unpack(const double4& v, double (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void pack(float& v, const double (&y)[1]) { v = (float)y[0]; }
-__device__ __forceinline__ void pack(double& v, const double (&y)[1]) { v = y[0]; }
-__device__ __forceinline__ void pack(float4& v, const double (&y)[4]) { v = make_float4((float)y[0], (float)y[1], (float)y[2], (float)y[3]); }
-__device__ __forceinline__ void pack(double4& v, const double (&y)[4]) { v = make_double4(y[0], y[1], y[2], y[3]); }
 
 constexpr int kRing = 8;
 
@@ -103,18 +90,15 @@ int launch_band(int type, int32_t rate, int64_t position, int32_t N, int32_t K, 
                 const double* low, int ls, const double* high, int hs, int param_blocks,
                 const T* in, int64_t in_ld, T* out, int64_t out_ld, int32_t* status, hipStream_t stream)
 {
-    const bool vec4 = (voices % 4 == 0) && (in_ld % 4 == 0) && (out_ld % 4 == 0) &&
-                      (reinterpret_cast<uintptr_t>(in) % (4 * sizeof(T)) == 0) &&
-                      (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0);
-    const int span = SIG_WAVE * (vec4 ? 4 : 1);
-    const int voice_tiles = (voices + span - 1) / span;
-    const int64_t nwg = ((int64_t)voice_tiles * K + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+    const bool vec4 = vec_ok(4, sizeof(T), voices, {in_ld, out_ld}, {in, out});
+    const int voice_tiles = sig_voice_tiles(voices, vec4 ? 4 : 1);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(voice_tiles, K, 1), nwg)) return (int)hipErrorInvalidValue;
     if (vec4)
-        band_coldstart_kernel<T, 4><<<(unsigned)nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
+        band_coldstart_kernel<T, 4><<<nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
                                                                          low, ls, high, hs, param_blocks, in, in_ld, out, out_ld, voice_tiles, status);
     else
-        band_coldstart_kernel<T, 1><<<(unsigned)nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
+        band_coldstart_kernel<T, 1><<<nwg, 256, 0, stream>>>(type, (double)rate, position, N, K, ctx, voices,
                                                                          low, ls, high, hs, param_blocks, in, in_ld, out, out_ld, voice_tiles, status);
     return sig_launch_status();
 }
@@ -125,20 +109,14 @@ int run_band(int type, int32_t rate, int64_t position, int32_t block_frames, int
              int32_t* status, void* stream)
 {
     SIG_CHECK_ARG(type == SIG_FILT_BANDPASS || type == SIG_FILT_BANDSTOP);
-    SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
-    SIG_CHECK_ARG(low && high && in && out && in_ld >= voices && out_ld >= voices);
-    SIG_CHECK_ARG((low_stride | 1) == 1 && (high_stride | 1) == 1);
-    SIG_CHECK_ARG(param_blocks == 1 || param_blocks == nblocks);
-    SIG_CHECK_ARG(in_history >= (position < context ? position : context));
-    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == SIG_F32)
-        return launch_band<float>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
-                                  param_blocks, static_cast<const float*>(in), in_ld, static_cast<float*>(out), out_ld, status, s);
-    if (dtype == SIG_F64)
-        return launch_band<double>(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
-                                   param_blocks, static_cast<const double*>(in), in_ld, static_cast<double*>(out), out_ld, status, s);
-    return (int)hipErrorInvalidValue;
+    bool empty;
+    SIG_CHECK_ARG(window_ok(rate, position, block_frames, nblocks, context, voices, in, in_ld, in_history, out, empty) && out_ld >= voices);
+    SIG_CHECK_ARG(rows_ok({low, low_stride, param_blocks}, nblocks, true) && rows_ok({high, high_stride, param_blocks}, nblocks, true));
+    if (empty) return 0;
+    return dispatch_dtype(dtype, in, out, [&](auto* x, auto* y) {
+        return launch_band(type, rate, position, block_frames, nblocks, context, voices, low, low_stride, high, high_stride,
+                           param_blocks, x, in_ld, y, out_ld, status, static_cast<hipStream_t>(stream));
+    });
 }
 
 }  // namespace

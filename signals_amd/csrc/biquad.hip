@@ -14,40 +14,21 @@
 #include <type_traits>
 
 #include "sig_adsr.h"
-#include "sig_biquad.h"
+#include "sig_coldstart.h"
 
 namespace {
 
+using namespace sig_cold;
 using sig_biquad::Biquad;
 using sig_biquad::design_butter2;
-
-template <typename T, int VPT> struct RowVec;
-template <> struct RowVec<float, 1> { using type = float; };
-template <> struct RowVec<double, 1> { using type = double; };
-template <> struct RowVec<float, 2> { using type = float2; };
-template <> struct RowVec<double, 2> { using type = double2; };
-template <> struct RowVec<float, 4> { using type = float4; };
-template <> struct RowVec<double, 4> { using type = double4; };
-
-template <typename T> __device__ __forceinline__ void unpack(const T& v, double (&x)[1]) { x[0] = (double)v; }
-__device__ __forceinline__ void unpack(const float2& v, double (&x)[2]) { x[0] = v.x; x[1] = v.y; }
-__device__ __forceinline__ void unpack(const double2& v, double (&x)[2]) { x[0] = v.x; x[1] = v.y; }
-__device__ __forceinline__ void pack(float2& v, const double (&y)[2]) { v = make_float2((float)y[0], (float)y[1]); }
-__device__ __forceinline__ void pack(double2& v, const double (&y)[2]) { v = make_double2(y[0], y[1]); }
-__device__ __forceinline__ void unpack(const float4& v, double (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void unpack(const double4& v, double (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void pack(float& v, const double (&y)[1]) { v = (float)y[0]; }
-__device__ __forceinline__ void pack(double& v, const double (&y)[1]) { v = y[0]; }
-__device__ __forceinline__ void pack(float4& v, const double (&y)[4]) { v = make_float4((float)y[0], (float)y[1], (float)y[2], (float)y[3]); }
-__device__ __forceinline__ void pack(double4& v, const double (&y)[4]) { v = make_double4(y[0], y[1], y[2], y[3]); }
 
 // ENV: multiply the stored rows by a per-voice ADSR envelope evaluated at the row's time (the
 // RingMod(Filter, ADSR) pair of BASELINE config 3 without a separate pass; sig_adsr.h).  n/rate is computed for
 // 64 rows at a time, one row per lane, and broadcast with v_readlane, like in the oscillator kernels.
 // RES: the resonance rows of sig_biquad_coldstart_q (ResRows), or NoRes: the Butterworth design, and nothing of the other in the code
 struct NoRes {};
-struct ResRows { const double* ptr; int rs, blocks; };    // (blocks, voices | 1) f64 rows of q; ptr null: unplugged = 1/sqrt2
-struct EqRows { ResRows q, gain; };                       // sig_biquad_coldstart_eq: q as above, gain (dB) likewise; null: 0 dB
+using ResRows = BlockRows;                                // q; ptr null: unplugged = 1/sqrt2
+struct EqRows { BlockRows q, gain; };                     // sig_biquad_coldstart_eq: q as above, gain (dB) likewise; null: 0 dB
 
 template <typename T, int VPT, int kRing, bool ENV, typename RES>   // kRing = rows of loads in flight per lane
 __device__ __forceinline__ void biquad_coldstart_body(
@@ -83,8 +64,8 @@ __device__ __forceinline__ void biquad_coldstart_body(
         if (!ok && live && status) atomicOr(status, SIG_STATUS_BAD_CUTOFF);
     } else if constexpr (std::is_same<RES, EqRows>::value) {
         int bad = 0;                                                           // SIG_STATUS_BAD_CUTOFF | _BAD_RESONANCE | _BAD_GAIN
-        auto at = [&](const ResRows& rows, int v) {
-            return rows.ptr ? rows.ptr + (rows.blocks > 1 ? b * (int64_t)(rows.rs ? voices : 1) : 0) + (int64_t)v * rows.rs : nullptr;
+        auto at = [&](const BlockRows& rows, int v) {
+            return rows.ptr ? rows.ptr + (rows.blocks > 1 ? b * (int64_t)(rows.stride ? voices : 1) : 0) + (int64_t)v * rows.stride : nullptr;
         };
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -100,7 +81,7 @@ __device__ __forceinline__ void biquad_coldstart_body(
         for (int i = 0; i < VPT; ++i) {
             const int v = (vc + i < voices) ? vc + i : vc;
             const double hz = cutoff[(cutoff_blocks > 1 ? b * (int64_t)(cs ? voices : 1) : 0) + (int64_t)v * cs];
-            const double* r = res.ptr ? res.ptr + (res.blocks > 1 ? b * (int64_t)(res.rs ? voices : 1) : 0) + (int64_t)v * res.rs : nullptr;
+            const double* r = res.ptr ? res.ptr + (res.blocks > 1 ? b * (int64_t)(res.stride ? voices : 1) : 0) + (int64_t)v * res.stride : nullptr;
             bad |= sig_biquad::design_resonant2(type, hz, r, rate, q[i]);
             z0[i] = 0.0; z1[i] = 0.0;
         }
@@ -303,55 +284,63 @@ __global__ __launch_bounds__(256) void biquad_walk_kernel(
     }
 }
 
-static int biquad_variant() {
-    // tuning hook: SIG_BIQUAD_VARIANT=<vpt><ring> e.g. "416" = 4 voices/lane, 16-row ring
-    static int v = [] { const char* e = getenv("SIG_BIQUAD_VARIANT"); return e ? atoi(e) : 0; }();
-    return v;
+// ---- host
+
+// one launch in the entries' terms; env, res, eq: at most one, null otherwise
+template <typename T>
+struct Launch {
+    int type; int32_t rate; int64_t position; int32_t N, K, ctx, voices;
+    BlockRows cutoff;
+    const T* in; int64_t in_ld; T* out; int64_t out_ld;
+    int32_t* status; hipStream_t stream;
+    const sig_env::AdsrRows* env; const ResRows* res; const EqRows* eq;
+};
+
+template <int VPT, int RING> struct Shape { static constexpr int vpt = VPT, ring = RING; };
+
+// f(Shape<vpt, ring>) for a pair among PAIRS (each written vpt * 100 + ring, like the tuning hooks), hipErrorInvalidValue
+// without a call for any other
+template <int... PAIRS, typename F>
+int dispatch_shape(int vpt, int ring, F&& f)
+{
+    int err = (int)hipErrorInvalidValue;
+    auto one = [&](auto shape) { if (vpt == shape.vpt && ring == shape.ring) err = f(shape); };
+    (one(Shape<PAIRS / 100, PAIRS % 100>{}), ...);
+    return err;
 }
 
+static int env_int(const char* name, int otherwise) { const char* e = getenv(name); return e ? atoi(e) : otherwise; }
+
 template <typename T, bool ENV>
-int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K, int32_t ctx, int32_t voices,
-                  const double* cutoff, int32_t cs, int32_t cutoff_blocks,
-                  const T* in, int64_t in_ld, T* out, int64_t out_ld, int32_t* status, hipStream_t stream,
-                  const sig_env::AdsrRows& env, const ResRows* res = nullptr, const EqRows* eq = nullptr)
+int launch_biquad(const Launch<T>& a)
 {
-    auto ok = [&](int vpt) {
-        return (voices % vpt == 0) && (in_ld % vpt == 0) && (out_ld % vpt == 0) &&
-               (reinterpret_cast<uintptr_t>(in) % (vpt * sizeof(T)) == 0) &&
-               (reinterpret_cast<uintptr_t>(out) % (vpt * sizeof(T)) == 0);
-    };
-    int variant = biquad_variant();
+    const int K = a.K, voices = a.voices;
+    const sig_env::AdsrRows env = ENV ? *a.env : sig_env::AdsrRows{};
+    auto ok = [&](int vpt) { return vec_ok(vpt, sizeof(T), voices, {a.in_ld, a.out_ld}, {a.in, a.out}); };
+    // tuning hook: SIG_BIQUAD_VARIANT=<vpt><ring> e.g. "416" = 4 voices/lane, 16-row ring
+    static const int variant = env_int("SIG_BIQUAD_VARIANT", 0);
     // span walker: every row read once (see biquad_walk_kernel).  Keep >= ~1024 waves on the chip.
     {
-        static const int walk_env = [] { const char* e = getenv("SIG_BIQUAD_WALK"); return e ? atoi(e) : -1; }();
-        static const int walk_variant = [] { const char* e = getenv("SIG_WALK_VARIANT"); return e ? atoi(e) : 0; }();
+        static const int walk_env = env_int("SIG_BIQUAD_WALK", -1);
+        static const int walk_variant = env_int("SIG_WALK_VARIANT", 0);
         int wvpt = walk_variant ? walk_variant / 100 : 4;                     // tuning: <vpt><ring>, e.g. 216
         const int wring = walk_variant ? walk_variant % 100 : 16;
         while (wvpt > 1 && !ok(wvpt)) wvpt >>= 1;
-        const int tiles = (voices + SIG_WAVE * wvpt - 1) / (SIG_WAVE * wvpt);
+        const int tiles = sig_voice_tiles(voices, wvpt);
         // measured on C2 at K=1024 (vpt x ring x span sweep): 4 voices/lane, 16 rows in flight, span 4 is the best
         // point (5.0 TB/s algorithmic); longer spans starve the chip of waves, shorter ones re-read more context
         int span = (int)(((int64_t)tiles * K) / 1024);
         if (span > 4) span = 4;
         if (walk_env >= 0) span = walk_env;                                    // tuning: 0/1 disables
-        if (span >= 2 && N > ctx && cutoff_blocks == 1 && variant == 0 && !res && !eq) {   // (the resonant and the equaliser entries: the plain kernel only)
-            const int64_t items = (int64_t)tiles * ((K + span - 1) / span);
-            const int64_t nwg = (items + 3) / 4;
-            if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-#define SIG_WALK(V, R) biquad_walk_kernel<T, V, R, ENV><<<(unsigned)nwg, 256, 0, stream>>>( \
-                type, (double)rate, position, N, K, ctx, voices, span, cutoff, cs, in, in_ld, out, out_ld, tiles, status, env)
-            switch (wvpt * 100 + wring) {
-                case 116: SIG_WALK(1, 16); break;
-                case 132: SIG_WALK(1, 32); break;
-                case 216: SIG_WALK(2, 16); break;
-                case 232: SIG_WALK(2, 32); break;
-                case 408: SIG_WALK(4, 8); break;
-                case 416: SIG_WALK(4, 16); break;
-                case 432: SIG_WALK(4, 32); break;
-                default: return (int)hipErrorInvalidValue;
-            }
-#undef SIG_WALK
-            return sig_launch_status();
+        if (span >= 2 && a.N > a.ctx && a.cutoff.blocks == 1 && variant == 0 && !a.res && !a.eq) {   // (the resonant and the equaliser entries: the plain kernel only)
+            unsigned nwg;
+            if (!sig_workgroups(sig_span_waves(tiles, K, span), nwg)) return (int)hipErrorInvalidValue;
+            return dispatch_shape<116, 132, 216, 232, 408, 416, 432>(wvpt, wring, [&](auto s) {
+                biquad_walk_kernel<T, s.vpt, s.ring, ENV><<<nwg, 256, 0, a.stream>>>(
+                    a.type, (double)a.rate, a.position, a.N, K, a.ctx, voices, span, a.cutoff.ptr, a.cutoff.stride,
+                    a.in, a.in_ld, a.out, a.out_ld, tiles, a.status, env);
+                return sig_launch_status();
+            });
         }
     }
     int vpt = variant ? variant / 100 : 4;
@@ -359,88 +348,54 @@ int launch_biquad(int type, int32_t rate, int64_t position, int32_t N, int32_t K
     if (!variant) {
         // lanes walk rows serially: with few (voice tile, block) items prefer more, narrower waves and a deeper
         // ring (big blocks x few blocks, e.g. N=1024 K=64, would otherwise leave 3/4 of the SIMDs idle)
-        while (vpt > 1 && (int64_t)((voices + SIG_WAVE * vpt - 1) / (SIG_WAVE * vpt)) * K < 2048) vpt >>= 1;
+        while (vpt > 1 && sig_span_waves(sig_voice_tiles(voices, vpt), K, 1) < 2048) vpt >>= 1;
         ring = (vpt == 4) ? 8 : 16;
     }
     while (vpt > 1 && !ok(vpt)) vpt >>= 1;
     if (vpt == 1 && !variant) ring = 16;
-    const int span = SIG_WAVE * vpt;
-    const int voice_tiles = (voices + span - 1) / span;
-    const int64_t items = (int64_t)voice_tiles * K;
-    const int64_t nwg = (items + 3) / 4;
-    if (nwg > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-#define SIG_BQ(V, R) do { \
-        if constexpr (!ENV) { \
-            if (eq) { \
-                biquad_coldstart_eq_kernel<T, V, R><<<(unsigned)nwg, 256, 0, stream>>>( \
-                    type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, *eq, in, in_ld, out, out_ld, voice_tiles, status); \
-                break; \
-            } \
-            if (res) { \
-                biquad_coldstart_q_kernel<T, V, R><<<(unsigned)nwg, 256, 0, stream>>>( \
-                    type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, *res, in, in_ld, out, out_ld, voice_tiles, status); \
-                break; \
-            } \
-        } \
-        biquad_coldstart_kernel<T, V, R, ENV><<<(unsigned)nwg, 256, 0, stream>>>( \
-            type, (double)rate, position, N, K, ctx, voices, cutoff, cs, cutoff_blocks, in, in_ld, out, out_ld, voice_tiles, status, env); \
-    } while (0)
-    switch (vpt * 100 + ring) {
-        case 108: SIG_BQ(1, 8); break;
-        case 116: SIG_BQ(1, 16); break;
-        case 132: SIG_BQ(1, 32); break;
-        case 208: SIG_BQ(2, 8); break;
-        case 216: SIG_BQ(2, 16); break;
-        case 232: SIG_BQ(2, 32); break;
-        case 408: SIG_BQ(4, 8); break;
-        case 416: SIG_BQ(4, 16); break;
-        case 432: SIG_BQ(4, 32); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef SIG_BQ
-    return sig_launch_status();
+    const int voice_tiles = sig_voice_tiles(voices, vpt);
+    unsigned nwg;
+    if (!sig_workgroups(sig_span_waves(voice_tiles, K, 1), nwg)) return (int)hipErrorInvalidValue;
+    return dispatch_shape<108, 116, 132, 208, 216, 232, 408, 416, 432>(vpt, ring, [&](auto s) {
+        constexpr int V = decltype(s)::vpt, R = decltype(s)::ring;
+        const double rate = a.rate;
+        const BlockRows& c = a.cutoff;
+        if (!ENV && a.eq) {
+            if constexpr (!ENV)
+                biquad_coldstart_eq_kernel<T, V, R><<<nwg, 256, 0, a.stream>>>(
+                    a.type, rate, a.position, a.N, K, a.ctx, voices, c.ptr, c.stride, c.blocks, *a.eq, a.in, a.in_ld, a.out, a.out_ld, voice_tiles, a.status);
+        } else if (!ENV && a.res) {
+            if constexpr (!ENV)
+                biquad_coldstart_q_kernel<T, V, R><<<nwg, 256, 0, a.stream>>>(
+                    a.type, rate, a.position, a.N, K, a.ctx, voices, c.ptr, c.stride, c.blocks, *a.res, a.in, a.in_ld, a.out, a.out_ld, voice_tiles, a.status);
+        } else {
+            biquad_coldstart_kernel<T, V, R, ENV><<<nwg, 256, 0, a.stream>>>(
+                a.type, rate, a.position, a.N, K, a.ctx, voices, c.ptr, c.stride, c.blocks, a.in, a.in_ld, a.out, a.out_ld, voice_tiles, a.status, env);
+        }
+        return sig_launch_status();
+    });
 }
-
-}  // namespace
-
-namespace {
 
 int run_biquad(int type, int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context,
                int32_t voices, const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
                const void* in, int64_t in_ld, int64_t in_history, void* out, int64_t out_ld, int32_t dtype,
                int32_t* status, void* stream, const sig_env::AdsrRows* env, const ResRows* res = nullptr, const EqRows* eq = nullptr)
 {
-    auto rows_ok = [&](const ResRows& r) { return (r.rs == 0 || r.rs == 1) && (r.blocks == 1 || r.blocks == nblocks); };
+    bool empty;
     SIG_CHECK_ARG(eq ? (type >= SIG_FILT_EQ_BANDPASS && type <= SIG_FILT_EQ_HIGHSHELF) : (type == SIG_FILT_LOWPASS || type == SIG_FILT_HIGHPASS));
-    SIG_CHECK_ARG(!res || (!env && rows_ok(*res)));
-    SIG_CHECK_ARG(!eq || (!env && !res && rows_ok(eq->q) && rows_ok(eq->gain)));
-    SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
-    SIG_CHECK_ARG(cutoff != nullptr && in != nullptr && out != nullptr);
-    SIG_CHECK_ARG(cutoff_stride == 0 || cutoff_stride == 1);
-    SIG_CHECK_ARG(cutoff_blocks == 1 || cutoff_blocks == nblocks);
-    SIG_CHECK_ARG(in_ld >= voices && out_ld >= voices);
-    // block 0 reads min(context, position) rows in front of `in`; later blocks reach back into
-    // earlier blocks' rows and, when block_frames < context, also into the history.
-    {
-        const int64_t c0 = position < context ? position : context;
-        SIG_CHECK_ARG(in_history >= c0);
-    }
-    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const sig_env::AdsrRows none{};
-    if (dtype == SIG_F32) {
-        const float* x = static_cast<const float*>(in);
-        float* y = static_cast<float*>(out);
-        return env ? launch_biquad<float, true>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
-                                                cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, *env)
-                   : launch_biquad<float, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
-                                                 cutoff_stride, cutoff_blocks, x, in_ld, y, out_ld, status, s, none, res, eq);
-    }
-    if (dtype == SIG_F64 && !env)
-        return launch_biquad<double, false>(type, rate, position, block_frames, nblocks, context, voices, cutoff,
-                                            cutoff_stride, cutoff_blocks, static_cast<const double*>(in), in_ld,
-                                            static_cast<double*>(out), out_ld, status, s, none, res, eq);
-    return (int)hipErrorInvalidValue;
+    SIG_CHECK_ARG(!res || (!env && rows_ok(*res, nblocks, false)));
+    SIG_CHECK_ARG(!eq || (!env && !res && rows_ok(eq->q, nblocks, false) && rows_ok(eq->gain, nblocks, false)));
+    SIG_CHECK_ARG(window_ok(rate, position, block_frames, nblocks, context, voices, in, in_ld, in_history, out, empty));
+    SIG_CHECK_ARG(rows_ok({cutoff, cutoff_stride, cutoff_blocks}, nblocks, true) && out_ld >= voices);
+    if (empty) return 0;
+    return dispatch_dtype(dtype, in, out, [&](auto* x, auto* y) {
+        using T = std::remove_pointer_t<decltype(y)>;
+        const Launch<T> a{type, rate, position, block_frames, nblocks, context, voices, {cutoff, cutoff_stride, cutoff_blocks},
+                          x, in_ld, y, out_ld, status, static_cast<hipStream_t>(stream), env, res, eq};
+        if (!env) return launch_biquad<T, false>(a);
+        if constexpr (std::is_same<T, float>::value) return launch_biquad<float, true>(a);      // the envelope epilogue: float32 only
+        return (int)hipErrorInvalidValue;
+    });
 }
 
 }  // namespace

@@ -10,11 +10,12 @@
 #include <type_traits>
 
 #include "sig_adsr.h"
-#include "sig_biquad.h"
 #include "sig_bus_tile.h"
+#include "sig_coldstart.h"
 
 namespace {
 
+using namespace sig_cold;
 using sig_biquad::Biquad;
 using sig_biquad::design_butter2;
 
@@ -26,16 +27,10 @@ struct Args {
     int voice_tiles; int* status;
 };
 
-template <int VPT> struct RowVec;
-template <> struct RowVec<1> { using type = float; };
-template <> struct RowVec<4> { using type = float4; };
-__device__ __forceinline__ void unpack(const float& v, double (&x)[1]) { x[0] = v; }
-__device__ __forceinline__ void unpack(const float4& v, double (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-
 template <int VPT, int kRing, bool ENV, int C>
 __global__ __launch_bounds__(256) void biquad_bus_kernel(Args a, sig_env::AdsrRows env)
 {
-    using Vec = typename RowVec<VPT>::type;
+    using Vec = typename RowVec<float, VPT>::type;
     __shared__ double lds[4][sig_bus::kTileDoubles];
     const int lane = threadIdx.x & 63;
     const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // one wave = one (voice tile, block)
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(256) void biquad_bus_kernel(Args a, sig_env::AdsrRo
 template <bool ENV, int C>
 int launch(Args a, const sig_env::AdsrRows& env, float* out, int64_t out_ld, hipStream_t stream)
 {
-    const bool vec = (a.voices % 4 == 0) && (a.in_ld % 4 == 0) && (reinterpret_cast<uintptr_t>(a.in) % 16 == 0);
+    const bool vec = vec_ok(4, sizeof(float), a.voices, {a.in_ld}, {a.in});
     const int vpt = vec ? 4 : 1;
     a.voice_tiles = sig_voice_tiles(a.voices, vpt);
     unsigned nwg;
@@ -182,18 +177,13 @@ extern "C" int sig_biquad_coldstart_bus(int type, int32_t rate, int64_t position
                                         double* workspace, float* out, int64_t out_ld, int32_t* status, void* stream)
 {
     SIG_CHECK_ARG(type == SIG_FILT_LOWPASS || type == SIG_FILT_HIGHPASS);
-    SIG_CHECK_ARG(rate > 0 && position >= 0 && block_frames >= 0 && nblocks >= 0 && context >= 0 && voices >= 0);
-    SIG_CHECK_ARG(cutoff && in && out && workspace && in_ld >= voices && out_ld >= bus_channels);
-    SIG_CHECK_ARG(cutoff_stride == 0 || cutoff_stride == 1);
-    SIG_CHECK_ARG(cutoff_blocks == 1 || cutoff_blocks == nblocks);
+    bool empty;
+    SIG_CHECK_ARG(window_ok(rate, position, block_frames, nblocks, context, voices, in, in_ld, in_history, out, empty));
+    SIG_CHECK_ARG(rows_ok({cutoff, cutoff_stride, cutoff_blocks}, nblocks, true) && workspace && out_ld >= bus_channels);
     SIG_CHECK_ARG(bus_gains ? bus_gains_ld >= voices : bus_channels == 1);
-    {   // the caller must have materialised min(context, position) rows in front of `in`
-        const int64_t need = position < context ? position : context;
-        SIG_CHECK_ARG(in_history >= need);
-    }
     sig_env::AdsrRows env{};
     if (adsr_params) SIG_CHECK_ARG(sig_env::load_rows(adsr_params, adsr_strides, env));
-    if (block_frames == 0 || nblocks == 0 || voices == 0) return 0;
+    if (empty) return 0;
     Args a{type, (double)rate, position, block_frames, nblocks, context, voices, cutoff, cutoff_stride, cutoff_blocks,
            in, in_ld, bus_gains, bus_gains_ld, workspace, (int64_t)block_frames * nblocks, 0, status};
     hipStream_t s = static_cast<hipStream_t>(stream);

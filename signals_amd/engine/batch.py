@@ -627,6 +627,15 @@ class _Batch:
     )
 
     # -------------------------------------------------------------- filters
+    @staticmethod
+    def _narrow(control: torch.Tensor, channels: int) -> torch.Tensor:
+        """the first `channels` columns of a filter's control rows, contiguous; narrower: the reference's IndexError (it indexes
+        crit[0, i] for every channel i, fx.py:99)"""
+        if control.shape[1] < channels:
+            raise IndexError(f'index {control.shape[1]} is out of bounds for axis 1 with size {control.shape[1]}')
+        control = control[:, :channels]
+        return control if control.is_contiguous() else control.contiguous()
+
     def _filter_window(self, node: fx.CritFilter, channels: int, cutoff: torch.Tensor | None = None):
         """(cutoff rows, input window with c0 = min(100, pos) context rows in front, c0) of a filter; `cutoff`
         defaults to the single-cutoff filters' control rows"""
@@ -644,13 +653,7 @@ class _Batch:
         window = window[have - c0:] if have != c0 else window
         if window.shape[1] < channels:
             raise IndexError(f'index {window.shape[1]} is out of bounds for axis 1 with size {window.shape[1]}')
-        if cutoff.shape[1] < channels:
-            raise IndexError(f'index {cutoff.shape[1]} is out of bounds for axis 1 with size {cutoff.shape[1]}')
-        window = window[:, :channels]
-        cutoff = cutoff[:, :channels]
-        if not cutoff.is_contiguous():
-            cutoff = cutoff.contiguous()
-        return cutoff, window, c0
+        return self._narrow(cutoff, channels), window[:, :channels], c0
 
     def _filter(self, node: fx.CritFilter, channels: int, hist: int, rows: int, envelope: dict | None = None,
                 owner_node: Emitter | None = None) -> torch.Tensor:
@@ -665,12 +668,7 @@ class _Batch:
         btype = str(node.type())
         status = o._status_word(node)
         if band:
-            high = self._control(node.high, 'high')
-            if high.shape[1] < channels:
-                raise IndexError(f'index {high.shape[1]} is out of bounds for axis 1 with size {high.shape[1]}')
-            high = high[:, :channels]
-            if not high.is_contiguous():
-                high = high.contiguous()
+            high = self._narrow(self._control(node.high, 'high'), channels)
             if cutoff.shape[0] == 1 and high.shape[0] == 1:
                 o._launch(f'band_coldstart[{btype}]',
                           lambda: _native.band_coldstart(btype, self.rate, pos, N, K, CONTEXT, cutoff, high, window, c0, main,
@@ -683,25 +681,13 @@ class _Batch:
                           units=N * K * channels)
         elif isinstance(node, ext.ResonantFilter):
             # the resonant low-pass / high-pass: a second control row, each of the two per block on its own (a swept cutoff, a swept q)
-            q = None if _ctl_unplugged(node.resonance) else self._control(node.resonance, 'resonance')
-            if q is not None:
-                if q.shape[1] < channels:
-                    raise IndexError(f'index {q.shape[1]} is out of bounds for axis 1 with size {q.shape[1]}')
-                q = q[:, :channels]
-                if not q.is_contiguous():
-                    q = q.contiguous()
+            q = None if _ctl_unplugged(node.resonance) else self._narrow(self._control(node.resonance, 'resonance'), channels)
             swept = cutoff.shape[0] > 1 or (q is not None and q.shape[0] > 1)
             if isinstance(node, ext.EqFilter):
                 # the equaliser biquads: a third control row for the three gain classes, per block on its own like the other two
                 gp = node.gain_port()
-                gain = None if gp is None or _ctl_unplugged(gp) else self._control(gp, 'gain')
-                if gain is not None:
-                    if gain.shape[1] < channels:
-                        raise IndexError(f'index {gain.shape[1]} is out of bounds for axis 1 with size {gain.shape[1]}')
-                    gain = gain[:, :channels]
-                    if not gain.is_contiguous():
-                        gain = gain.contiguous()
-                    swept = swept or gain.shape[0] > 1
+                gain = None if gp is None or _ctl_unplugged(gp) else self._narrow(self._control(gp, 'gain'), channels)
+                swept = swept or (gain is not None and gain.shape[0] > 1)
                 o._launch(f'biquad_coldstart_eq[{btype}{",blocks" if swept else ""}]',
                           lambda: _native.biquad_coldstart_eq(btype, self.rate, pos, N, K, CONTEXT, cutoff, q, gain, window, c0, main,
                                                               status=status),
