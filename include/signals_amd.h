@@ -199,6 +199,31 @@ int sig_shaper_table(int64_t rows, int32_t voices,
                      const float* table, int32_t table_points, int32_t table_waves,
                      void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Short multi-tap delay line, chain/ext.py Delay (build-defined: the reference has no node that delays a signal).  The rows are
+ * `nblocks` consecutive blocks of `block_frames` frames behind `context_rows` rows of context: `in` points at the FIRST row of that
+ * window, (context_rows + nblocks * block_frames, voices | 1) float32 or float64 (in_stride == 0: one column broadcast over the
+ * voices), whose row r is absolute frame position - context_rows + r; context_rows == min(SIG_DELAY_CONTEXT, position), like a
+ * cold-start filter's history.  x[m] = 0 for an absolute frame m < 0: such rows are not read.  `taps` rows (multiplier[u], gain[u]),
+ * 1 <= taps <= SIG_DELAY_MAX_TAPS, are HOST arrays copied into the kernel's arguments.  For block b, its row n and voice v, in f64,
+ * every operation rounded, the input widened exactly:
+ *   t   = time[b or 0, v]                                                  (seconds; NULL = unplugged = 0)
+ *   d_u = clip((t * rate) * multiplier[u], 0, SIG_DELAY_MAX_FRAMES)        (NaN stays NaN, +inf -> 99, -inf -> 0)
+ *   i_u = floor(d_u);  f_u = d_u - i_u                                     (once per block)
+ *   s_u = x[n - i_u] + f_u * (x[n - i_u - 1] - x[n - i_u])
+ *   out[n,v] = gain[0] * s_0  (+ gain[1] * s_1 + ... in ascending u)
+ * A NaN d_u makes every row of that voice in that block NaN; no index is formed from it.  `time`: f64 (1 | nblocks, voices | 1),
+ * time_blocks rows time_row_stride apart.  The float64 value in front of the store is bit-exact against numpy
+ * (tests/delay_reference.py).  float32 input is staged in LDS tiles of (SIG_DELAY_TILE_ROWS + SIG_DELAY_CONTEXT) x 64 voices with
+ * coalesced row loads; float64 input is gathered.  taps outside 1 .. 16, context_rows > SIG_DELAY_CONTEXT or != min(SIG_DELAY_CONTEXT,
+ * position), a null in / out / multiplier / gain, block_frames < 1, out_ld < voices or a stride other than 0 / 1:
+ * hipErrorInvalidValue, nothing launched; nblocks == 0 or voices == 0: no launch. */
+enum { SIG_DELAY_CONTEXT = 100, SIG_DELAY_MAX_FRAMES = 99, SIG_DELAY_MAX_TAPS = 16, SIG_DELAY_TILE_ROWS = 220 };
+int sig_delay_taps(int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context_rows, int32_t voices,
+                   const void* in, int32_t in_dtype, int64_t in_ld, int32_t in_stride,
+                   const double* time, int32_t time_stride, int64_t time_row_stride, int32_t time_blocks,
+                   int32_t taps, const double* multiplier, const double* gain,
+                   void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):

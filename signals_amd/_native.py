@@ -71,6 +71,9 @@ VP_FAMILIES = {'band': ('Band',), 'pm': ('OscPM',), 'table': VP_TABLE_OPS, 'reso
 VP_VARIANTS = ('plain', 'band', 'pm', 'table', 'shape', 'resonant', 'unison', 'blep', 'mixed')    # SIG_VP_FAMILY_*: the interpreter's variants (`voice_program_variant`)
 UNISON_MAX_COPIES = 16                      # SIG_UNISON_MAX_COPIES: copies of a unison oscillator (ext.py UnisonOsc)
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
+DELAY_CONTEXT = 100                         # SIG_DELAY_CONTEXT: the rows of context in front of a delay line's block, the filters' window
+DELAY_MAX_FRAMES = 99                       # SIG_DELAY_MAX_FRAMES: the longest delay (ext.py Delay): the context minus the one further row the interpolation reads
+DELAY_MAX_TAPS = 16                         # SIG_DELAY_MAX_TAPS: taps of a delay line
 
 
 class VpIns(ctypes.Structure):
@@ -136,6 +139,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_blep': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_osc_bank_sync': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
+        'sig_delay_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, i32, dp, dp, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_eq': cold + [dp, i32, i32] * 3 + window + [vp, i64, i32, vp, vp],
@@ -497,6 +501,38 @@ def shaper_table(x: torch.Tensor, select: torch.Tensor | None, table: torch.Tens
     _check(lib().sig_shaper_table(rows, voices, x.data_ptr(), _dt(x), 0 if x.shape[0] == 1 else x.stride(0), 0 if x.shape[1] == 1 else 1,
                                   sp, ss, srs, rows_per_select, *_table(table, pow2=False),
                                   out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_shaper_table')
+    return out
+
+
+def _taps(taps) -> tuple:
+    """(U, multipliers, gains) of a delay line's (U, 2) `taps` array: two host arrays of U doubles the launch takes by value"""
+    import numpy as np
+    c = np.asarray(taps, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= DELAY_MAX_TAPS or not np.isfinite(c).all():
+        raise NativeError(f'delay taps must be a finite (1..{DELAY_MAX_TAPS}, 2) array of (multiplier, gain) rows, got shape {c.shape}')
+    U = c.shape[0]
+    return U, (ctypes.c_double * U)(*c[:, 0].tolist()), (ctypes.c_double * U)(*c[:, 1].tolist())
+
+
+def delay_taps(rate: int, position: int, block_frames: int, nblocks: int, window: torch.Tensor, history: int,
+               time: torch.Tensor | None, taps, out: torch.Tensor) -> torch.Tensor:
+    """out[(nblocks * block_frames, voices)] <- short multi-tap delay line (sig_delay_taps; ext.py Delay): `window` holds `history` =
+    min(100, position) context rows, then one input row per row of `out`, float32 | float64 (rows, V | 1); row n of block b is
+    sum_u g_u * (x[n - i_u] + f_u * (x[n - i_u - 1] - x[n - i_u])) with d_u = clip(time[b] * rate * m_u, 0, 99) = i_u + f_u, x = 0
+    in front of absolute frame 0.  time: f64 (1 | nblocks, V | 1) seconds, None: unplugged = 0; taps: a host (U, 2) array of
+    (m_u, g_u) rows, by value."""
+    _gpu(window, time, out)
+    _audio(window, 'delay in')
+    _audio(out, 'delay out')
+    rows, voices = out.shape
+    if rows != block_frames * nblocks or window.shape[0] != history + rows or window.shape[1] not in (1, voices):
+        raise NativeError(f'delay shapes: in {tuple(window.shape)} history {history} out {tuple(out.shape)} blocks {nblocks}x{block_frames}')
+    tp, ts, trs, trows = _voice_rows(voices, (time, 'time'), form=_ctrl_rows)
+    if trows not in (1, nblocks):
+        raise NativeError(f'time has {trows} rows, launch needs 1 or {nblocks}')
+    _check(lib().sig_delay_taps(rate, position, block_frames, nblocks, history, voices,
+                                window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
+                                tp, ts, trs, trows, *_taps(taps), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_delay_taps')
     return out
 
 

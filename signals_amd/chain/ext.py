@@ -523,6 +523,82 @@ class Shaper(BlockCachingEmitter, ImplicitChannels):
         return _native.shaper_table(x, select, self.resident_table(), out)
 
 
+def _validate_taps(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and new_value.shape[1] == 2 and 1 <= new_value.shape[0] <= _native.DELAY_MAX_TAPS
+          and bool(np.isfinite(new_value).all()))
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a 2D real array (taps, 2) of finite (time multiplier, gain) rows, 1 <= taps <= '
+                            f'{_native.DELAY_MAX_TAPS}')
+
+
+class Delay(BlockCachingEmitter, ImplicitChannels):
+    """Short multi-tap delay line with linear interpolation, up to 99 frames (2 ms at 48 kHz): the flanger
+    `Mix(x, Delay(x, time=LFO))`, a feed-forward comb or a multi-tap comb series in front of a filter, a sub-2 ms stereo decorrelator in
+    front of `SumBus`, a fractional-sample phase aligner.  The state `taps` is a (U, 2) array, 1 <= U <= 16: row u holds (m_u, g_u),
+    a multiplier of `time` and a gain; the default [[1.0, 1.0]] is one tap at `time`.  Ports: `input` at frame rate; `time` (seconds)
+    at block rate, read once per block at the block's position like every control (unplugged or disabled: 0).  Per voice v and
+    block, in float64 and every operation rounded, the input widened exactly, x[m] = 0 for an absolute frame m < 0:
+        t   = time[0, v]
+        d_u = clip((t * rate) * m_u, 0, 99)                                (np.clip: NaN stays NaN, +inf -> 99, -inf -> 0)
+        i_u = floor(d_u);  f_u = d_u - i_u
+        s_u[n] = x[n - i_u] + f_u * (x[n - i_u - 1] - x[n - i_u])
+        out[n] = g_0 * s_0[n]  (+ g_1 * s_1[n] + ...  added in ascending u)
+    (kernel: sig_delay_taps; restated in numpy by tests/delay_reference.py).  A NaN d_u makes every row of that voice in that block
+    NaN; no status bit is set.  One tap (1, 1) at time = 0 is the identity, an integral d the shifted input, both bit for bit.
+    The node takes its window exactly as a filter does -- [<= 100 context rows | block | 100 rows after], the rows after discarded
+    but requested, so that upstream caches see what a filter would leave them -- and to the batched engine it IS a
+    filter: request-dependent, min(100, position) history rows, tails between batches, no batch of blocks <= 100 frames over an
+    impure input.  `input` of width 1 broadcasts; `time` or `input` narrower than the request but wider than 1 raises the IndexError
+    of a narrow `cutoff`.  Integer arrays (what a .sigs value arrives as) are converted; the taps travel by value with each launch,
+    so an in-place edit of the array or a replaced array takes effect at the next render.
+    Out of scope: delays beyond 99 frames (chorus, echo, reverb: they need a longer context than the block semantics have, and a ring
+    per lane in the voice-program machine); feedback inside the node (a truncated comb series is spelled with `taps`); a frame-rate
+    `time`; interpolation above linear; the voice program, the specialised build and the fused kernels (a graph with the node
+    renders one kernel per node); the node inside a block-rate control path (the batched engine answers NotBatchable with the reason
+    and the graph keeps the eager path, which serves frames == 1 in float64)."""
+    input: Receiver.BoundPort = port('input')
+    time: Receiver.BoundPort = port('time')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        taps: np.ndarray = attr.ib(factory=lambda: np.array([[1.0, 1.0]]), validator=_validate_taps, on_setattr=attr.setters.validate)
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.EFFECT
+
+    def context_frames(self) -> int:
+        return _native.DELAY_CONTEXT
+
+    def host_taps(self) -> np.ndarray:
+        """the (U, 2) float64 array a launch takes by value, as the state holds it now"""
+        return np.ascontiguousarray(self._state.taps, dtype=np.float64)
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        time = as_control(self.time.forward_at_block_rate(request))            # unplugged: zeros((1, 1)), no delay
+        context_frames = self.context_frames()
+        window = self.input.forward_with_context(request, context_frames)
+        loc, shape = request.loc, request.loc.shape
+        for reply in (window, time):
+            if 1 < reply.shape[1] < shape.channels:
+                raise IndexError(f'index {reply.shape[1]} is out of bounds for axis 1 with size {reply.shape[1]}')
+        history = window.shape[0] - shape.frames - context_frames             # rows the `before` request returned
+        if history != min(context_frames, loc.position):
+            raise ValueError(f'could not broadcast input array from shape ({window.shape[0] - context_frames},) '
+                             f'into shape ({shape.frames},)')
+        buf = window[:history + shape.frames, :shape.channels]
+        if buf.dtype not in (torch.float32, torch.float64):
+            buf = buf.to(result_dtype(shape.frames))
+        time = time[:, :shape.channels]
+        if not time.is_contiguous():
+            time = time.contiguous()
+        voices = max(buf.shape[1], time.shape[1])
+        out = torch.empty((shape.frames, voices), dtype=result_dtype(shape.frames), device=buf.device)
+        return _native.delay_taps(loc.rate, loc.position, shape.frames, 1, buf, history, time, self.host_taps(), out)
+
+
 class ResonantFilter(fx.CritFilter, abc.ABC):
     """Resonant 2-pole low-pass / high-pass: the bilinear transform with prewarping of the analogue second-order section with quality
     factor q -- the RBJ cookbook's low-pass / high-pass (alpha = sin(w0) / (2 q)) in another form, the reference's Butterworth

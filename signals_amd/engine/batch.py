@@ -72,6 +72,7 @@ class _Batch:
         (ext.UnisonOsc, 'a unison oscillator', 'the eager node serves one-frame requests'),
         (ext.Shaper, 'a waveshaper', 'the eager node serves one-frame requests'),
         (ext.ResonantFilter, 'a resonant filter', 'the eager node serves one-frame requests'),
+        (ext.Delay, 'a delay line', 'the eager node serves one-frame requests'),
     )
 
     def _control_node(self, src: Emitter | None, what: str) -> torch.Tensor:
@@ -156,7 +157,7 @@ class _Batch:
         self._need[key] = hist
         if not node.get_state().enabled and not isinstance(node, (ext.Tap, files.FileWriter)):
             return
-        if isinstance(node, fx.CritFilter):
+        if isinstance(node, (fx.CritFilter, ext.Delay)):
             hist = min(CONTEXT, self.pos)
         elif _modulated(node):
             hist = 0                                              # own history comes from the tail / a fresh block
@@ -275,6 +276,21 @@ class _Batch:
                   lambda: _native.shaper_table(x, select, table, main, rows_per_select=self.N if mod else 0), units=main.shape[0] * cols)
         if mod:
             self._own_history(node, cols, hist, result)
+        return result
+
+    def _sched_delay(self, node, channels, hist, rows):
+        """a delay line: the input window of a filter (c0 = min(100, pos) context rows in front; the same NotBatchable for an impure
+        input at N <= 100), one sig_delay_taps launch over the K blocks -- per-block time rows when that port is modulated -- and the
+        node's own history rows from the tail or a fresh block, like `_filter`; the taps go with the launch by value"""
+        o, N, K, pos = self.owner, self.N, self.K, self.pos
+        time, window, c0 = self._filter_window(node, channels, self._control(node.time, 'time'), narrow_ok=True)
+        taps = node.host_taps()
+        cols = max(window.shape[1], time.shape[1])
+        result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=window.device)
+        main = result[hist:]
+        o._launch(f'delay_taps[{taps.shape[0]}{",per-block" if time.shape[0] > 1 else ""}]',
+                  lambda: _native.delay_taps(self.rate, pos, N, K, window, c0, time, taps, main), units=N * K * cols)
+        self._own_history(node, cols, hist, result)
         return result
 
     def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
@@ -617,6 +633,7 @@ class _Batch:
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
         (ext.Shaper, _sched_shaper),
+        (ext.Delay, _sched_delay),
         (ext.SumBus, _sched_bus),
         (ext.Tap, _sched_tap),
         (files.FileWriter, _sched_file_writer),
@@ -636,9 +653,10 @@ class _Batch:
         control = control[:, :channels]
         return control if control.is_contiguous() else control.contiguous()
 
-    def _filter_window(self, node: fx.CritFilter, channels: int, cutoff: torch.Tensor | None = None):
+    def _filter_window(self, node: fx.CritFilter, channels: int, cutoff: torch.Tensor | None = None, narrow_ok: bool = False):
         """(cutoff rows, input window with c0 = min(100, pos) context rows in front, c0) of a filter; `cutoff`
-        defaults to the single-cutoff filters' control rows"""
+        defaults to the single-cutoff filters' control rows.  `narrow_ok` (ext.Delay): a one-column window or control row
+        broadcasts over the voices instead of raising"""
         N, K, pos = self.N, self.K, self.pos
         if cutoff is None:
             cutoff = self._control(node.cutoff, 'cutoff')
@@ -651,8 +669,10 @@ class _Batch:
         if window.shape[0] == 1:
             raise ValueError('filter input answered a single row (unplugged or disabled input)')
         window = window[have - c0:] if have != c0 else window
-        if window.shape[1] < channels:
+        if window.shape[1] < channels and not (narrow_ok and window.shape[1] == 1):
             raise IndexError(f'index {window.shape[1]} is out of bounds for axis 1 with size {window.shape[1]}')
+        if narrow_ok and cutoff.shape[1] == 1:
+            return cutoff, window[:, :channels], c0
         return self._narrow(cutoff, channels), window[:, :channels], c0
 
     def _filter(self, node: fx.CritFilter, channels: int, hist: int, rows: int, envelope: dict | None = None,

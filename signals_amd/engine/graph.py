@@ -17,7 +17,7 @@ class NotBatchable(Exception):
 
 # the node classes with a kernel schedule, one entry of _Batch._SCHEDULES each (batch.py checks that the two agree)
 _KNOWN_TYPES = (fixed.Fixed, osc.Osc, ext.PMOsc, ext.Wavetable, ext.UnisonOsc, noise.White, fx.CritFilter, fx.Mix, fx.RingMod, fx.Gain,
-                fx.Amp, ext.Shaper, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
+                fx.Amp, ext.Shaper, ext.Delay, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
 
 
 def _ctl_const(port: Receiver.BoundPort) -> bool:
@@ -45,6 +45,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.hertz, node.phase, node.spread]
     if isinstance(node, ext.Shaper):
         return [node.select]
+    if isinstance(node, ext.Delay):
+        return [node.time]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
@@ -68,7 +70,7 @@ def _audio_ports(node: Emitter) -> list:
         return [node.left, node.right]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.left]
-    if isinstance(node, (fx.CritFilter, ext.SumBus, ext.MixMatrix, ext.Tap, ext.Shaper, files.FileWriter)):
+    if isinstance(node, (fx.CritFilter, ext.SumBus, ext.MixMatrix, ext.Tap, ext.Shaper, ext.Delay, files.FileWriter)):
         return [node.input]
     if isinstance(node, shape.Merge):
         return [node.left, node.right]
@@ -98,7 +100,7 @@ def _is_pure(node: Emitter | None, memo: dict) -> bool:
         return True
     if node not in memo:
         memo[node] = True       # cycles are rejected elsewhere
-        if isinstance(node, fx.CritFilter) or _modulated(node) or _foreign(node):
+        if isinstance(node, (fx.CritFilter, ext.Delay)) or _modulated(node) or _foreign(node):    # (a delay line takes a filter's window)
             memo[node] = False
         else:
             memo[node] = all(_is_pure(p.sig, memo) for p in _audio_ports(node))
