@@ -224,6 +224,38 @@ int sig_delay_taps(int32_t rate, int64_t position, int32_t block_frames, int32_t
                    int32_t taps, const double* multiplier, const double* gain,
                    void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Sample playback, chain/ext.py Sampler (build-defined: the reference streams a file linearly and has no pitch, trigger or per-voice
+ * start).  `table` float32 in device memory, COLUMN-major: table_waves recordings of table_frames frames, recording w contiguous at
+ * table + w * table_frames (the transpose of the node's (T, W) state); T >= 2, W >= 1, T * W <= SIG_SAMPLER_MAX_POINTS.  loop_end == 0:
+ * no loop, else 0 <= loop_start < loop_end <= T.  Rows, strides, `position_step` and `rows_per_param` as sig_osc_bank_table takes them:
+ * output row r is absolute frame n = position + r * position_step and reads control row r / rows_per_param (0: one row for the whole
+ * launch); ratio, offset, gate_on, select: f64 (1 | P, voices | 1), NULL = unplugged = 0.  A pure function of n, no carried read
+ * pointer; per voice v, in f64, every operation rounded, tbl = (double) table:
+ *   q = n / rate;  e = q - gate_on[v];  s = e * rate;  u = s * ratio[v] + offset[v]
+ *   not (e >= 0)          -> out = 0                                       (before the trigger; a NaN gate is silence)
+ *   u is NaN or +-inf     -> out = NaN                                     (no index is formed from it)
+ *   no loop:  u < 0 or u > T - 1 -> out = 0;  i = floor(u); f = u - i; j = min(i + 1, T - 1)
+ *   loop:     u < 0 -> out = 0;  L = loop_end - loop_start
+ *             u >= loop_end:  c = floor((u - loop_start) / L);  u = (u - loop_start) - c * L + loop_start
+ *                             if that rounds to u >= loop_end:  u = loop_start
+ *                             (likewise if it falls below loop_start: from 2^53 frames on the rounded quotient can exceed the true one)
+ *             i = floor(u); f = u - i; j = (i + 1 >= loop_end) ? loop_start : i + 1
+ *   w = clip(floor(select[v]), 0, W - 1)                                   (NaN -> 0)
+ *   out[n,v] = tbl[i, w] + f * (tbl[j, w] - tbl[i, w])
+ * The float64 value in front of the store is bit-exact against numpy (tests/sampler_reference.py); no status word.  Lanes own voices
+ * and gather from the table in HBM (no LDS).  A null table or out, T < 2, W < 1, T * W over the cap, loop bounds outside the rule,
+ * out_ld < voices or a stride other than 0 / 1: hipErrorInvalidValue, nothing launched; rows == 0 or voices == 0: no launch. */
+enum { SIG_SAMPLER_MAX_POINTS = 1 << 26 };
+int sig_sampler_play(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                     int32_t voices, int32_t rows_per_param,
+                     const double* ratio, int32_t ratio_stride, int64_t ratio_row_stride,
+                     const double* offset, int32_t offset_stride, int64_t offset_row_stride,
+                     const double* gate_on, int32_t gate_on_stride, int64_t gate_on_row_stride,
+                     const double* select, int32_t select_stride, int64_t select_row_stride,
+                     const float* table, int32_t table_frames, int32_t table_waves,
+                     int32_t loop_start, int32_t loop_end,
+                     void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):

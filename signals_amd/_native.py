@@ -74,6 +74,7 @@ TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a
 DELAY_CONTEXT = 100                         # SIG_DELAY_CONTEXT: the rows of context in front of a delay line's block, the filters' window
 DELAY_MAX_FRAMES = 99                       # SIG_DELAY_MAX_FRAMES: the longest delay (ext.py Delay): the context minus the one further row the interpolation reads
 DELAY_MAX_TAPS = 16                         # SIG_DELAY_MAX_TAPS: taps of a delay line
+SAMPLER_MAX_POINTS = 1 << 26                # SIG_SAMPLER_MAX_POINTS: frames x recordings of a sampler's table (ext.py Sampler), resident in HBM
 
 
 class VpIns(ctypes.Structure):
@@ -140,6 +141,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_sync': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_delay_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, i32, dp, dp, vp, i32, i64, vp],
+        'sig_sampler_play': [i64, i64, i32, i64, i32, i32] + [dp, i32, i64] * 4 + [vp, i32, i32, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_eq': cold + [dp, i32, i32] * 3 + window + [vp, i64, i32, vp, vp],
@@ -533,6 +535,26 @@ def delay_taps(rate: int, position: int, block_frames: int, nblocks: int, window
     _check(lib().sig_delay_taps(rate, position, block_frames, nblocks, history, voices,
                                 window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
                                 tp, ts, trs, trows, *_taps(taps), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_delay_taps')
+    return out
+
+
+def sampler_play(position: int, rate: int, ratio: torch.Tensor | None, offset: torch.Tensor | None, gate_on: torch.Tensor | None,
+                 select: torch.Tensor | None, table: torch.Tensor, loop_start: int, loop_end: int, out: torch.Tensor,
+                 step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- sample playback (sig_sampler_play; ext.py Sampler): row r is absolute frame n = position + r * step, read
+    at u = ((n / rate - gate_on) * rate) * ratio + offset with linear interpolation, silence before the trigger and outside the
+    recording, the loop [loop_start, loop_end) wrapped when loop_end != 0.  `table`: the device copy, float32 (W, T) contiguous -- W
+    recordings of T frames, each contiguous (the transpose of the node's state).  ratio / offset / gate_on / select: (1|P, V|1) f64
+    like `osc_bank`, None: unplugged = 0."""
+    named = ((ratio, 'ratio'), (offset, 'offset'), (gate_on, 'gate_on'), (select, 'select'))
+    if table is None or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise NativeError('a sampler table is a contiguous float32 (recordings, frames) tensor')
+    waves, frames = table.shape
+    if frames < 2 or waves < 1 or frames * waves > SAMPLER_MAX_POINTS:
+        raise NativeError(f'sampler table of {frames} frames x {waves} recordings: frames >= 2, frames * recordings <= {SAMPLER_MAX_POINTS}')
+    head, rows, tail = _osc_launch(out, position, step, rate, rows_per_param, *named, also=(table,))
+    _check(lib().sig_sampler_play(*head, *(x for row in rows for x in row), table.data_ptr(), frames, waves, loop_start, loop_end, *tail),
+           'sig_sampler_play')
     return out
 
 

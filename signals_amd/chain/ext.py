@@ -599,6 +599,134 @@ class Delay(BlockCachingEmitter, ImplicitChannels):
         return _native.delay_taps(loc.rate, loc.position, shape.frames, 1, buf, history, time, self.host_taps(), out)
 
 
+def _validate_recordings(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and new_value.shape[0] >= 2 and new_value.shape[1] >= 1
+          and new_value.shape[0] * new_value.shape[1] <= _native.SAMPLER_MAX_POINTS)
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a 2D real array (frames, recordings), frames >= 2, frames * recordings <= '
+                            f'{_native.SAMPLER_MAX_POINTS}')
+
+
+def _validate_loop(instance, attribute, new_value):
+    """what the state alone decides: an integer >= 0, and loop_start < loop_end where a loop is on.  The table's length is checked at
+    every render: the table may be set after the bounds (a patch sets its properties in the order written) or replaced later."""
+    if isinstance(new_value, (bool, np.bool_)) or not isinstance(new_value, (int, np.integer)) or new_value < 0:
+        raise BadStateValue(instance, attribute.name, new_value, 'must be an integer >= 0, in frames')
+    start = new_value if attribute.name == 'loop_start' else getattr(instance, 'loop_start', 0)
+    end = new_value if attribute.name == 'loop_end' else getattr(instance, 'loop_end', 0)
+    if end != 0 and not start < end:
+        raise BadStateValue(instance, attribute.name, new_value, f'a loop needs loop_start < loop_end, got {start} and {end}')
+
+
+class Sampler(BlockCachingEmitter, ImplicitChannels):
+    """Sample playback: the state `table` holds W recordings of T frames each as a (T, W) array (the reference's (frames, channels)
+    orientation), recorded at the graph's rate; every voice plays one of them from a trigger time, at its own speed and start, with
+    linear interpolation -- a drum hit per voice, a multisample transposed per voice, a looped pad.  Ports, all at block rate and read
+    once per block at the block's position like every control: `ratio` (playback speed, 1 = the original; unplugged reads zeros like
+    every port, so set it), `offset` (frames into the recording at the trigger), `gate_on` (seconds, ADSR's meaning), `select` (the
+    column: w = clip(floor(select), 0, W - 1), NaN and unplugged = 0, Wavetable's rule).  State: `table`, T >= 2, W >= 1, T * W <=
+    2**26, integer arrays (what a .sigs value arrives as) are converted, the device copy is float32 and follows in-place edits and
+    replacement; `loop_start`, `loop_end` in frames, loop_end == 0 (the default) = no loop, else 0 <= loop_start < loop_end <= T
+    (the order is checked on set, the table's length at every render, where it raises BadStateValue: the table may have been
+    replaced).  The node is a pure function of the absolute frame, like `osc.Osc`, `ext.ADSR` and `ext.SyncOsc`: no carried read
+    pointer, so a block-rate change of `ratio` moves the read position exactly as a block-rate change of `hertz` moves an oscillator's
+    phase -- and it needs no context rows, no history and no tails, and renders from any position.  For absolute frame n and voice v,
+    in float64 and every operation rounded, no fused multiply-add, tbl = float32(table) widened to float64:
+        q  = n / rate                                  (osc.py's order: one IEEE divide)
+        e  = q - gate_on[v]
+        s  = e * rate
+        u  = s * ratio[v] + offset[v]                  (two roundings)
+        not (e >= 0)           -> out = 0              (before the trigger; a NaN gate is silence)
+        u is NaN or +-inf      -> out = NaN            (no index is formed from it)
+        no loop:  u < 0 or u > T - 1 -> out = 0        (outside the recording)
+                  i = floor(u); f = u - i; j = min(i + 1, T - 1)
+        loop:     u < 0 -> out = 0
+                  L = loop_end - loop_start
+                  u >= loop_end:  c = floor((u - loop_start) / L);  u = (u - loop_start) - c * L + loop_start
+                                  if that rounds to u >= loop_end:  u = loop_start
+                                  (likewise if it falls below loop_start: from 2**53 frames on the rounded quotient can exceed the true one)
+                  i = floor(u); f = u - i; j = (i + 1 >= loop_end) ? loop_start : i + 1
+        out = tbl[i, w] + f * (tbl[j, w] - tbl[i, w])
+    (kernel: sig_sampler_play; restated in numpy by tests/sampler_reference.py).  The rows are float32, a one-frame request float64;
+    no status bit is set for any input.  The width is the broadcast of the four control rows; a control narrower than the request but
+    wider than 1 raises the IndexError of a narrow `cutoff`.  Amplitude shaping and release are not the node's job:
+    `RingMod(Sampler, ADSR)` with the same `gate_on` does them.  `Sampler.table_from_wav(path)` reads a WAV file into a table.
+    Out of scope: a carried read pointer (varispeed without jumps); a frame-rate `ratio`; interpolation above linear, and
+    anti-aliasing when ratio > 1; a recording rate other than the graph's (fold it into `ratio`); reverse loops and crossfades; the
+    voice program, the specialised build and the fused kernels (a graph with the node renders one kernel per node); the node inside a
+    block-rate control path (the batched engine answers NotBatchable with the reason and the graph keeps the eager path, which serves
+    frames == 1 in float64)."""
+    ratio: Receiver.BoundPort = port('ratio')
+    offset: Receiver.BoundPort = port('offset')
+    gate_on: Receiver.BoundPort = port('gate_on')
+    select: Receiver.BoundPort = port('select')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        table: np.ndarray = attr.ib(factory=lambda: np.array([[0.0], [0.0]]), validator=_validate_recordings,
+                                    on_setattr=attr.setters.validate)
+        loop_start: int = attr.ib(default=0, validator=_validate_loop, on_setattr=attr.setters.validate)
+        loop_end: int = attr.ib(default=0, validator=_validate_loop, on_setattr=attr.setters.validate)
+
+    def __init__(self):
+        super().__init__()
+        self._resident = None
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR | SignalFlags.EPOCH
+
+    @staticmethod
+    def table_from_wav(path) -> np.ndarray:
+        """the (T, W) float64 array of a WAV file (PCM_16 or FLOAT, chain/files.py's reader): W = the file's channels.  Host only; the
+        file's rate is not looked at -- fold a rate other than the graph's into `ratio`"""
+        import pathlib
+        from signals_amd.chain import files
+        wav = files._WaveFile(pathlib.Path(path), 'r')
+        try:
+            return np.ascontiguousarray(wav.read(0, wav.frames), dtype=np.float64)
+        finally:
+            wav.close()
+
+    def loop(self) -> tuple[int, int]:
+        """(loop_start, loop_end) checked against the table as it is now: BadStateValue where they no longer fit it"""
+        s = self._state
+        start, end, frames = int(s.loop_start), int(s.loop_end), s.table.shape[0]
+        if end != 0 and not 0 <= start < end <= frames:
+            raise BadStateValue(s, 'loop_end', end, f'a loop needs 0 <= loop_start < loop_end <= {frames} frames, got {start} and {end}')
+        return start, end
+
+    def resident_table(self) -> torch.Tensor:
+        """the device copy: float32 (W, T), every recording contiguous -- the transpose of the state's array"""
+        table = self._state.table
+        held = self._resident
+        if held is None or held[0] is not table or not held[1].matches(table):
+            host = np.ascontiguousarray(np.asarray(table, dtype=np.float32).T)
+            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
+        return held[2]
+
+    def control_rows(self, fetch, channels: int) -> list:
+        """the four control rows (ratio, offset, gate_on, select) as contiguous float64 rows at most `channels` wide"""
+        rows = []
+        for bound in (self.ratio, self.offset, self.gate_on, self.select):
+            row = as_control(fetch(bound))
+            if 1 < row.shape[1] < channels:
+                raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
+            row = row[:, :channels]
+            rows.append(row if row.is_contiguous() else row.contiguous())
+        return rows
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        loc = request.loc
+        rows = self.control_rows(lambda bound: bound.forward_at_block_rate(request), loc.shape.channels)
+        frames, voices = broadcast_shape((loc.shape.frames, 1), *(r.shape for r in rows))
+        start, end = self.loop()
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=rows[0].device)
+        return _native.sampler_play(loc.position, loc.rate, *rows, self.resident_table(), start, end, out)
+
+
 class ResonantFilter(fx.CritFilter, abc.ABC):
     """Resonant 2-pole low-pass / high-pass: the bilinear transform with prewarping of the analogue second-order section with quality
     factor q -- the RBJ cookbook's low-pass / high-pass (alpha = sin(w0) / (2 q)) in another form, the reference's Butterworth

@@ -73,6 +73,7 @@ class _Batch:
         (ext.Shaper, 'a waveshaper', 'the eager node serves one-frame requests'),
         (ext.ResonantFilter, 'a resonant filter', 'the eager node serves one-frame requests'),
         (ext.Delay, 'a delay line', 'the eager node serves one-frame requests'),
+        (ext.Sampler, 'a sampler', 'the eager node serves one-frame requests'),
     )
 
     def _control_node(self, src: Emitter | None, what: str) -> torch.Tensor:
@@ -292,6 +293,16 @@ class _Batch:
                   lambda: _native.delay_taps(self.rate, pos, N, K, window, c0, time, taps, main), units=N * K * cols)
         self._own_history(node, cols, hist, result)
         return result
+
+    def _sched_sampler(self, node, channels, hist, rows):
+        """a sampler: one sig_sampler_play launch, a pure function of the absolute frame like an oscillator -- per-block ratio / offset /
+        gate_on / select rows when one is modulated; the table is the node's resident copy, the loop checked against it now"""
+        operands = node.control_rows(lambda bound: self._control(bound, bound.name), channels)
+        table, (start, end) = node.resident_table(), node.loop()
+
+        def play(kind, position, rate, ratio, offset, gate_on, select, out, **kw):
+            return _native.sampler_play(position, rate, ratio, offset, gate_on, select, table, start, end, out, **kw)
+        return self._osc_launch(node, 'sampler_play', play, operands, hist, rows, kind='Loop' if end else 'OneShot')
 
     def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
         """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
@@ -634,6 +645,7 @@ class _Batch:
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
         (ext.Shaper, _sched_shaper),
         (ext.Delay, _sched_delay),
+        (ext.Sampler, _sched_sampler),
         (ext.SumBus, _sched_bus),
         (ext.Tap, _sched_tap),
         (files.FileWriter, _sched_file_writer),

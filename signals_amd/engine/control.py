@@ -155,6 +155,9 @@ class _ControlProgram:
         elif isinstance(src, ext.Delay):
             raise NotBatchable(f'{src.cls_name()} in a control path: a delay line has no block-rate program '
                                f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.Sampler):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a sampler has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
         elif isinstance(src, ext.PMOsc) and window:
             raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
                                f'window-rate program')

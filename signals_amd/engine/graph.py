@@ -17,7 +17,7 @@ class NotBatchable(Exception):
 
 # the node classes with a kernel schedule, one entry of _Batch._SCHEDULES each (batch.py checks that the two agree)
 _KNOWN_TYPES = (fixed.Fixed, osc.Osc, ext.PMOsc, ext.Wavetable, ext.UnisonOsc, noise.White, fx.CritFilter, fx.Mix, fx.RingMod, fx.Gain,
-                fx.Amp, ext.Shaper, ext.Delay, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
+                fx.Amp, ext.Shaper, ext.Delay, ext.Sampler, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
 
 
 def _ctl_const(port: Receiver.BoundPort) -> bool:
@@ -47,6 +47,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.select]
     if isinstance(node, ext.Delay):
         return [node.time]
+    if isinstance(node, ext.Sampler):
+        return [node.ratio, node.offset, node.gate_on, node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
