@@ -289,10 +289,35 @@ class _Batch:
         cols = max(window.shape[1], time.shape[1])
         result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=window.device)
         main = result[hist:]
-        o._launch(f'delay_taps[{taps.shape[0]}{",per-block" if time.shape[0] > 1 else ""}]',
-                  lambda: _native.delay_taps(self.rate, pos, N, K, window, c0, time, taps, main), units=N * K * cols)
+        if window.shape[1] < channels and not _is_pure(node.input.sig, self._pure):
+            self._delay_uncached(node, channels, window[c0:], time, taps, main)
+        else:
+            o._launch(f'delay_taps[{taps.shape[0]}{",per-block" if time.shape[0] > 1 else ""}]',
+                      lambda: _native.delay_taps(self.rate, pos, N, K, window, c0, time, taps, main), units=N * K * cols)
         self._own_history(node, cols, hist, result)
         return result
+
+    def _delay_uncached(self, node, channels, blocks, time, taps, main):
+        """a Delay over a request-dependent input that answers ONE column to a wider request.  The block cache files a reply under the
+        reply's own shape (chain/cache.py: _write_block_cache), so such a reply never serves a later request of the asked width, neither
+        as an exact hit nor as a containing block: the eager path evaluates every `before` request [p - c, p) afresh, with the input's
+        controls read at p - c -- not the rows the block in front holds, whose controls were read at p - N.  So every block takes its
+        context rows from the input rendered as a block of its own (what `_own_history` does in front of a fresh batch), one launch per
+        block.  (A filter never gets here: it raises the reference's IndexError on a one-column input.)"""
+        o, N = self.owner, self.N
+        for b in range(self.K):
+            p = self.pos + b * N
+            c = min(CONTEXT, p)
+            window = blocks[b * N:(b + 1) * N]
+            if c:
+                sub = _Batch(o, p - c, c, 1, False)
+                sub.history_of = p
+                front = sub.buffer(node.input.sig, channels, 0)[:, :window.shape[1]]      # (a voice program stores its one column V times)
+                window = torch.cat((front.to(window.dtype), window))
+            row = time if time.shape[0] == 1 else time[b:b + 1]
+            out = main[b * N:(b + 1) * N]
+            o._launch(f'delay_taps[{taps.shape[0]},uncached-input]',
+                      lambda: _native.delay_taps(self.rate, p, N, 1, window, c, row, taps, out), units=N * out.shape[1])
 
     def _sched_sampler(self, node, channels, hist, rows):
         """a sampler: one sig_sampler_play launch, a pure function of the absolute frame like an oscillator -- per-block ratio / offset /

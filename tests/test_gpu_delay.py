@@ -199,6 +199,16 @@ def graph(which, p):
     if which == 'over_lowpass':
         f = fx.LowPass(); f.input = saw(); f.cutoff = fix(p['cut'])
         return delay_node(f, p['time'], COMB), RD(R.Filter('lp', rsaw(), R.Fixed(p['cut'])), R.Fixed(p['time']), COMB), GV
+    if which == 'narrow_swept':
+        # ONE column: a Sine whose hertz follows a block-rate LFO (440 +- 60 Hz), into a Delay with per-voice time rows
+        def hertz():
+            g = fx.Gain(); g.left = mkosc('Triangle', [[7.0]]); g.right = fix([[120.0]])
+            m = fx.Mix(); m.left = g; m.right = fix([[880.0]]); m.mix = fix([[0.5]])
+            return m
+        from signals_amd.chain import osc
+        src = osc.Sine(); src.hertz = hertz()
+        rhertz = R.Binary('Mix', R.Binary('Gain', R.Osc('Triangle', R.Fixed([[7.0]])), R.Fixed([[120.0]])), R.Fixed([[880.0]]), R.Fixed([[0.5]]))
+        return delay_node(src, p['time'], COMB), RD(R.Osc('Sine', rhertz), R.Fixed(p['time']), COMB), GV
     if which == 'twice':
         return (delay_node(delay_node(saw(), p['time']), p['time2'], COMB),
                 RD(RD(rsaw(), R.Fixed(p['time'])), R.Fixed(p['time2']), COMB), GV)
@@ -271,6 +281,27 @@ def test_a_fresh_batch_at_position_4096_takes_the_own_history_path(which):
     want = R.render_stream(ref, pos, N, GK, C)
     eager = eager_rows(graph(which, p)[0], C, pos, N, GK)
     check_routes(which, p, eager, want, pos, N, (GK,))
+
+
+@pytest.mark.parametrize('pos,N,ks', [(0, 128, (3, 3)), (4096, 256, (3,)), (37, 128, (2, 1))])
+def test_a_one_column_swept_input_is_evaluated_afresh_for_every_context_request(pos, N, ks):
+    """Delay(Sine with its hertz on a block-rate LFO, ONE column; time per voice), the reduced form of the random graphs that found it
+    (tests/test_gpu_random_ext_graphs.py, seed 0 among 17).  The block cache files a reply under the reply's own shape, so a one-column
+    reply never serves a later request of the asked width: the eager path (and the oracle) evaluates the Delay's `before` request
+    [p - 100, p) afresh, hertz read at p - 100, where the batched engine took the last rows of the block in front, hertz read at p - N:
+    off by 1e-2 from the second block of a batch on.  Continuing batches, a fresh start mid-stream and one with fewer than 100 rows"""
+    from oracle import chain_ref as R
+    p = draw()
+    top, ref, C = graph('narrow_swept', p)
+    want = R.render_stream(ref, pos, N, sum(ks), C)
+    eager = eager_rows(graph('narrow_swept', p)[0], C, pos, N, sum(ks))
+    check_routes('narrow_swept', p, eager, want, pos, N, ks)
+    # not vacuous: the second block's context rows with hertz read at their own position, and as the block in front holds them
+    hertz = graph('narrow_swept', p)[1].inputs['input'].inputs['hertz']
+    first = pos + N - 100
+    fresh = R.osc('Sine', first, 100, RATE, R.render(hertz, first, 1, 1))
+    stale = R.osc('Sine', first, 100, RATE, R.render(hertz, pos, 1, 1))
+    assert maxerr(fresh, stale) > 1e-3
 
 
 def test_short_blocks_over_an_impure_input_render_eagerly():
