@@ -154,7 +154,8 @@ template <int C, bool GAINS>
 bool launch_bus_fast(int64_t rows, int voices, const float* x, int64_t ld, const double* gains, int64_t gld,
                      void* out, int64_t out_ld, int out_f64, hipStream_t stream)
 {
-    if (voices % 256 || voices > 1024 || ld % 4 || reinterpret_cast<uintptr_t>(x) % 16) return false;
+    // (no voices: declined, so that the generic kernel writes the zeros -- there is no CHUNKS = 0 kernel below)
+    if (voices == 0 || voices % 256 || voices > 1024 || ld % 4 || reinterpret_cast<uintptr_t>(x) % 16) return false;
     const int64_t groups = (rows + kFastRows - 1) / kFastRows;
     int64_t nwg = (groups + 3) / 4;
     if (nwg > 256 * 8) nwg = 256 * 8;
