@@ -42,7 +42,9 @@ enum { SIG_FILT_LOWPASS = 0, SIG_FILT_HIGHPASS = 1, SIG_FILT_BANDPASS = 2, SIG_F
        /* the RBJ equaliser biquads of chain/ext.py EqFilter: sig_biquad_coldstart_eq's types, and the filter slots of a voice program
         * that a FILTEREQ word runs */
        SIG_FILT_EQ_BANDPASS = 6, SIG_FILT_EQ_NOTCH = 7, SIG_FILT_EQ_ALLPASS = 8, SIG_FILT_EQ_PEAKING = 9, SIG_FILT_EQ_LOWSHELF = 10,
-       SIG_FILT_EQ_HIGHSHELF = 11 };
+       SIG_FILT_EQ_HIGHSHELF = 11,
+       /* the 4-pole ladder of chain/ext.py Ladder: the node's own type, run by sig_ladder_coldstart alone */
+       SIG_FILT_LADDER = 12 };
 
 /* element-wise effects: fx.py:35-60 */
 enum { SIG_EW_GAIN = 0, SIG_EW_MIX = 1, SIG_EW_RINGMOD = 2, SIG_EW_AMP = 3 };
@@ -318,6 +320,32 @@ int sig_biquad_coldstart_eq(int type, int32_t rate, int64_t position,
                             const void* in, int64_t in_ld, int64_t in_history,
                             void* out, int64_t out_ld, int32_t dtype,
                             int32_t* status, void* stream);
+
+/* The 4-pole ladder low-pass of chain/ext.py Ladder (build-defined: every other filter here is a linear biquad): four trapezoidal
+ * one-pole low-passes in series, the resonance k fed back around all four with the zero-delay loop solved in closed form, a tanh
+ * saturator of drive d at the loop's summing point.  Per voice and block, in f64, states s1..s4 = 0 at the window's first row:
+ *   wn = clip(cutoff / (rate / 2), 0, 1);  g = tan(pi wn / 2);  G = g / (1 + g);  H = 1 - G
+ *   k = clip(resonance, 0, 4);  d = max(drive, 0);  c = 1 / (1 + k ((G G) (G G)))
+ *   per row:  S = H (((s1 G + s2) G + s3) G + s4);  u = (x - k S) c;  if d > 0: u = tanh(d u) / d
+ *             for j = 1..4:  v = (u - s_j) G;  y_j = v + s_j;  s_j = y_j + v;  u = y_j
+ *             out = y_poles
+ * (tests/ladder_reference.py restates it), with the buffers, the window [<= context rows | block] and the block semantics of
+ * sig_biquad_coldstart.  cutoff, resonance, drive: f64 (blocks, voices | 1) contiguous rows, blocks in {1, nblocks} each on its
+ * own, stride 0 / 1; resonance or drive NULL: unplugged = 0 (no feedback; a linear loop -- a NULL drive launches a kernel without
+ * tanh; their strides and row counts are still checked).  A cutoff outside (0, rate / 2) or NaN sets SIG_STATUS_BAD_CUTOFF, a k that
+ * is NaN or +-inf SIG_STATUS_BAD_RESONANCE, and that voice's rows (of that block) are NaN; a drive that is NaN or +inf gives NaN rows
+ * and no status bit; voices past `voices` never set a bit.  poles in 1 .. 4: the output tap, 6 / 12 / 18 / 24 dB per octave, one for
+ * the launch.  No filter type argument: the node's type is SIG_FILT_LADDER, which no other entry accepts.  Argument errors:
+ * hipErrorInvalidValue, nothing launched; a launch with nothing to render is a success. */
+int sig_ladder_coldstart(int32_t rate, int64_t position,
+                         int32_t block_frames, int32_t nblocks, int32_t context, int32_t voices,
+                         const double* cutoff, int32_t cutoff_stride, int32_t cutoff_blocks,
+                         const double* resonance, int32_t resonance_stride, int32_t resonance_blocks,
+                         const double* drive, int32_t drive_stride, int32_t drive_blocks,
+                         int32_t poles,
+                         const void* in, int64_t in_ld, int64_t in_history,
+                         void* out, int64_t out_ld, int32_t dtype,
+                         int32_t* status, void* stream);
 
 /* sig_biquad_coldstart whose stored rows are multiplied by a per-voice ADSR envelope evaluated at the row's
  * time (f32 buffers): RingMod(Filter(x), ADSR) -- fx.py:43-46 over fx.py:85-121 and the envelope of sig_adsr --

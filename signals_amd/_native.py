@@ -18,7 +18,8 @@ LIB_PATH = pathlib.Path(os.environ.get('SIG_LIB_PATH') or pathlib.Path(__file__)
 F32, F64 = 0, 1
 OSC_KINDS = {'Sine': 0, 'Square': 1, 'Sawtooth': 2, 'Triangle': 3}
 FILT_TYPES = {'lp': 0, 'hp': 1, 'bp': 2, 'bs': 3, 'rlp': 4, 'rhp': 5,     # rlp / rhp: a voice program's resonant slots (SIG_FILT_RES_*)
-              'eqbp': 6, 'eqnotch': 7, 'eqap': 8, 'eqpeak': 9, 'eqls': 10, 'eqhs': 11}    # SIG_FILT_EQ_*: the equaliser biquads (chain/ext.py EqFilter)
+              'eqbp': 6, 'eqnotch': 7, 'eqap': 8, 'eqpeak': 9, 'eqls': 10, 'eqhs': 11,    # SIG_FILT_EQ_*: the equaliser biquads (chain/ext.py EqFilter)
+              'ladder': 12}                 # SIG_FILT_LADDER: the 4-pole ladder (chain/ext.py Ladder), run by sig_ladder_coldstart alone
 EQ_GAIN_TYPES = ('eqpeak', 'eqls', 'eqhs')  # the equaliser types that read a gain
 EW_OPS = {'Gain': 0, 'Mix': 1, 'RingMod': 2, 'Amp': 3}
 STATUS_BAD_CUTOFF = 1
@@ -145,6 +146,7 @@ def _argtypes() -> dict:
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_eq': cold + [dp, i32, i32] * 3 + window + [vp, i64, i32, vp, vp],
+        'sig_ladder_coldstart': cold[1:] + [dp, i32, i32] * 3 + [i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_env': cold + [dp, i32, i32] + env + window + out,
         'sig_biquad_coldstart_bus': cold + [dp, i32, i32] + env + window + bus + out,
         'sig_band_coldstart': cold + [dp, i32, dp, i32] + window + [vp, i64, i32, vp, vp],
@@ -621,6 +623,22 @@ def biquad_coldstart_eq(btype: str, rate: int, position: int, block_frames: int,
     g = _optional_rows(gain, 'gain', nblocks, voices)
     _check(lib().sig_biquad_coldstart_eq(FILT_TYPES[btype], *head, *_block_rows(cutoff, 'cutoff', nblocks, voices), *q, *g,
                                          *window, *dst, _dt(out), *tail), 'sig_biquad_coldstart_eq')
+    return out
+
+
+def ladder_coldstart(rate: int, position: int, block_frames: int, nblocks: int, context: int, cutoff: torch.Tensor,
+                     resonance: torch.Tensor | None, drive: torch.Tensor | None, poles: int, buf: torch.Tensor, history: int,
+                     out: torch.Tensor, status: torch.Tensor | None = None) -> torch.Tensor:
+    """the 4-pole ladder low-pass (sig_ladder_coldstart; chain/ext.py Ladder), buffers and blocks as `biquad_coldstart_q`.
+    cutoff: f64 (1|nblocks, V); resonance (the feedback k, clipped to 0 .. 4) and drive (the saturator's, max(drive, 0)): f64
+    (1|nblocks, V|1), each per block on its own; None: unplugged = 0 -- no feedback, and for drive the kernel without tanh.
+    poles: 1 .. 4, the output tap."""
+    voices, head, window, dst, tail = _coldstart_launch('ladder', rate, position, block_frames, nblocks, context, buf, history, out, status,
+                                                cutoff, resonance, drive)
+    k = _optional_rows(resonance, 'resonance', nblocks, voices)
+    d = _optional_rows(drive, 'drive', nblocks, voices)
+    _check(lib().sig_ladder_coldstart(*head, *_block_rows(cutoff, 'cutoff', nblocks, voices), *k, *d, int(poles),
+                                      *window, *dst, _dt(out), *tail), 'sig_ladder_coldstart')
     return out
 
 

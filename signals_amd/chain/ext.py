@@ -893,6 +893,87 @@ class HighShelf(GainEqFilter):
         return self.Type.high_shelf
 
 
+def _validate_poles(instance, attribute, new_value):
+    if isinstance(new_value, (bool, np.bool_)) or not isinstance(new_value, (int, np.integer)) or not 1 <= new_value <= 4:
+        raise BadStateValue(instance, attribute.name, new_value, 'must be an integer 1, 2, 3 or 4: the output tap, 6 dB/oct per pole')
+
+
+class Ladder(fx.CritFilter):
+    """4-pole transistor-ladder low-pass, 24 dB/oct: four one-pole low-passes in series with the resonance fed back around all four, up
+    to self-oscillation, and a saturator in the loop -- the synthesiser filter, which two `ResonantLowPass` in series are not (they give
+    the slope, neither the global feedback nor the drive).  Ports: `input` at frame rate; `cutoff` (Hz), `resonance` (the feedback k,
+    dimensionless) and `drive` at block rate, read once per block at the block's position like every control.  State: `poles` in
+    {1, 2, 3, 4}, default 4, the output tap: 6, 12, 18 or 24 dB/oct (validated on set).  Per voice and block, in float64, the input
+    widened exactly, the states s1..s4 = 0 at the window's first row:
+        wn = clip(cutoff / (rate / 2), 0, 1)                                (as fx.py:99-102; an error unless 0 < wn < 1, NaN too)
+        g  = tan(pi * wn / 2);  G = g / (1 + g);  H = 1 - G
+        k  = clip(resonance, 0, 4)
+        d  = max(drive, 0)
+        c  = 1 / (1 + k * ((G*G) * (G*G)))
+        per row:
+            S = H * (((s1*G + s2)*G + s3)*G + s4)                           (what the four states put on the output with zero input)
+            u = (x - k*S) * c                                               (the zero-delay feedback loop solved in closed form)
+            if d > 0:  u = tanh(d*u) / d                                    (the saturator at the loop's summing point)
+            for j = 1..4:  v = (u - s_j)*G;  y_j = v + s_j;  s_j = y_j + v;  u = y_j
+            out = y_poles
+    -- the trapezoidal ("TPT") one-pole, four in series, the linear feedback resolved without a unit delay, the non-linearity applied
+    after the solve -- over `CritFilter._filter`'s window: zero state over [<= 100 context rows | block] (kernel: sig_ladder_coldstart,
+    which multiplies by a rounded 1 / d where this divides; restated in numpy by tests/ladder_reference.py).  At k = 0, d = 0 it is four
+    bilinear one-pole low-passes; the DC gain is 1 / (1 + k); k = 4 is the edge of self-oscillation; the saturator bounds the loop's
+    input by 1 / d.
+    The controls' edges: an unplugged or disabled `resonance` or `drive` answers the ordinary zeros((1, 1)) of an unplugged port -- no
+    feedback, a linear loop (and a kernel without tanh).  k above 4 is 4, below 0 is 0; a k that is NaN or +-inf is an error like a bad
+    cutoff: the voice's rows are NaN and `runtime.check_status()` raises the resonant filters' ValueError (SIG_STATUS_BAD_RESONANCE).
+    A negative drive (-inf too) is 0; a drive that is NaN or +inf makes the voice's rows NaN and sets no status bit.  `input` of width
+    1 broadcasts over the request's channels (wider than 1 but narrower than the request it raises); a plugged `resonance` or `drive`
+    narrower than the request raises the IndexError of a narrow `cutoff`, as on `ResonantFilter`.
+    Not an `ext.ResonantFilter`, an `fx.SingleCritFilter` or an `fx.DoubleCritFilter`: to the voice program and the fused matchers
+    those mean a biquad.  Its type is its own (`Ladder.Type.ladder`, _native.FILT_TYPES['ladder']).  To the batched engine it is a
+    filter: request-dependent, min(100, position) history rows, tails between batches, no batch of blocks <= 100 frames over an impure
+    input.
+    The inherited limit: the resonance rings for far longer than the reference's 100-frame cold start
+    lets it.  At k = 3.5 and 48 kHz the share of the impulse response's L1 norm beyond 100 frames is 93 % at 200 Hz, 66 % at 1 kHz,
+    29 % at 3 kHz (k = 0: 73 %, 0.1 %, none).  Near k = 4 the ring IS the sound, and 100 frames from zero state truncate it: every block
+    hears the first 100 frames of a ring, never a standing self-oscillation.  That is the reference's block semantics, not a defect
+    of this node; carried state would lift it, and is out of scope.
+    Out of scope: the voice program, the specialised build and the fused kernels (a graph with the node renders one kernel per node;
+    the machine's filter slots carry two states each); the node inside a block-rate control path (the batched engine answers
+    NotBatchable with the reason and the graph keeps the eager path, which serves frames == 1 in float64); a frame-rate cutoff, k or
+    drive; pass-band gain compensation (a `Gain` behind it does that); high-pass and band-pass pole mixes; oversampling; carried
+    state."""
+    cutoff: Receiver.BoundPort = port('cutoff')
+    resonance: Receiver.BoundPort = port('resonance')
+    drive: Receiver.BoundPort = port('drive')
+
+    class Type(str, enum.Enum):
+        """the node's own filter type: SIG_FILT_LADDER by its _native.FILT_TYPES name"""
+        ladder = 'ladder'
+
+        def __str__(self) -> str:
+            return str(self.value)
+
+        @property
+        def is_band(self) -> bool:
+            return False
+
+    @state
+    class State(fx.CritFilter.State):
+        poles: int = attr.ib(default=4, validator=_validate_poles, on_setattr=attr.setters.validate)
+
+    def type(self) -> 'Ladder.Type':
+        return self.Type.ladder
+
+    def control_rows(self, fetch) -> tuple:
+        """(resonance, drive): each the port's block-rate reply through `fetch`, or None where nothing enabled is plugged"""
+        return tuple(None if bound.sig is None or not bound.sig.get_state().enabled else as_control(fetch(bound))
+                     for bound in (self.resonance, self.drive))
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        hertz = as_control(self.cutoff.forward_at_block_rate(request))
+        k, drive = self.control_rows(lambda bound: bound.forward_at_block_rate(request))
+        return self._filter(request, hertz, ladder=(k, drive, int(self._state.poles)))
+
+
 def _validate_matrix(instance, attribute, new_value):
     if not (isinstance(new_value, np.ndarray) and new_value.shape == (64, 64)):
         raise BadStateValue(instance, attribute.name, new_value, 'must be a (64, 64) array')

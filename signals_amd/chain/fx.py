@@ -108,18 +108,21 @@ class CritFilter(Effect, abc.ABC):
 
     def _filter(self, request: Request, crit_1: torch.Tensor, crit_2: torch.Tensor = None,
                 resonant: bool = False, resonance: typing.Optional[torch.Tensor] = None,
-                equaliser: typing.Optional[str] = None, gain: typing.Optional[torch.Tensor] = None) -> torch.Tensor:
+                equaliser: typing.Optional[str] = None, gain: typing.Optional[torch.Tensor] = None,
+                ladder: typing.Optional[tuple] = None) -> torch.Tensor:
         """`resonant` (chain/ext.py ResonantFilter, single-cutoff types only): the resonant design with `resonance`, a one-row q
         tensor, or None for an unplugged port (1/sqrt2); otherwise a Butterworth filter of the reference.  `equaliser` (with
         `resonant`; chain/ext.py EqFilter): the equaliser design of that name (a key of _native.FILT_TYPES) instead, with `gain`, a
-        one-row tensor of dB, or None for an unplugged port (0 dB)"""
+        one-row tensor of dB, or None for an unplugged port (0 dB).  `ladder` (chain/ext.py Ladder): (resonance, drive, poles) of the
+        4-pole ladder instead of any biquad -- two one-row tensors, None for an unplugged port (0), and the output tap; an input of
+        width 1 then broadcasts over the request's channels"""
         assert Shape.of_array(crit_1).frames == 1
         if crit_2 is not None:
             assert Shape.of_array(crit_2).frames == 1
         context_frames = self.context_frames()
         window = self.input.forward_with_context(request, context_frames)
         shape = request.loc.shape
-        if window.shape[1] < shape.channels:
+        if window.shape[1] < shape.channels and not (ladder is not None and window.shape[1] == 1):
             raise IndexError(f'index {window.shape[1]} is out of bounds for axis 1 with size {window.shape[1]}')
         if crit_1.shape[1] < shape.channels:
             raise IndexError(f'index {crit_1.shape[1]} is out of bounds for axis 1 with size {crit_1.shape[1]}')
@@ -149,7 +152,7 @@ class CritFilter(Effect, abc.ABC):
             return _native.band_coldstart(str(self.type()), request.loc.rate, request.loc.position, shape.frames, 1,
                                           context_frames, cutoff, high, buf, history, result,
                                           status=self._status.tensor)
-        if resonant:
+        if resonant or ladder is not None:
             def one_row(row):
                 if row is None:
                     return None
@@ -158,6 +161,12 @@ class CritFilter(Effect, abc.ABC):
                     raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
                 row = row[:, :shape.channels]
                 return row if row.is_contiguous() else row.contiguous()
+            if ladder is not None:
+                k, drive, poles = ladder
+                if buf.shape[1] < shape.channels:
+                    buf = buf.expand(-1, shape.channels).contiguous()         # one column for every voice
+                return _native.ladder_coldstart(request.loc.rate, request.loc.position, shape.frames, 1, context_frames, cutoff,
+                                                one_row(k), one_row(drive), poles, buf, history, result, status=self._status.tensor)
             resonance = one_row(resonance)
             if equaliser is not None:
                 return _native.biquad_coldstart_eq(equaliser, request.loc.rate, request.loc.position, shape.frames, 1, context_frames, cutoff,

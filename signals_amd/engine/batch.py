@@ -72,6 +72,7 @@ class _Batch:
         (ext.UnisonOsc, 'a unison oscillator', 'the eager node serves one-frame requests'),
         (ext.Shaper, 'a waveshaper', 'the eager node serves one-frame requests'),
         (ext.ResonantFilter, 'a resonant filter', 'the eager node serves one-frame requests'),
+        (ext.Ladder, 'a ladder filter', 'the eager node serves one-frame requests'),
         (ext.Delay, 'a delay line', 'the eager node serves one-frame requests'),
         (ext.Sampler, 'a sampler', 'the eager node serves one-frame requests'),
     )
@@ -716,6 +717,8 @@ class _Batch:
                 owner_node: Emitter | None = None) -> torch.Tensor:
         """`envelope` / `owner_node`: the filter runs on behalf of RingMod(filter, ADSR) -- its stored rows are
         multiplied by the envelope and the buffer (history rows, tail) belongs to that RingMod node"""
+        if isinstance(node, ext.Ladder):
+            return self._ladder(node, channels, hist, rows)
         o = self.owner
         N, K, pos = self.N, self.K, self.pos
         band = isinstance(node, fx.DoubleCritFilter)
@@ -759,6 +762,32 @@ class _Batch:
                                                        status=status, envelope=envelope),
                       units=N * K * channels)
         self._own_history(owner_node or node, channels, hist, result)
+        return result
+
+    def _ladder(self, node: ext.Ladder, channels: int, hist: int, rows: int) -> torch.Tensor:
+        """the 4-pole ladder: a filter's window, history rows and tails, one sig_ladder_coldstart launch over the K blocks; the cutoff,
+        the resonance and the drive rows each per block on their own when that port is modulated, the last two None when unplugged.
+        A one-column input broadcasts over the voices where it is position-pure; a request-dependent one is answered afresh for every
+        context request on the eager path (chain/cache.py files a reply under its own shape; `_delay_uncached`), which this schedule
+        does not reproduce: NotBatchable"""
+        o, N, K, pos = self.owner, self.N, self.K, self.pos
+        cutoff, window, c0 = self._filter_window(node, channels, self._narrow(self._control(node.cutoff, 'cutoff'), channels), narrow_ok=True)
+        if window.shape[1] < channels:
+            if not _is_pure(node.input.sig, self._pure):
+                raise NotBatchable(f'{node.cls_name()} over a request-dependent input of one column (the eager path answers its context '
+                                   f'requests afresh)')
+            window = window.expand(-1, channels).contiguous()
+        k, drive = (None if row is None else self._narrow(row, channels)
+                    for row in node.control_rows(lambda bound: self._control(bound, bound.name)))
+        poles = int(node.get_state().poles)
+        swept = any(row is not None and row.shape[0] > 1 for row in (cutoff, k, drive))
+        result = torch.empty((rows, channels), dtype=AUDIO_DTYPE, device=window.device)
+        main = result[hist:]
+        status = o._status_word(node)
+        o._launch(f'ladder_coldstart[{poles}{",drive" if drive is not None else ""}{",blocks" if swept else ""}]',
+                  lambda: _native.ladder_coldstart(self.rate, pos, N, K, CONTEXT, cutoff, k, drive, poles, window, c0, main, status=status),
+                  units=N * K * channels)
+        self._own_history(node, channels, hist, result)
         return result
 
     def _own_history(self, node: Emitter, channels: int, hist: int, result: torch.Tensor) -> None:

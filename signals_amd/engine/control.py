@@ -137,6 +137,9 @@ class _ControlProgram:
         elif isinstance(src, ext.ResonantFilter):
             raise NotBatchable(f'{src.cls_name()} in a control path: a resonant filter has no block-rate program '
                                f'(the eager node serves one-frame requests)')
+        elif isinstance(src, ext.Ladder):
+            raise NotBatchable(f'{src.cls_name()} in a control path: a ladder filter has no block-rate program '
+                               f'(the eager node serves one-frame requests)')
         elif window and isinstance(src, fx.CritFilter):
             raise NotBatchable('a filter whose input contains a filter, in a control path')
         elif isinstance(src, fx.SingleCritFilter):

@@ -57,6 +57,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.cutoff, node.resonance, node.gain_port()]
     if isinstance(node, ext.ResonantFilter):
         return [node.cutoff, node.resonance]
+    if isinstance(node, ext.Ladder):
+        return [node.cutoff, node.resonance, node.drive]
     if isinstance(node, fx.SingleCritFilter):
         return [node.cutoff]
     if isinstance(node, fx.DoubleCritFilter):
