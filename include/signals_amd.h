@@ -599,7 +599,11 @@ typedef struct {
 } sig_ctl_ins;
 typedef struct { int32_t reg; int32_t cols; double* out; double* front; } sig_ctl_out;   /* out: (nblocks, cols) float64, contiguous; front: (1, cols) or NULL */
 /* front_position >= 0: the program is evaluated once more, at that frame position, into the outputs' `front` rows (the
- * controls of the block in front of the batch -- sig_fused_*_fm's *_hist -- without a launch of their own); -1: not. */
+ * controls of the block in front of the batch -- sig_fused_*_fm's *_hist -- without a launch of their own); -1: not.  The front
+ * evaluation is not clamped at min_position, it runs with nblocks == 0 too (the front rows alone), an output whose `front` is
+ * NULL is skipped, and a ROW with rows == nblocks is read at its row 0 there (there is no block in front of the first: a program
+ * whose front row matters keeps such rows out of it).  A ROW with rows == nblocks is (nblocks, cols) contiguous: block b reads
+ * element b * cols + v * stride (cols 1, stride 0: element b). */
 int sig_control_program(int32_t rate, int64_t position, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position,
                         int64_t min_position,
                         const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream);
