@@ -6,49 +6,39 @@
 // work each -- a vibrato + cutoff sweep + tremolo voice spent half of its batch time (and all of its host time) in eleven
 // of them.  Here the subgraph is a short straight-line program over registers, the same for every (block, column): thread
 // (b, v) evaluates it for block b at column v and writes the requested registers to their (nblocks, cols) outputs.
-// Arithmetic as in the per-node kernels (osc_bank.hip's f64 store path, elementwise.hip's ew_apply): the same expressions
-// under -ffp-contract=off, so the same bits.  Registers live in LDS, [register][thread]: every thread executes the same
-// instruction, so a register index is uniform and the accesses are conflict-free (a private array indexed by a run-time
-// value would go to scratch).  Instruction k writes register dst < n_ins (the host assigns them in instruction order).
+// The machine itself -- an instruction's value, a block's frame, the filter, the stores -- is sig_ctl_machine.h, one statement
+// for both builds of this file; here is what they do not share.  In the interpreter registers live in LDS, [register][thread]:
+// every thread executes the same instruction, so a register index is uniform and the accesses are conflict-free (a private
+// array indexed by a run-time value would go to scratch).  Instruction k writes register dst < n_ins (the host assigns them in
+// instruction order).
 #include <cstring>
 #include <mutex>
 #include <vector>
 
-#include "sig_adsr.h"
-#include "sig_biquad.h"
-#include "sig_noise.h"
-#include "sig_osc.h"
+#include "sig_ctl_machine.h"
 
-#define SIG_CTL_CONTEXT 100                 // a filter's `before` window: min(100, p) rows (fx.py:105, CritFilter.context_frames)
+using sig_ctl::kSpecThreads;
+using sig_ctl::kThreads;
 
 #ifdef SIG_CTL_STATIC_INS
 // A SPECIALISED build of this file (signals_amd/specialise.py: hipcc --genco with the program's structure as macros): the
 // registers are VGPRs, the interpretive loop and its chain of dependent LDS accesses are gone.  SIG_CTL_STATIC_INS = {{op, kind,
 // a, b, c, dst, wide}, ...} in evaluation order, SIG_CTL_STATIC_OUTS = {{reg, wide}, ...}; row pointers, strides and output
-// pointers are still read from the run-time `program` / `outs` arrays (uniform loads).  The same expressions as the interpreter
-// below, so the same bits.  One workgroup per block: the one-column instructions once per thread, the wide ones per chunk of
-// 256 columns.
+// pointers are still read from the run-time `program` / `outs` arrays (uniform loads).  One workgroup per block: the one-column
+// instructions once per thread, the wide ones per chunk of 256 columns.
 namespace {
 struct SIns { int op, kind, a, b, c, dst, wide; };
 struct SOut { int reg, wide; };
 constexpr SIns kIns[] = SIG_CTL_STATIC_INS;
 constexpr SOut kOuts[] = SIG_CTL_STATIC_OUTS;
 constexpr int kN = (int)(sizeof(kIns) / sizeof(kIns[0])), kNO = (int)(sizeof(kOuts) / sizeof(kOuts[0]));
-constexpr int kSpecThreads = 256;
-static_assert(kSpecThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h + 1 <= 101 window rows over the threads");
 // wide: bit 0 = more than one column, bit 1 = window-rate (the run right in front of a FILTER)
 constexpr int window_start(int k) { int w = k; while (w > 0 && (kIns[w - 1].wide & 2)) --w; return w; }
 constexpr bool has_filter() { for (int k = 0; k < kN; ++k) if (kIns[k].op == SIG_CTL_FILTER) return true; return false; }
 constexpr bool kHasFilter = has_filter();
-// an ADSR's other three registers ride in the ADSRARGS word right in front of it (the header's description)
-constexpr bool pairs_formed() {
-    for (int k = 0; k < kN; ++k) {
-        if (kIns[k].op == SIG_CTL_ADSR && (k == 0 || kIns[k - 1].op != SIG_CTL_ADSRARGS || kIns[k - 1].wide != kIns[k].wide)) return false;
-        if (kIns[k].op == SIG_CTL_ADSRARGS && (k + 1 >= kN || kIns[k + 1].op != SIG_CTL_ADSR)) return false;
-    }
-    return true;
-}
-static_assert(pairs_formed(), "every SIG_CTL_ADSR has its SIG_CTL_ADSRARGS right in front of it");
+constexpr int op_of(int k) { return kIns[k].op; }
+constexpr int wide_of(int k) { return kIns[k].wide; }
+static_assert(sig_ctl::pairs_formed(kN, op_of, wide_of), "every SIG_CTL_ADSR has its SIG_CTL_ADSRARGS right in front of it");
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(double rate, int64_t position, int64_t step, int nblocks, int cols,
@@ -56,69 +46,22 @@ extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(d
                                                                                const sig_ctl_ins* __restrict__ program, int n_ins,
                                                                                const sig_ctl_out* __restrict__ outs, int n_outs)
 {
-    // (the header's SIG_CTL_FILTER / SIG_CTL_NOISE semantics, as in the interpreter below)
-    const bool front = front_position >= 0 && blockIdx.x == (unsigned)nblocks;
-    const int64_t b = front ? 0 : blockIdx.x;
-    if (front) { position = front_position; step = 0; }
-    int64_t frame_b = position + b * step;
-    if (!front && frame_b < min_position) frame_b = min_position;
-    const int h = (int)(frame_b < SIG_CTL_CONTEXT ? frame_b : SIG_CTL_CONTEXT);     // a filter's history rows: min(100, p)
+    const sig_ctl::Block blk(position, step, nblocks, front_position, min_position);
+    const int64_t frame_b = blk.frame();
+    const int h = sig_ctl::window_rows(frame_b);
     double reg[kN];
 #pragma unroll
     for (int k = 0; k < kN; ++k) reg[k] = 0.0;
     auto get = [&](int r) { return r < 0 ? 0.0 : reg[r]; };
     auto exec = [&](int k, int v, int64_t frame, bool narrow) {
-        const SIns I = kIns[k];
-        double x;
-        switch (I.op) {
-            case SIG_CTL_ROW: {
-                const sig_ctl_ins& ins = program[k];
-                x = ins.row[(ins.rows > 1 ? b * (int64_t)(ins.stride ? ins.cols : 1) : 0) + (int64_t)(v < ins.cols ? v : 0) * ins.stride];
-                break;
-            }
-            case SIG_CTL_OSC: {
-                const double t = (double)frame / rate * get(I.a) + get(I.b);          // osc.py:32
-                if (narrow) {                                                          // osc_bank.hip's f32 store path
-                    switch (I.kind) {
-                        case SIG_OSC_SINE: x = sig_osc::osc_wave<SIG_OSC_SINE, float>(t); break;
-                        case SIG_OSC_SQUARE: x = sig_osc::osc_wave<SIG_OSC_SQUARE, float>(t); break;
-                        case SIG_OSC_SAWTOOTH: x = sig_osc::osc_wave<SIG_OSC_SAWTOOTH, float>(t); break;
-                        default: x = sig_osc::osc_wave<SIG_OSC_TRIANGLE, float>(t); break;
-                    }
-                    break;
-                }
-                switch (I.kind) {
-                    case SIG_OSC_SINE: x = sig_osc::osc_sine(t); break;
-                    case SIG_OSC_SQUARE: x = sig_osc::osc_square(t); break;
-                    case SIG_OSC_SAWTOOTH: x = sig_osc::osc_sawtooth(t); break;
-                    default: x = sig_osc::osc_triangle(t); break;
-                }
-                break;
-            }
-            case SIG_CTL_MIX: { const double c = get(I.c); x = c * get(I.a) + (1.0 - c) * get(I.b); break; }   // fx.py:40
-            case SIG_CTL_AMP: { const double a = get(I.a); x = copysign(pow(a, get(I.b)), a); break; }           // fx.py:60
-            case SIG_CTL_NOISE: x = sig_noise::noise_value((uint64_t)(uintptr_t)program[k].row, frame, v); break;   // noise.hip
-            case SIG_CTL_ADSRARGS: x = 0.0; break;                                                             // (read by the ADSR behind it)
-            case SIG_CTL_ADSR: {                                                                               // adsr.hip
-                const SIns G = kIns[k > 0 ? k - 1 : 0];
-                const sig_env::Voice p = sig_env::make_voice(get(I.a), get(I.b), get(I.c), get(G.a), get(G.b), get(G.c));
-                x = sig_env::level(p, (double)frame / rate);
-                break;
-            }
-            default: x = get(I.a) * get(I.b); break;                                                           // Gain, RingMod: fx.py:46, :52
-        }
-        if (narrow) x = (double)(float)x;
-        return x;
+        return sig_ctl::value<true, true>(kIns[k], program[k], blk, v, frame, rate, narrow, get,
+                                          [&] { const SIns G = kIns[k > 0 ? k - 1 : 0]; return sig_ctl::Carrier{G.a, G.b, G.c}; });
     };
     // window-rate instructions [window_start(k), k) of the FILTER k for the row at `frame`
     auto window = [&](int k, int v, int64_t frame, bool narrow) {
 #pragma unroll
         for (int w = 0; w < kN; ++w)
             if (w >= window_start(k) && w < k) reg[kIns[w].dst] = exec(w, v, frame, narrow);
-    };
-    auto design = [&](int k, bool report, sig_biquad::Biquad& q) {
-        const bool ok = sig_biquad::design_butter2(kIns[k].kind, get(kIns[k].b), rate, q);
-        if (!ok && report && program[k].row) atomicOr(reinterpret_cast<int*>(const_cast<double*>(program[k].row)), SIG_STATUS_BAD_CUTOFF);
     };
     __shared__ double xs[kHasFilter ? kSpecThreads : 1];                       // a one-column filter's window rows
     auto run = [&](int v, bool wide_pass) {
@@ -134,22 +77,14 @@ extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(d
                 const int j = threadIdx.x;
                 if (j <= h) { window(k, 0, frame_b - h + j, j < h && h > 1); xs[j] = get(I.a); }
                 __syncthreads();
-                design(k, threadIdx.x == 0, q);
-                for (int i = 0; i <= h; ++i) {
-                    const double x = xs[i];
-                    y = q.b0 * x + z0;
-                    z0 = q.b1 * x - q.a1 * y + z1;
-                    z1 = q.b2 * x - q.a2 * y;
-                }
+                sig_ctl::design(I.kind, get(I.b), rate, threadIdx.x == 0, program[k], q);
+                for (int i = 0; i <= h; ++i) y = sig_biquad::step(q, xs[i], z0, z1);
                 __syncthreads();
             } else {                                                           // thread v walks the rows of its column
-                design(k, v < program[k].cols, q);
+                sig_ctl::design(I.kind, get(I.b), rate, v < program[k].cols, program[k], q);
                 for (int j = 0; j <= h; ++j) {
                     window(k, v, frame_b - h + j, j < h && h > 1);
-                    const double x = get(I.a);
-                    y = q.b0 * x + z0;
-                    z0 = q.b1 * x - q.a1 * y + z1;
-                    z1 = q.b2 * x - q.a2 * y;
+                    y = sig_biquad::step(q, get(I.a), z0, z1);
                 }
             }
             reg[I.dst] = y;
@@ -159,23 +94,14 @@ extern "C" __global__ __launch_bounds__(kSpecThreads) void sig_ctl_specialised(d
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < kNO; ++k)
-            if (!kOuts[k].wide) {
-                if (!front) outs[k].out[b] = reg[kOuts[k].reg];
-                else if (outs[k].front) outs[k].front[0] = reg[kOuts[k].reg];
-            }
+            if (!kOuts[k].wide) sig_ctl::store<false>(outs, k, blk, 0, [&] { return reg[kOuts[k].reg]; });
     }
     for (int v0 = 0; v0 < cols; v0 += kSpecThreads) {
         const int v = v0 + threadIdx.x;
         run(v, true);
 #pragma unroll
         for (int k = 0; k < kNO; ++k)
-            if (kOuts[k].wide) {
-                const sig_ctl_out o = outs[k];
-                if (v < o.cols) {
-                    if (!front) o.out[b * o.cols + v] = reg[kOuts[k].reg];
-                    else if (o.front) o.front[v] = reg[kOuts[k].reg];
-                }
-            }
+            if (kOuts[k].wide) { const sig_ctl_out o = outs[k]; sig_ctl::store<true>(&o, 0, blk, v, [&] { return reg[kOuts[k].reg]; }); }
     }
 }
 // what the attaching library checks: the structure the image was built for
@@ -191,11 +117,6 @@ extern "C" __global__ void sig_ctl_specialised_info(int32_t* out)
 #else
 
 namespace {
-
-constexpr int kMaxRegs = SIG_CTL_MAX_REGS;
-
-constexpr int kThreads = 128;
-static_assert(kThreads > SIG_CTL_CONTEXT, "a one-column filter spreads its h + 1 <= 101 window rows over the threads");
 
 // One workgroup per block.  The program is copied into LDS once (fetching every instruction from global memory cost a
 // dependent scalar load of ~0.5 us per instruction per wave); the register file behind it is sized by the program (n_regs x
@@ -221,77 +142,20 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
         for (int w = threadIdx.x; w < words; w += kThreads) dst[w] = src[w];
     }
     __syncthreads();
-    // the last workgroup of a launch with a front position evaluates the program ONCE more, at that position, into the
-    // outputs' `front` rows (the controls of the block in front of the batch: sig_fused_*_fm's *_hist)
-    const bool front = front_position >= 0 && blockIdx.x == (unsigned)nblocks;
-    const int64_t b = front ? 0 : blockIdx.x;
-    if (front) { position = front_position; step = 0; }
+    const sig_ctl::Block blk(position, step, nblocks, front_position, min_position);
     double* r = regs + threadIdx.x;
     auto get = [&](int reg) { return reg < 0 ? 0.0 : r[reg * kThreads]; };
-    auto row_value = [&](const sig_ctl_ins& ins, int v) {
-        return ins.row[(ins.rows > 1 ? b * (int64_t)(ins.stride ? ins.cols : 1) : 0) + (int64_t)(v < ins.cols ? v : 0) * ins.stride];
-    };
-    auto block_frame = [&]() {
-        int64_t frame = position + b * step;
-        if (!front && frame < min_position) frame = min_position;              // (the first blocks of a run that starts before min_position are evaluated there)
-        return frame;
-    };
-    const int64_t frame_b = EXT ? block_frame() : 0;                           // (EXT: the filters' window position)
-    // `narrow`: a history row of a filter's window -- every node's reply is float32 audio there (EXT only)
+    const int64_t frame_b = EXT ? blk.frame() : 0;                             // (EXT: the filters' window position)
     auto execute = [&](const sig_ctl_ins& ins, int v, int64_t frame, bool narrow) {
-        double x;
-        switch (ins.op) {
-            case SIG_CTL_ROW: x = row_value(ins, v); break;
-            case SIG_CTL_OSC: {
-                if (!EXT) frame = block_frame();
-                const double t = (double)frame / rate * get(ins.a) + get(ins.b);      // osc.py:32
-                if (EXT && narrow) {                                                   // osc_bank.hip's f32 store path
-                    switch (ins.kind) {
-                        case SIG_OSC_SINE: x = sig_osc::osc_wave<SIG_OSC_SINE, float>(t); break;
-                        case SIG_OSC_SQUARE: x = sig_osc::osc_wave<SIG_OSC_SQUARE, float>(t); break;
-                        case SIG_OSC_SAWTOOTH: x = sig_osc::osc_wave<SIG_OSC_SAWTOOTH, float>(t); break;
-                        default: x = sig_osc::osc_wave<SIG_OSC_TRIANGLE, float>(t); break;
-                    }
-                    break;
-                }
-                switch (ins.kind) {
-                    case SIG_OSC_SINE: x = sig_osc::osc_sine(t); break;
-                    case SIG_OSC_SQUARE: x = sig_osc::osc_square(t); break;
-                    case SIG_OSC_SAWTOOTH: x = sig_osc::osc_sawtooth(t); break;
-                    default: x = sig_osc::osc_triangle(t); break;
-                }
-                break;
-            }
-            case SIG_CTL_MIX: { const double c = get(ins.c); x = c * get(ins.a) + (1.0 - c) * get(ins.b); break; }   // fx.py:40
-            case SIG_CTL_AMP: { const double a = get(ins.a); x = copysign(pow(a, get(ins.b)), a); break; }           // fx.py:60
-            case SIG_CTL_NOISE:
-                if (EXT) { x = sig_noise::noise_value((uint64_t)(uintptr_t)ins.row, frame, v); break; }   // noise.hip
-                [[fallthrough]];
-            case SIG_CTL_ADSRARGS:
-                if (ENV) return;                                                        // (read by the ADSR behind it)
-                [[fallthrough]];
-            case SIG_CTL_ADSR:
-                if (ENV) {                                                              // adsr.hip: the level at this one frame
-                    const sig_ctl_ins* g = &ins - 1;                                    // a lone ADSR reads zeros for the carrier's three
-                    const bool paired = &ins != prog && g->op == SIG_CTL_ADSRARGS;
-                    const sig_env::Voice p = sig_env::make_voice(get(ins.a), get(ins.b), get(ins.c), get(paired ? g->a : -1),
-                                                                 get(paired ? g->b : -1), get(paired ? g->c : -1));
-                    x = sig_env::level(p, (double)frame / rate);
-                    break;
-                }
-                [[fallthrough]];
-            default: x = get(ins.a) * get(ins.b); break;                                                           // Gain, RingMod: fx.py:46, :52
-        }
-        if (EXT && narrow) x = (double)(float)x;
-        r[ins.dst * kThreads] = x;
+        if (ENV && ins.op == SIG_CTL_ADSRARGS) return;                         // (read by the ADSR behind it)
+        r[ins.dst * kThreads] = sig_ctl::value<EXT, ENV>(ins, ins, blk, v, frame, rate, narrow, get, [&] {
+            const sig_ctl_ins* g = &ins - 1;                                   // a lone ADSR reads zeros for the carrier's three
+            const bool paired = &ins != prog && g->op == SIG_CTL_ADSRARGS;
+            return sig_ctl::Carrier{paired ? g->a : -1, paired ? g->b : -1, paired ? g->c : -1};
+        });
     };
-    // FILTER `f` over the window-rate instructions [w0, k): the biquad designed from the cutoff register, cold-started over
-    // the rows p - h .. p (biquad.hip: design_butter2, then scipy's _sosfilt step, one rounding per operation)
-    auto design = [&](const sig_ctl_ins& f, bool report, sig_biquad::Biquad& q) {
-        const bool ok = sig_biquad::design_butter2(f.kind, get(f.b), rate, q);
-        if (!ok && report && f.row) atomicOr(reinterpret_cast<int*>(const_cast<double*>(f.row)), SIG_STATUS_BAD_CUTOFF);
-    };
-    const int h = (int)(frame_b < SIG_CTL_CONTEXT ? frame_b : SIG_CTL_CONTEXT);     // BlockLoc.before: min(100, p)
+    // FILTER `f` over the window-rate instructions [w0, k), cold-started over the rows p - h .. p
+    const int h = sig_ctl::window_rows(frame_b);
     // one column: thread j evaluates window row j, then every thread steps the filter over the rows in the register file
     auto filter_narrow = [&](const sig_ctl_ins& f, int w0, int k) {
         const int j = threadIdx.x;
@@ -299,29 +163,21 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
             for (int w = w0; w < k; ++w) execute(prog[w], 0, frame_b - h + j, j < h && h > 1);
         __syncthreads();
         sig_biquad::Biquad q;
-        design(f, threadIdx.x == 0, q);
+        sig_ctl::design(f.kind, get(f.b), rate, threadIdx.x == 0, f, q);
         double z0 = 0.0, z1 = 0.0, y = 0.0;
         const double* xs = regs + f.a * kThreads;
-        for (int i = 0; i <= h; ++i) {
-            const double x = xs[i];
-            y = q.b0 * x + z0;
-            z0 = q.b1 * x - q.a1 * y + z1;
-            z1 = q.b2 * x - q.a2 * y;
-        }
+        for (int i = 0; i <= h; ++i) y = sig_biquad::step(q, xs[i], z0, z1);
         __syncthreads();                                                       // (every thread has read the rows)
         r[f.dst * kThreads] = y;
     };
     // wider: thread v walks the rows of its own column
     auto filter_wide = [&](const sig_ctl_ins& f, int w0, int k, int v) {
         sig_biquad::Biquad q;
-        design(f, v < f.cols, q);
+        sig_ctl::design(f.kind, get(f.b), rate, v < f.cols, f, q);
         double z0 = 0.0, z1 = 0.0, y = 0.0;
         for (int j = 0; j <= h; ++j) {
             for (int w = w0; w < k; ++w) execute(prog[w], v, frame_b - h + j, j < h && h > 1);
-            const double x = get(f.a);
-            y = q.b0 * x + z0;
-            z0 = q.b1 * x - q.a1 * y + z1;
-            z1 = q.b2 * x - q.a2 * y;
+            y = sig_biquad::step(q, get(f.a), z0, z1);
         }
         r[f.dst * kThreads] = y;
     };
@@ -332,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     for (int k = 0; k < k0; k += 4) {
         double x[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = (k + u < k0) ? row_value(prog[k + u], 0) : 0.0;
+        for (int u = 0; u < 4; ++u) x[u] = (k + u < k0) ? sig_ctl::row_value(prog[k + u], blk.b, 0) : 0.0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) if (k + u < k0) r[prog[k + u].dst * kThreads] = x[u];
     }
@@ -354,10 +210,7 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
     }
     if (threadIdx.x == 0)
         for (int k = 0; k < n_outs; ++k)
-            if (outs[k].cols == 1) {
-                if (!front) outs[k].out[b] = r[outs[k].reg * kThreads];
-                else if (outs[k].front) outs[k].front[0] = r[outs[k].reg * kThreads];
-            }
+            if (outs[k].cols == 1) sig_ctl::store<false>(outs, k, blk, 0, [&] { return r[outs[k].reg * kThreads]; });
     // ---- wider: per chunk of 128 columns
     for (int v0 = 0; v0 < cols; v0 += kThreads) {
         const int v = v0 + threadIdx.x;
@@ -379,12 +232,20 @@ __global__ __launch_bounds__(kThreads) void control_program_kernel(double rate, 
         }
         for (int k = 0; k < n_outs; ++k) {
             const sig_ctl_out o = outs[k];
-            if (o.cols > 1 && v < o.cols) {
-                if (!front) o.out[b * o.cols + v] = r[o.reg * kThreads];
-                else if (o.front) o.front[v] = r[o.reg * kThreads];
-            }
+            if (o.cols > 1) sig_ctl::store<true>(&o, 0, blk, v, [&] { return r[o.reg * kThreads]; });
         }
     }
+}
+
+// What every launching entry checks, and the workgroups of the launch: one per block and one for a front position; 0 where
+// there is nothing to do
+int ctl_workgroups(int32_t rate, int32_t step, int32_t nblocks, int32_t cols, int64_t front_position, int64_t min_position,
+                   const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, unsigned& workgroups)
+{
+    SIG_CHECK_ARG(rate > 0 && step >= 0 && nblocks >= 0 && cols >= 1 && n_ins >= 0 && n_outs >= 0 && front_position >= -1 && min_position >= 0);
+    SIG_CHECK_ARG((program || n_ins == 0) && (outs || n_outs == 0) && n_ins <= SIG_CTL_MAX_INS);
+    workgroups = ((nblocks == 0 && front_position < 0) || n_outs == 0) ? 0u : (unsigned)(nblocks + (front_position >= 0 ? 1 : 0));
+    return 0;
 }
 
 template <bool EXT, bool ENV = false>
@@ -392,15 +253,15 @@ int launch_control_program(int32_t rate, int64_t position, int32_t step, int32_t
                            int64_t front_position, int64_t min_position,
                            const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
 {
-    SIG_CHECK_ARG(rate > 0 && step >= 0 && nblocks >= 0 && cols >= 1 && n_ins >= 0 && n_outs >= 0 && front_position >= -1 && min_position >= 0);
-    SIG_CHECK_ARG((program || n_ins == 0) && (outs || n_outs == 0) && n_ins <= SIG_CTL_MAX_INS);
-    if ((nblocks == 0 && front_position < 0) || n_outs == 0) return 0;
+    unsigned workgroups = 0;
+    if (const int bad = ctl_workgroups(rate, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, workgroups)) return bad;
+    if (workgroups == 0) return 0;
     // one register per instruction (dst < n_ins): the program lives in device memory, so register indices cannot be checked
     // here -- the LDS register file is sized by n_ins, and n_ins <= SIG_CTL_MAX_INS == SIG_CTL_MAX_REGS was checked above
     static_assert(SIG_CTL_MAX_INS <= SIG_CTL_MAX_REGS, "the register file is sized by the instruction count");
     const int n_regs = n_ins > 0 ? n_ins : 1;
-    control_program_kernel<EXT, ENV><<<(unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>((double)rate, position, step, nblocks, cols, front_position, min_position,
-                                                                                          program, n_ins, outs, n_outs);
+    control_program_kernel<EXT, ENV><<<workgroups, kThreads, (size_t)n_regs * kThreads * sizeof(double), static_cast<hipStream_t>(stream)>>>(
+        (double)rate, position, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs);
     return sig_launch_status();
 }
 
@@ -432,19 +293,6 @@ extern "C" int sig_control_program_envelope(int32_t rate, int64_t position, int3
 // image from (signals_amd/engine/control.py: _ControlProgram).
 namespace {
 struct CtlSpecial { hipModule_t mod; hipFunction_t fn; };
-// the ADSRARGS / ADSR pairs of a description (the header's words): each ADSR right behind its carrier, both of one width and rate
-bool ctl_pairs_formed(const int32_t* description, int32_t n_words)
-{
-    const int n = description[0];
-    if (n < 0 || n > SIG_CTL_MAX_INS || 2 + 7 * n > n_words) return false;
-    auto op = [&](int k) { return description[2 + 7 * k]; };
-    auto wide = [&](int k) { return description[2 + 7 * k + 6]; };
-    for (int k = 0; k < n; ++k) {
-        if (op(k) == SIG_CTL_ADSR && (k == 0 || op(k - 1) != SIG_CTL_ADSRARGS || wide(k - 1) != wide(k))) return false;
-        if (op(k) == SIG_CTL_ADSRARGS && (k + 1 >= n || op(k + 1) != SIG_CTL_ADSR)) return false;
-    }
-    return true;
-}
 std::vector<CtlSpecial>& ctl_specials() { static std::vector<CtlSpecial> v; return v; }
 std::mutex& ctl_specials_lock() { static std::mutex m; return m; }
 }  // namespace
@@ -452,7 +300,9 @@ std::mutex& ctl_specials_lock() { static std::mutex m; return m; }
 extern "C" int sig_control_program_attach(const int32_t* description, int32_t n_words, const void* image, int32_t* handle)
 {
     SIG_CHECK_ARG(description && image && handle && n_words >= 2 && n_words <= 2 + 7 * SIG_CTL_MAX_INS + 2 * 64);
-    SIG_CHECK_ARG(ctl_pairs_formed(description, n_words));
+    const int n = description[0];
+    SIG_CHECK_ARG(n >= 0 && n <= SIG_CTL_MAX_INS && 2 + 7 * n <= n_words);
+    SIG_CHECK_ARG(sig_ctl::pairs_formed(n, [&](int k) { return description[2 + 7 * k]; }, [&](int k) { return description[2 + 7 * k + 6]; }));
     CtlSpecial e{};
     hipError_t err = hipModuleLoadData(&e.mod, image);
     if (err != hipSuccess) { (void)hipGetLastError(); return (int)err; }
@@ -481,19 +331,18 @@ extern "C" int sig_control_program_attached(int32_t handle, int32_t rate, int64_
                                             int64_t front_position, int64_t min_position,
                                             const sig_ctl_ins* program, int32_t n_ins, const sig_ctl_out* outs, int32_t n_outs, void* stream)
 {
-    SIG_CHECK_ARG(rate > 0 && step >= 0 && nblocks >= 0 && cols >= 1 && n_ins >= 0 && n_outs >= 0 && front_position >= -1 && min_position >= 0);
-    SIG_CHECK_ARG((program || n_ins == 0) && (outs || n_outs == 0) && n_ins <= SIG_CTL_MAX_INS);
+    unsigned workgroups = 0;
+    if (const int bad = ctl_workgroups(rate, step, nblocks, cols, front_position, min_position, program, n_ins, outs, n_outs, workgroups)) return bad;
     hipFunction_t fn = nullptr;
     {
         std::lock_guard<std::mutex> g(ctl_specials_lock());
         SIG_CHECK_ARG(handle >= 1 && (size_t)handle <= ctl_specials().size());
         fn = ctl_specials()[(size_t)handle - 1].fn;
     }
-    if ((nblocks == 0 && front_position < 0) || n_outs == 0) return 0;
+    if (workgroups == 0) return 0;
     double rate_d = (double)rate;
     int64_t step64 = step;
     void* params[] = {&rate_d, &position, &step64, &nblocks, &cols, &front_position, &min_position, &program, &n_ins, &outs, &n_outs};
-    return (int)hipModuleLaunchKernel(fn, (unsigned)(nblocks + (front_position >= 0 ? 1 : 0)), 1, 1, 256, 1, 1, 0,
-                                      static_cast<hipStream_t>(stream), params, nullptr);
+    return (int)hipModuleLaunchKernel(fn, workgroups, 1, 1, kSpecThreads, 1, 1, 0, static_cast<hipStream_t>(stream), params, nullptr);
 }
 #endif  // SIG_CTL_STATIC_INS

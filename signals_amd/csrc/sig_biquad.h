@@ -27,6 +27,14 @@ __device__ __forceinline__ bool design_butter2(int type, double cutoff, double r
     return !bad;
 }
 
+// One transposed-direct-form-II step (scipy's _sosfilt), one rounding per operation: the reply to x, the state moved on.
+__device__ __forceinline__ double step(const Biquad& q, double x, double& z0, double& z1) {
+    const double y = q.b0 * x + z0;
+    z0 = q.b1 * x - q.a1 * y + z1;
+    z1 = q.b2 * x - q.a2 * y;
+    return y;
+}
+
 // Resonant 2-pole low-pass / high-pass (chain/ext.py ResonantLowPass / ResonantHighPass): design_butter2's bilinear transform with
 // the damping 1/q in place of sqrt2 -- the RBJ cookbook's low-pass / high-pass (alpha = sin(w0) / (2 q)) in another form, the
 // Butterworth response at q = 1/sqrt2.  `resonance` null: unplugged, the damping is sqrt2 itself (design_butter2's bits).

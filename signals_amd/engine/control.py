@@ -6,7 +6,7 @@ import torch
 from signals_amd import _native, runtime
 from signals_amd.chain import CTRL_DTYPE, Emitter, as_control, broadcast_shape
 from signals_amd.chain import ext, fixed, fx, noise, osc
-from signals_amd.engine.graph import NotBatchable, _ctl_const
+from signals_amd.engine.graph import NotBatchable, _ctl_const, _no_block_rate
 
 
 class _ControlProgram:
@@ -134,39 +134,14 @@ class _ControlProgram:
             got = self._push(_native.CtlIns(_native.CTL_OPS['Adsr'], 0, at, de, su, 0, 0, 0, cols, int(window), None), cols)
         elif isinstance(src, noise.White):
             got = self._push(self._noise(src, window), self._request_width(src))
-        elif isinstance(src, ext.ResonantFilter):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a resonant filter has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.Ladder):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a ladder filter has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
+        elif _no_block_rate(src, 'program', window) is not None:       # (ahead of the filters: a resonant or ladder filter is a CritFilter)
+            raise NotBatchable(_no_block_rate(src, 'program', window))
         elif window and isinstance(src, fx.CritFilter):
             raise NotBatchable('a filter whose input contains a filter, in a control path')
         elif isinstance(src, fx.SingleCritFilter):
             got = self._filter(src)
         elif isinstance(src, fx.DoubleCritFilter):
             raise NotBatchable(f'{src.cls_name()} in a control path: only LowPass / HighPass run at block rate')
-        elif isinstance(src, ext.Wavetable):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a wavetable oscillator has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.UnisonOsc):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a unison oscillator has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.Shaper):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a waveshaper has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.Delay):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a delay line has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.Sampler):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a sampler has no block-rate program '
-                               f'(the eager node serves one-frame requests)')
-        elif isinstance(src, ext.PMOsc) and window:
-            raise NotBatchable(f'{src.cls_name()} inside a control filter\'s input: a phase-modulation oscillator has no '
-                               f'window-rate program')
-        elif isinstance(src, ext.PMOsc):
-            raise NotBatchable(f'{src.cls_name()} in a control path: a phase-modulation oscillator has no block-rate program '
-                               f'(its modulator is a frame-rate input)')
         elif window:
             raise NotBatchable(f'no window-rate program for {src.cls_name()} inside a control filter\'s input')
         else:

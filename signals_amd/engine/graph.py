@@ -20,6 +20,31 @@ _KNOWN_TYPES = (fixed.Fixed, osc.Osc, ext.PMOsc, ext.Wavetable, ext.UnisonOsc, n
                 fx.Amp, ext.Shaper, ext.Delay, ext.Sampler, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
 
 
+# the extension nodes that are not evaluated at block rate: (class, what a refusal calls it, why), one table for the control
+# program (control.py: `_emit`) and the node-by-node control rows (batch.py: `_control_node`)
+_NO_BLOCK_RATE = (
+    (ext.PMOsc, 'a phase-modulation oscillator', 'its modulator is a frame-rate input'),
+    (ext.Wavetable, 'a wavetable oscillator', 'the eager node serves one-frame requests'),
+    (ext.UnisonOsc, 'a unison oscillator', 'the eager node serves one-frame requests'),
+    (ext.Shaper, 'a waveshaper', 'the eager node serves one-frame requests'),
+    (ext.ResonantFilter, 'a resonant filter', 'the eager node serves one-frame requests'),
+    (ext.Ladder, 'a ladder filter', 'the eager node serves one-frame requests'),
+    (ext.Delay, 'a delay line', 'the eager node serves one-frame requests'),
+    (ext.Sampler, 'a sampler', 'the eager node serves one-frame requests'),
+)
+
+
+def _no_block_rate(node: Emitter, route: str, window: bool = False) -> str | None:
+    """the refusal of a node of _NO_BLOCK_RATE in a control path, None for any other node; `route`: 'program' | 'schedule', what
+    the refusing site would have run; `window`: inside a control filter's input, where a frame-rate input has its own wording"""
+    for family, phrase, why in _NO_BLOCK_RATE:
+        if isinstance(node, family):
+            if window and family is ext.PMOsc:                 # (its modulator would have to be a window-rate input)
+                return f'{node.cls_name()} inside a control filter\'s input: {phrase} has no window-rate {route}'
+            return f'{node.cls_name()} in a control path: {phrase} has no block-rate {route} ({why})'
+    return None
+
+
 def _ctl_const(port: Receiver.BoundPort) -> bool:
     """a control port whose value cannot change from block to block: unplugged, disabled, or a Fixed"""
     src = port.sig

@@ -16,6 +16,7 @@ Reference semantics are not touched: the image is voice_program.hip itself (same
 import hashlib
 import os
 import pathlib
+import re
 import shutil
 import subprocess
 import threading
@@ -24,10 +25,31 @@ from . import _native
 
 CSRC = pathlib.Path(__file__).resolve().parent / 'csrc'
 CACHE = pathlib.Path(os.environ.get('SIG_SPECIALISE_CACHE') or pathlib.Path(__file__).resolve().parent / '_specialised')
-SOURCES = ('voice_program.hip', 'sig_vp_machine.h', 'control_program.hip', 'sig_adsr.h', 'sig_biquad.h', 'sig_bus_tile.h', 'sig_noise.h', 'sig_osc.h', 'sig_table.h', 'sig_common.h', '../../include/signals_amd.h')
+ROOTS = ('voice_program.hip', 'control_program.hip')         # the two files that are built specialised
 
-_attached: set = set()
+
+def _sources() -> tuple:
+    """every file a specialised image is compiled from: the two kernels, the closure of their quoted #include "..." lines
+    (resolved beside the including file, then in include/), and the public header; paths relative to CSRC, in a fixed order"""
+    include = CSRC.parent.parent / 'include'
+    seen, todo = {}, [CSRC / name for name in ROOTS] + [include / 'signals_amd.h']
+    while todo:
+        path = todo.pop().resolve()
+        if path in seen:
+            continue
+        seen[path] = path.read_bytes()
+        for name in re.findall(rb'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', seen[path], re.M):
+            found = [d / name.decode() for d in (path.parent, include) if (d / name.decode()).exists()]
+            if not found:
+                raise SpecialiseError(f'{path.name} includes "{name.decode()}", which is neither beside it nor in include/')
+            todo.append(found[0])
+    return tuple(sorted(os.path.relpath(p, CSRC.resolve()) for p in seen))
+
+
+_attached: dict = {}        # key -> what attaching returned: True (a voice program), a handle (a control program)
 _failed: set = set()
+_pending: dict = {}         # key -> the future of its background build
+_pool = None                # one worker: builds queue up behind each other
 _lock = threading.Lock()
 
 
@@ -42,8 +64,8 @@ def hipcc() -> str | None:
 
 def _source_digest() -> str:
     h = hashlib.sha1()
-    for name in SOURCES:
-        h.update((CSRC / name).read_bytes())
+    for name in _sources():
+        h.update(name.encode() + b'\0' + (CSRC / name).read_bytes())
     return h.hexdigest()
 
 
@@ -98,9 +120,6 @@ def build(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, 
 
 # ---- block-rate control programs (control_program.hip): the same idea, keyed by the program's STRUCTURE (ops, register indices,
 # which instructions and outputs are wide); row and output pointers stay run-time arguments
-_ctl_handles: dict = {}
-
-
 def control_flags(description: list) -> list:
     n_ins, n_outs = description[0], description[1]
     ins = [description[2 + 7 * k: 2 + 7 * k + 7] for k in range(n_ins)]
@@ -109,101 +128,77 @@ def control_flags(description: list) -> list:
     return [f'-DSIG_CTL_STATIC_INS={braces(ins)}', f'-DSIG_CTL_STATIC_OUTS={braces(outs)}']
 
 
+# ---- build and attach, once per process and key, for both kinds: `build()` compiles (or loads from the cache), `attach(image)`
+# hands the image to the library and returns what the attached kernel is known by
+def _ensure(key, what: str, build, attach, background: bool):
+    """what `attach` returned for this key, now or earlier; None where it is not available: no hipcc, a failed build (warned
+    about once), or -- `background` -- still being built on the worker thread"""
+    global _pool
+    with _lock:
+        if key in _attached:
+            return _attached[key]
+        if key in _failed or (background and key in _pending):
+            return None
+        if background:
+            if _pool is None:
+                import concurrent.futures
+                _pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix='sig-specialise')
+            _pending[key] = _pool.submit(_finish, key, what, build, attach, True)
+            return None
+    return _finish(key, what, build, attach, False)
+
+
+def _finish(key, what: str, build, attach, queued: bool):
+    try:
+        image = build()                                   # (outside the lock: the compiler takes seconds)
+        with _lock:
+            if key not in _attached:                      # (a synchronous request may have overtaken a queued one)
+                _attached[key] = attach(image)
+            return _attached[key]
+    except (SpecialiseError, _native.NativeError) as e:
+        with _lock:
+            _failed.add(key)
+        import warnings
+        warnings.warn(f'{what} not specialised, the interpreter runs it: {e}')
+        return None
+    finally:
+        if queued:
+            with _lock:
+                _pending.pop(key, None)
+
+
 def ensure_control(description: list, background: bool = False):
     """the handle of the kernel specialised for this control-program structure (built and attached once per process), or None
-    while it is not available (no hipcc, a failed build, or -- `background` -- still being built)"""
-    key = tuple(description)
+    while it is not available (no hipcc, a failed build, or still being built in the background)"""
+    key = ('ctl',) + tuple(description)
     with _lock:
-        if key in _ctl_handles:
-            return _ctl_handles[key]
-        if key in _failed or key in _pending:
+        if key not in _attached and key in _pending:      # (being built: the interpreter runs it meanwhile, whoever asks)
             return None
     if description[0] == 0 or description[1] == 0:
         return None
+    words = list(description)
+    return _ensure(key, 'control program', lambda: _compile('control_program.hip', control_flags(words), 'ctl'),
+                   lambda image: _native.control_program_attach(words, image), background)
 
-    def make():
-        try:
-            image = _compile('control_program.hip', control_flags(description), 'ctl')
-            handle = _native.control_program_attach(list(description), image)
-        except (SpecialiseError, _native.NativeError) as e:
-            with _lock:
-                _failed.add(key)
-            import warnings
-            warnings.warn(f'control program not specialised, the interpreter runs it: {e}')
-            return None
-        with _lock:
-            _ctl_handles[key] = handle
-        return handle
-    if not background:
-        return make()
-    global _pool
-    with _lock:
-        if _pool is None:
-            import concurrent.futures
-            _pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix='sig-specialise')
 
-        def job():
-            try:
-                return make()
-            finally:
-                with _lock:
-                    _pending.pop(key, None)
-        _pending[key] = _pool.submit(job)
-    return None
+def _ensure_voice(background: bool, code: list, *sizes) -> bool:
+    code = list(code)                                     # (the caller's list may change while a queued build waits)
+    got = _ensure(('vp', tuple(code)) + sizes, 'voice program', lambda: build(code, *sizes),
+                  lambda image: _native.voice_program_attach(code, *sizes, image) or True, background)
+    return got is True
 
 
 def ensure(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, voices_per_lane: int, bus_channels: int) -> bool:
     """build (or load from the cache) and attach the specialised kernel for this program once per process; False when that is
     not possible here -- the caller's launches then run the interpreter"""
-    key = (tuple(code), n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels)
-    with _lock:
-        if key in _attached:
-            return True
-        if key in _failed:
-            return False
-    try:                                                  # (outside the lock: the compiler takes seconds)
-        image = build(code, n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels)
-        with _lock:
-            if key not in _attached:
-                _native.voice_program_attach(code, n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels, image)
-                _attached.add(key)
-    except (SpecialiseError, _native.NativeError) as e:
-        with _lock:
-            _failed.add(key)
-        import warnings
-        warnings.warn(f'voice program not specialised, the interpreter runs it: {e}')
-        return False
-    return True
-
-
-_pending: dict = {}
-_pool = None
+    return _ensure_voice(False, code, n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels)
 
 
 def ensure_in_background(code: list, n_oscs: int, n_params: int, n_filters: int, n_temps: int, voices_per_lane: int,
                          bus_channels: int) -> bool:
     """`ensure` on a worker thread: True once the kernel is attached, False while it is being built (or cannot be) -- the
     caller's launches run the interpreter until then, so a real-time sink never waits for the compiler"""
-    global _pool
-    key = (tuple(code), n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels)
-    with _lock:
-        if key in _attached:
-            return True
-        if key in _failed or key in _pending:
-            return False
-        if _pool is None:
-            import concurrent.futures
-            _pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix='sig-specialise')
-        _pending[key] = _pool.submit(_finish, key)
-        return False
-
-
-def _finish(key) -> bool:
-    try:
-        return ensure(list(key[0]), *key[1:])
-    finally:
-        with _lock:
-            _pending.pop(key, None)
+    return _ensure_voice(True, code, n_oscs, n_params, n_filters, n_temps, voices_per_lane, bus_channels)
 
 
 def wait() -> None:
@@ -218,9 +213,10 @@ def wait() -> None:
 
 
 def forget() -> None:
-    """detach every specialised kernel (tests)"""
+    """detach every specialised voice program (tests); attached control programs keep their handles"""
     wait()
     with _lock:
         _native.voice_program_detach_all()
-        _attached.clear()
+        for key in [k for k in _attached if k[0] == 'vp']:
+            del _attached[key]
         _failed.clear()
