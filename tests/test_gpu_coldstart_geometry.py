@@ -13,8 +13,8 @@ band.hip launch_band):
 The resonant and the equaliser entries have the plain kernel only, the band entries four voices or one.  The first geometry of
 each entry is also held against the CPU restatements (oracle/chain_ref.py, tests/resonant_reference.py, tests/eq_reference.py), at
 some voices of every lane group and the first, middle and last blocks, within the bound the entry's existing test uses; an error
-that every geometry shares does not get past that.  The bus entry sums voices in an order that depends on the geometry and stays
-with its own tests."""
+that every geometry shares does not get past that.  The bus entry sums voices in an order that depends on the geometry: it is
+called directly by tests/test_gpu_bus_pass.py."""
 import functools
 
 import numpy as np
