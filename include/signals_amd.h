@@ -226,6 +226,30 @@ int sig_delay_taps(int32_t rate, int64_t position, int32_t block_frames, int32_t
                    int32_t taps, const double* multiplier, const double* gain,
                    void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Dense FIR filter, chain/ext.py FIR (build-defined: every filter of the reference is recursive).  The window, the blocks and the
+ * buffers of sig_delay_taps: `nblocks` consecutive blocks of `block_frames` frames behind `context_rows` == min(SIG_FIR_CONTEXT,
+ * position) rows of context, `in` pointing at the window's FIRST row, float32 or float64 (in_stride == 0: one column broadcast over
+ * the voices); x[m] = +0 for an absolute frame m < 0: such rows are not read.  `taps` is a DEVICE array, float64 (table_taps,
+ * table_waves) row-major: table_waves impulse responses of table_taps = L taps each, 1 <= L <= SIG_FIR_MAX_TAPS, table_waves = W >= 1,
+ * L * W <= SIG_FIR_MAX_POINTS.  For block b, its row n and voice v, in f64, every operation rounded, the input widened exactly:
+ *   w   = clip(floor(select[b or 0, v]), 0, W - 1)                         (NULL = unplugged, NaN: column 0; once per block)
+ *   acc = taps[0, w] * x[n]
+ *   acc = acc + taps[k, w] * x[n - k]                                      (k = 1 .. L - 1, ascending)
+ *   out[n, v] = acc
+ * No tap is skipped: zero taps and the zero-filled rows are multiplied and added like the rest, so NaN and +-inf in the input
+ * propagate as they do in numpy; no status word.  `select`: f64 (1 | nblocks, voices | 1), select_blocks rows select_row_stride
+ * apart.  The float64 value in front of the store is bit-exact against numpy (tests/fir_reference.py).  float32 input is staged in LDS
+ * tiles of (SIG_FIR_TILE_ROWS + SIG_FIR_CONTEXT) x 64 voices beside the table; float64 input is gathered.  L outside 1 .. 101, W < 1,
+ * L * W > SIG_FIR_MAX_POINTS, context_rows > SIG_FIR_CONTEXT or != min(SIG_FIR_CONTEXT, position), a null in / out / taps,
+ * block_frames < 1, out_ld < voices or a stride other than 0 / 1: hipErrorInvalidValue, nothing launched; nblocks == 0 or
+ * voices == 0: no launch. */
+enum { SIG_FIR_CONTEXT = 100, SIG_FIR_MAX_TAPS = 101, SIG_FIR_MAX_POINTS = 4096, SIG_FIR_TILE_ROWS = 256 };
+int sig_fir_taps(int32_t rate, int64_t position, int32_t block_frames, int32_t nblocks, int32_t context_rows, int32_t voices,
+                 const void* in, int32_t in_dtype, int64_t in_ld, int32_t in_stride,
+                 const double* select, int32_t select_stride, int64_t select_row_stride, int32_t select_blocks,
+                 const double* taps, int32_t table_taps, int32_t table_waves,
+                 void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Sample playback, chain/ext.py Sampler (build-defined: the reference streams a file linearly and has no pitch, trigger or per-voice
  * start).  `table` float32 in device memory, COLUMN-major: table_waves recordings of table_frames frames, recording w contiguous at
  * table + w * table_frames (the transpose of the node's (T, W) state); T >= 2, W >= 1, T * W <= SIG_SAMPLER_MAX_POINTS.  loop_end == 0:

@@ -75,6 +75,9 @@ TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a
 DELAY_CONTEXT = 100                         # SIG_DELAY_CONTEXT: the rows of context in front of a delay line's block, the filters' window
 DELAY_MAX_FRAMES = 99                       # SIG_DELAY_MAX_FRAMES: the longest delay (ext.py Delay): the context minus the one further row the interpolation reads
 DELAY_MAX_TAPS = 16                         # SIG_DELAY_MAX_TAPS: taps of a delay line
+FIR_CONTEXT = 100                           # SIG_FIR_CONTEXT: the rows of context in front of a FIR filter's block, the filters' window
+FIR_MAX_TAPS = 101                          # SIG_FIR_MAX_TAPS: taps of a FIR filter (ext.py FIR): x[n - 100] .. x[n], the window a filter is handed
+FIR_MAX_POINTS = 4096                       # SIG_FIR_MAX_POINTS: taps x columns of a FIR filter's table
 SAMPLER_MAX_POINTS = 1 << 26                # SIG_SAMPLER_MAX_POINTS: frames x recordings of a sampler's table (ext.py Sampler), resident in HBM
 
 
@@ -142,6 +145,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_sync': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_shaper_table': [i64, i32, vp, i32, i64, i32, dp, i32, i64, i32, vp, i32, i32, vp, i32, i64, vp],
         'sig_delay_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, i32, dp, dp, vp, i32, i64, vp],
+        'sig_fir_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, dp, i32, i32, vp, i32, i64, vp],
         'sig_sampler_play': [i64, i64, i32, i64, i32, i32] + [dp, i32, i64] * 4 + [vp, i32, i32, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
@@ -537,6 +541,38 @@ def delay_taps(rate: int, position: int, block_frames: int, nblocks: int, window
     _check(lib().sig_delay_taps(rate, position, block_frames, nblocks, history, voices,
                                 window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
                                 tp, ts, trs, trows, *_taps(taps), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_delay_taps')
+    return out
+
+
+def _fir_table(table: torch.Tensor):
+    """(ptr, taps, columns) of a FIR filter's table: float64 (L, W) contiguous on the device, 1 <= L <= 101, W >= 1, L * W within the cap"""
+    if table is None or table.dtype != torch.float64 or table.dim() != 2 or not table.is_contiguous():
+        raise NativeError('a FIR table is a contiguous float64 (taps, columns) tensor')
+    taps, waves = table.shape
+    if not 1 <= taps <= FIR_MAX_TAPS or waves < 1 or taps * waves > FIR_MAX_POINTS:
+        raise NativeError(f'FIR table {tuple(table.shape)}: 1 <= taps <= {FIR_MAX_TAPS}, columns >= 1, taps * columns <= {FIR_MAX_POINTS}')
+    return table.data_ptr(), taps, waves
+
+
+def fir_taps(rate: int, position: int, block_frames: int, nblocks: int, window: torch.Tensor, history: int,
+             select: torch.Tensor | None, table: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[(nblocks * block_frames, voices)] <- dense FIR filter (sig_fir_taps; ext.py FIR): `window` holds `history` =
+    min(100, position) context rows, then one input row per row of `out`, float32 | float64 (rows, V | 1); row n of block b is
+    h[0, w] * x[n] + h[1, w] * x[n - 1] + ... + h[L - 1, w] * x[n - L + 1], summed in ascending k, with w = clip(floor(select[b]), 0,
+    W - 1) and x = 0 in front of absolute frame 0.  select: f64 (1 | nblocks, V | 1), None: unplugged = column 0; table: the (L, W)
+    float64 taps on the device."""
+    _gpu(window, select, table, out)
+    _audio(window, 'fir in')
+    _audio(out, 'fir out')
+    rows, voices = out.shape
+    if rows != block_frames * nblocks or window.shape[0] != history + rows or window.shape[1] not in (1, voices):
+        raise NativeError(f'fir shapes: in {tuple(window.shape)} history {history} out {tuple(out.shape)} blocks {nblocks}x{block_frames}')
+    sp, ss, srs, srows = _voice_rows(voices, (select, 'select'), form=_ctrl_rows)
+    if srows not in (1, nblocks):
+        raise NativeError(f'select has {srows} rows, launch needs 1 or {nblocks}')
+    _check(lib().sig_fir_taps(rate, position, block_frames, nblocks, history, voices,
+                              window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
+                              sp, ss, srs, srows, *_fir_table(table), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_fir_taps')
     return out
 
 

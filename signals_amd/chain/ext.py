@@ -599,6 +599,198 @@ class Delay(BlockCachingEmitter, ImplicitChannels):
         return _native.delay_taps(loc.rate, loc.position, shape.frames, 1, buf, history, time, self.host_taps(), out)
 
 
+def _validate_fir_taps(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and 1 <= new_value.shape[0] <= _native.FIR_MAX_TAPS and new_value.shape[1] >= 1
+          and new_value.shape[0] * new_value.shape[1] <= _native.FIR_MAX_POINTS
+          and bool(np.isfinite(new_value).all()))
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a finite 2D real array (taps, columns), 1 <= taps <= {_native.FIR_MAX_TAPS}, columns >= 1, '
+                            f'taps * columns <= {_native.FIR_MAX_POINTS}')
+
+
+def _fir_window(name: str, L: int) -> np.ndarray:
+    """the (L,) window of a windowed-sinc design, symmetric about (L - 1) / 2.  Blackman and Hann are sampled at (k + 1) / (L + 1), the
+    L interior points of the (L + 2)-point window: their end points are zeros, which would waste two of at most 101 taps"""
+    k = np.arange(L, dtype=np.float64)
+    if name in ('rectangular', 'boxcar', None):
+        return np.ones(L)
+    a = 2.0 * np.pi * (k + 1.0) / (L + 1.0)
+    if name == 'blackman':
+        return 0.42 - 0.5 * np.cos(a) + 0.08 * np.cos(2.0 * a)
+    if name == 'hann':
+        return 0.5 - 0.5 * np.cos(a)
+    if name == 'hamming':
+        return 0.54 - 0.46 * np.cos(2.0 * np.pi * k / (L - 1)) if L > 1 else np.ones(L)
+    raise ValueError(f'unknown window {name!r}: blackman, hamming, hann or rectangular')
+
+
+def _fir_mirror(h: np.ndarray, sign: float = 1.0) -> np.ndarray:
+    """the (L, 1) column whose second half is the first half mirrored (times `sign`), so that h[k] == sign * h[L - 1 - k] bit for bit"""
+    L = h.shape[0]
+    out = np.array(h, dtype=np.float64)
+    half = L // 2
+    out[L - half:] = sign * out[:half][::-1]
+    return out.reshape(L, 1)
+
+
+def _fir_sinc(cutoff: float, rate: float, L: int, window: str) -> np.ndarray:
+    """the windowed ideal low-pass of `cutoff` Hz, (L,), not normalised"""
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= _native.FIR_MAX_TAPS:
+        raise ValueError(f'taps must be an integer 1 .. {_native.FIR_MAX_TAPS}, got {L!r}')
+    if not (np.isfinite(cutoff) and np.isfinite(rate) and rate > 0 and 0 < cutoff < rate / 2):
+        raise ValueError(f'a cutoff lies inside (0, rate / 2), got {cutoff!r} at rate {rate!r}')
+    fc = float(cutoff) / float(rate)
+    m = np.arange(L, dtype=np.float64) - (L - 1) / 2.0
+    return 2.0 * fc * np.sinc(2.0 * fc * m) * _fir_window(window, L)
+
+
+class FIR(fx.CritFilter):
+    """Dense finite-impulse-response filter of up to 101 taps: the one filter class the block structure renders EXACTLY -- x[n - 100]
+    .. x[n] is precisely the window a filter is handed, so nothing of the impulse response is truncated, where every recursive
+    filter here answers a block from zero state over 100 context rows.  Linear-phase low-pass / high-pass / band-pass (crossovers and
+    band splits), a Hilbert transformer (with `Delay` at the group delay as the matched path: single-sideband frequency shifting,
+    `RingMod(Delay(x), cos) - RingMod(FIR_hilbert(x), sin)`), a differentiator, a pre-emphasis, a short body or cabinet response.
+    The state `taps` is an (L, W) real array, 1 <= L <= 101, W >= 1, L * W <= 4096, every value finite: W impulse responses of L taps,
+    column w = h[:, w]; integer arrays (what a .sigs value arrives as) are converted; the device copy is float64 and follows in-place
+    edits of the array.  The default [[1.0]] is the identity.  Ports: `input` at frame rate; `select` at block rate, read once per
+    block at the block's position like every control (unplugged, disabled or NaN: column 0).  Per voice v and block, in float64 and
+    every operation rounded (no fma), the input widened exactly:
+        w      = clip(floor(select[0, v]), 0, W - 1)
+        x[m]   = +0.0  for an absolute frame m < 0
+        acc    = h[0, w] * x[n]
+        acc    = acc + h[k, w] * x[n - k]        for k = 1 .. L - 1, ascending
+        out[n] = acc
+    (kernel: sig_fir_taps; restated in numpy by tests/fir_reference.py).  No tap is skipped: zero taps and the zero-filled rows are
+    multiplied and added like the rest, so NaN and +-inf in the input propagate exactly as the numpy restatement's do; no status bit
+    is set.  [[1.0]] returns the input and a unit tap at k = d the input d frames late, both bit for bit on finite input.
+    The node takes its window exactly as `Delay` does -- [<= 100 context rows | block | 100 rows after], the rows after discarded but
+    requested, so that upstream caches see what a filter would leave them -- and to the batched engine it IS a
+    filter: request-dependent, min(100, position) history rows, tails between batches, no batch of blocks <= 100 frames over an
+    impure input.  `input` of width 1 broadcasts; `select` or `input` narrower than the request but wider than 1 raises the
+    IndexError of a narrow `cutoff`.  Like `Ladder` it is an `fx.CritFilter` -- that class is what the engine's planner means by "takes
+    a filter's window" -- but not an `fx.SingleCritFilter` or `fx.DoubleCritFilter`: to the voice program and the fused matchers
+    those mean a biquad.  Its type is its own (`FIR.Type.fir`); it has no cutoff and no status word.
+    Designers (static, numpy on the host): `FIR.lowpass`, `FIR.highpass`, `FIR.bandpass`, `FIR.hilbert`; each returns an (L, 1)
+    float64 column, so a bank is an `np.hstack`.  A symmetric or antisymmetric design of L taps has the group delay (L - 1) / 2
+    frames at every frequency: 50 frames at the default 101 taps.
+    Out of scope: more than 101 taps (partitioned or FFT convolution, and a longer context than the block semantics have); a
+    frame-rate `select` and morphing between columns; float32 or matrix-core accumulation; an fma build of the sum (it would halve
+    the arithmetic and change the bits: not measured); the voice program, the specialised build and the fused kernels (a graph with
+    the node renders one kernel per node); the node inside a block-rate control path (the batched engine answers NotBatchable with
+    the reason and the graph keeps the eager path, which serves frames == 1 in float64); the random-graph generator of the tests."""
+    select: Receiver.BoundPort = port('select')
+
+    class Type(str, enum.Enum):
+        """the node's own filter type: no entry of the biquad kernels takes it"""
+        fir = 'fir'
+
+        def __str__(self) -> str:
+            return str(self.value)
+
+        @property
+        def is_band(self) -> bool:
+            return False
+
+    @state
+    class State(fx.CritFilter.State):
+        taps: np.ndarray = attr.ib(factory=lambda: np.array([[1.0]]), validator=_validate_fir_taps, on_setattr=attr.setters.validate)
+
+    def __init__(self):
+        super().__init__()
+        self._resident = None
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.EFFECT
+
+    def type(self) -> 'FIR.Type':
+        return self.Type.fir
+
+    def context_frames(self) -> int:
+        return _native.FIR_CONTEXT
+
+    def host_taps(self) -> np.ndarray:
+        """the (L, W) float64 array as the state holds it now"""
+        return np.ascontiguousarray(self._state.taps, dtype=np.float64)
+
+    def resident_table(self) -> torch.Tensor:
+        """the (L, W) float64 device copy of `taps`; an in-place edit or a replaced array is seen at the next render"""
+        taps = self._state.taps
+        held = self._resident
+        if held is None or held[0] is not taps or not held[1].matches(taps):
+            self._resident = held = (taps, HostSnapshot(taps), torch.from_numpy(self.host_taps().copy()).to(runtime.device()))
+        return held[2]
+
+    # ---- designers: numpy on the host, one (L, 1) float64 column each
+    @staticmethod
+    def lowpass(cutoff: float, rate: float, taps: int = 101, window: str = 'blackman') -> np.ndarray:
+        """windowed-sinc linear-phase low-pass, h[k] == h[L - 1 - k] bit for bit, unit gain at DC; group delay (L - 1) / 2 frames"""
+        h = _fir_mirror(_fir_sinc(cutoff, rate, taps, window))
+        return _fir_mirror(h[:, 0] / np.sum(h[:, 0]))
+
+    @staticmethod
+    def highpass(cutoff: float, rate: float, taps: int = 101, window: str = 'blackman') -> np.ndarray:
+        """the spectral inversion of `lowpass`: a unit tap at the centre minus the low-pass, so odd lengths only; zero gain at DC up to
+        rounding; group delay (L - 1) / 2 frames"""
+        if isinstance(taps, (int, np.integer)) and taps % 2 == 0:
+            raise ValueError(f'a high-pass needs an odd number of taps (a centre tap), got {taps}')
+        h = -FIR.lowpass(cutoff, rate, taps, window)
+        h[(taps - 1) // 2, 0] += 1.0
+        return h
+
+    @staticmethod
+    def bandpass(low: float, high: float, rate: float, taps: int = 101, window: str = 'blackman') -> np.ndarray:
+        """the difference of two windowed-sinc low-passes, mirrored, unit gain at the band's centre (low + high) / 2; group delay
+        (L - 1) / 2 frames"""
+        if not low < high:
+            raise ValueError(f'a band needs low < high, got {low!r}, {high!r}')
+        h = _fir_mirror(_fir_sinc(high, rate, taps, window) - _fir_sinc(low, rate, taps, window))[:, 0]
+        m = np.arange(taps, dtype=np.float64) - (taps - 1) / 2.0
+        centre = np.pi * (float(low) + float(high)) / float(rate)               # radians per frame
+        gain = np.sum(h * np.cos(centre * m))                                  # the zero-phase response of a symmetric h
+        if not abs(gain) > 0:
+            raise ValueError('the design has no gain at the band centre (too few taps for the band)')
+        return _fir_mirror(h / gain)
+
+    @staticmethod
+    def hilbert(taps: int = 101, window: str = 'blackman') -> np.ndarray:
+        """windowed ideal Hilbert transformer (a 90 degree phase shifter): h[c + m] = 2 / (pi m) for odd m, exactly 0 for even m (the
+        centre too), antisymmetric h[k] == -h[L - 1 - k] bit for bit; odd lengths only; group delay (L - 1) / 2 frames, so the matched
+        path is a delay of that many frames"""
+        if isinstance(taps, bool) or not isinstance(taps, (int, np.integer)) or not 1 <= taps <= _native.FIR_MAX_TAPS or taps % 2 == 0:
+            raise ValueError(f'a Hilbert transformer needs an odd number of taps 1 .. {_native.FIR_MAX_TAPS}, got {taps!r}')
+        c = (taps - 1) // 2
+        m = np.arange(taps) - c
+        h = np.zeros(taps)
+        odd = (m % 2) != 0
+        h[odd] = 2.0 / (np.pi * m[odd]) * _fir_window(window, taps)[odd]
+        return _fir_mirror(h, -1.0)
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
+        context_frames = self.context_frames()
+        window = self.input.forward_with_context(request, context_frames)
+        loc, shape = request.loc, request.loc.shape
+        for reply in (window, select):
+            if 1 < reply.shape[1] < shape.channels:
+                raise IndexError(f'index {reply.shape[1]} is out of bounds for axis 1 with size {reply.shape[1]}')
+        history = window.shape[0] - shape.frames - context_frames             # rows the `before` request returned
+        if history != min(context_frames, loc.position):
+            raise ValueError(f'could not broadcast input array from shape ({window.shape[0] - context_frames},) '
+                             f'into shape ({shape.frames},)')
+        buf = window[:history + shape.frames, :shape.channels]
+        if buf.dtype not in (torch.float32, torch.float64):
+            buf = buf.to(result_dtype(shape.frames))
+        select = select[:, :shape.channels]
+        if not select.is_contiguous():
+            select = select.contiguous()
+        voices = max(buf.shape[1], select.shape[1])
+        out = torch.empty((shape.frames, voices), dtype=result_dtype(shape.frames), device=buf.device)
+        return _native.fir_taps(loc.rate, loc.position, shape.frames, 1, buf, history, select, self.resident_table(), out)
+
+
 def _validate_recordings(instance, attribute, new_value):
     ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
           and new_value.shape[0] >= 2 and new_value.shape[1] >= 1

@@ -698,6 +698,8 @@ class _Batch:
         multiplied by the envelope and the buffer (history rows, tail) belongs to that RingMod node"""
         if isinstance(node, ext.Ladder):
             return self._ladder(node, channels, hist, rows)
+        if isinstance(node, ext.FIR):
+            return self._fir(node, channels, hist, rows)
         o = self.owner
         N, K, pos = self.N, self.K, self.pos
         band = isinstance(node, fx.DoubleCritFilter)
@@ -767,6 +769,26 @@ class _Batch:
                   lambda: _native.ladder_coldstart(self.rate, pos, N, K, CONTEXT, cutoff, k, drive, poles, window, c0, main, status=status),
                   units=N * K * channels)
         self._own_history(node, channels, hist, result)
+        return result
+
+    def _fir(self, node: ext.FIR, channels: int, hist: int, rows: int) -> torch.Tensor:
+        """the dense FIR filter: a filter's window (c0 = min(100, pos) context rows in front; the same NotBatchable for an impure input
+        at N <= 100), history rows and tails, one sig_fir_taps launch over the K blocks -- per-block select rows when that port is
+        modulated; the table is the node's resident copy.  A one-column input or select row broadcasts over the voices as a Delay's
+        does; a request-dependent one-column input is answered afresh for every context request on the eager path (`_delay_uncached`
+        has the story), which this schedule does not reproduce: NotBatchable, as `_ladder`"""
+        o, N, K, pos = self.owner, self.N, self.K, self.pos
+        select, window, c0 = self._filter_window(node, channels, self._control(node.select, 'select'), narrow_ok=True)
+        if window.shape[1] < channels and not _is_pure(node.input.sig, self._pure):
+            raise NotBatchable(f'{node.cls_name()} over a request-dependent input of one column (the eager path answers its context '
+                               f'requests afresh)')
+        table = node.resident_table()
+        cols = max(window.shape[1], select.shape[1])
+        result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=window.device)
+        main = result[hist:]
+        o._launch(f'fir_taps[{table.shape[0]}{",per-block" if select.shape[0] > 1 else ""}]',
+                  lambda: _native.fir_taps(self.rate, pos, N, K, window, c0, select, table, main), units=N * K * cols)
+        self._own_history(node, cols, hist, result)
         return result
 
     def _own_history(self, node: Emitter, channels: int, hist: int, result: torch.Tensor) -> None:

@@ -37,6 +37,9 @@ _NO_BLOCK_RATE = (
 def _no_block_rate(node: Emitter, route: str, window: bool = False) -> str | None:
     """the refusal of a node of _NO_BLOCK_RATE in a control path, None for any other node; `route`: 'program' | 'schedule', what
     the refusing site would have run; `window`: inside a control filter's input, where a frame-rate input has its own wording"""
+    if isinstance(node, ext.FIR):                              # a branch of its own, like the band filters': the table's families are pinned
+        return (f'{node.cls_name()} in a control path: a FIR filter has no block-rate {route} -- the eager node serves '
+                f'one-frame requests')
     for family, phrase, why in _NO_BLOCK_RATE:
         if isinstance(node, family):
             if window and family is ext.PMOsc:                 # (its modulator would have to be a window-rate input)
@@ -72,6 +75,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.select]
     if isinstance(node, ext.Delay):
         return [node.time]
+    if isinstance(node, ext.FIR):
+        return [node.select]
     if isinstance(node, ext.Sampler):
         return [node.ratio, node.offset, node.gate_on, node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
