@@ -428,15 +428,23 @@ def osc_bank_pm(kind: str, position: int, rate: int, hertz: torch.Tensor, phase:
     return out
 
 
+def _device_table(table: torch.Tensor, dtype, what: str, axes: str, fits, limits: str) -> tuple:
+    """(ptr, rows, columns) of a table a kernel reads: a contiguous 2-D device tensor of `dtype` with `fits(rows, columns)`; `what` and
+    `axes` name it in the first refusal, `limits` (a format of shape, rows, cols) is the second"""
+    if table is None or table.dtype != dtype or table.dim() != 2 or not table.is_contiguous():
+        raise NativeError(f'{what} is a contiguous {str(dtype).split(".")[-1]} ({axes}) tensor')
+    rows, cols = table.shape
+    if not fits(rows, cols):
+        raise NativeError(limits.format(shape=tuple(table.shape), rows=rows, cols=cols))
+    return table.data_ptr(), rows, cols
+
+
 def _table(table: torch.Tensor, pow2: bool = True):
     """(ptr, points, waves) of a wavetable: float32 (T, W) contiguous on the device, T a power of two >= 2, T * W within the cap;
     `pow2` False: a shaper's table, any T >= 2"""
-    if table is None or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
-        raise NativeError('a wavetable is a contiguous float32 (points, waves) tensor')
-    points, waves = table.shape
-    if points < 2 or (pow2 and points & (points - 1)) or waves < 1 or points * waves > TABLE_MAX_POINTS:
-        raise NativeError(f'table {tuple(table.shape)}: points {"a power of two " if pow2 else ""}>= 2, points * waves <= {TABLE_MAX_POINTS}')
-    return table.data_ptr(), points, waves
+    return _device_table(table, torch.float32, 'a wavetable', 'points, waves',
+                         lambda T, W: T >= 2 and not (pow2 and T & (T - 1)) and W >= 1 and T * W <= TABLE_MAX_POINTS,
+                         f'table {{shape}}: points {"a power of two " if pow2 else ""}>= 2, points * waves <= {TABLE_MAX_POINTS}')
 
 
 def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, select: torch.Tensor | None,
@@ -449,14 +457,20 @@ def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.T
     return out
 
 
-def _copies(copies) -> tuple:
-    """(U, detune, offsets) of a unison oscillator's (U, 2) `copies` array: two host arrays of U doubles the launch takes by value"""
+def _pairs_by_value(pairs, cap: int, what: str, columns: str) -> tuple:
+    """(U, first column, second column) of a host (U, 2) array, 1 <= U <= cap, every value finite: two arrays of U doubles a launch
+    takes by value"""
     import numpy as np
-    c = np.asarray(copies, dtype=np.float64)
-    if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= UNISON_MAX_COPIES or not np.isfinite(c).all():
-        raise NativeError(f'unison copies must be a finite (1..{UNISON_MAX_COPIES}, 2) array of (detune, phase offset) rows, got shape {c.shape}')
+    c = np.asarray(pairs, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= cap or not np.isfinite(c).all():
+        raise NativeError(f'{what} must be a finite (1..{cap}, 2) array of {columns} rows, got shape {c.shape}')
     U = c.shape[0]
     return U, (ctypes.c_double * U)(*c[:, 0].tolist()), (ctypes.c_double * U)(*c[:, 1].tolist())
+
+
+def _copies(copies) -> tuple:
+    """(U, detune, offsets) of a unison oscillator's (U, 2) `copies` array"""
+    return _pairs_by_value(copies, UNISON_MAX_COPIES, 'unison copies', '(detune, phase offset)')
 
 
 def _osc_bank_copies(entry: str, kind: str, position: int, rate: int, copies, out, step: int, rows_per_param: int, *named):
@@ -513,13 +527,28 @@ def shaper_table(x: torch.Tensor, select: torch.Tensor | None, table: torch.Tens
 
 
 def _taps(taps) -> tuple:
-    """(U, multipliers, gains) of a delay line's (U, 2) `taps` array: two host arrays of U doubles the launch takes by value"""
-    import numpy as np
-    c = np.asarray(taps, dtype=np.float64)
-    if c.ndim != 2 or c.shape[1] != 2 or not 1 <= c.shape[0] <= DELAY_MAX_TAPS or not np.isfinite(c).all():
-        raise NativeError(f'delay taps must be a finite (1..{DELAY_MAX_TAPS}, 2) array of (multiplier, gain) rows, got shape {c.shape}')
-    U = c.shape[0]
-    return U, (ctypes.c_double * U)(*c[:, 0].tolist()), (ctypes.c_double * U)(*c[:, 1].tolist())
+    """(U, multipliers, gains) of a delay line's (U, 2) `taps` array"""
+    return _pairs_by_value(taps, DELAY_MAX_TAPS, 'delay taps', '(multiplier, gain)')
+
+
+def _window_launch(what: str, rate: int, position: int, block_frames: int, nblocks: int, window: torch.Tensor, history: int,
+                   control: torch.Tensor | None, name: str, out: torch.Tensor, also=()):
+    """what the window nodes' launches (sig_delay_taps, sig_fir_taps) marshal the same way, from `window` (`history` = min(100,
+    position) context rows, then one input row per row of `out`, float32 | float64 (rows, V | 1)) and the per-block control row
+    `control` (f64 (1 | nblocks, V | 1), None: unplugged), called `name`: (head, tail) -- head = every argument up to the control row's
+    block count, tail = (out, dtype, ld, stream); the entry's own operands go between.  `also`: further tensors that must be on the GPU"""
+    _gpu(window, control, *also, out)
+    _audio(window, f'{what} in')
+    _audio(out, f'{what} out')
+    rows, voices = out.shape
+    if rows != block_frames * nblocks or window.shape[0] != history + rows or window.shape[1] not in (1, voices):
+        raise NativeError(f'{what} shapes: in {tuple(window.shape)} history {history} out {tuple(out.shape)} blocks {nblocks}x{block_frames}')
+    ptr, stride, row_stride, blocks = _voice_rows(voices, (control, name), form=_ctrl_rows)
+    if blocks not in (1, nblocks):
+        raise NativeError(f'{name} has {blocks} rows, launch needs 1 or {nblocks}')
+    return ((rate, position, block_frames, nblocks, history, voices,
+             window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1, ptr, stride, row_stride, blocks),
+            (out.data_ptr(), _dt(out), out.stride(0), _stream(out)))
 
 
 def delay_taps(rate: int, position: int, block_frames: int, nblocks: int, window: torch.Tensor, history: int,
@@ -529,29 +558,16 @@ def delay_taps(rate: int, position: int, block_frames: int, nblocks: int, window
     sum_u g_u * (x[n - i_u] + f_u * (x[n - i_u - 1] - x[n - i_u])) with d_u = clip(time[b] * rate * m_u, 0, 99) = i_u + f_u, x = 0
     in front of absolute frame 0.  time: f64 (1 | nblocks, V | 1) seconds, None: unplugged = 0; taps: a host (U, 2) array of
     (m_u, g_u) rows, by value."""
-    _gpu(window, time, out)
-    _audio(window, 'delay in')
-    _audio(out, 'delay out')
-    rows, voices = out.shape
-    if rows != block_frames * nblocks or window.shape[0] != history + rows or window.shape[1] not in (1, voices):
-        raise NativeError(f'delay shapes: in {tuple(window.shape)} history {history} out {tuple(out.shape)} blocks {nblocks}x{block_frames}')
-    tp, ts, trs, trows = _voice_rows(voices, (time, 'time'), form=_ctrl_rows)
-    if trows not in (1, nblocks):
-        raise NativeError(f'time has {trows} rows, launch needs 1 or {nblocks}')
-    _check(lib().sig_delay_taps(rate, position, block_frames, nblocks, history, voices,
-                                window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
-                                tp, ts, trs, trows, *_taps(taps), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_delay_taps')
+    head, tail = _window_launch('delay', rate, position, block_frames, nblocks, window, history, time, 'time', out)
+    _check(lib().sig_delay_taps(*head, *_taps(taps), *tail), 'sig_delay_taps')
     return out
 
 
 def _fir_table(table: torch.Tensor):
     """(ptr, taps, columns) of a FIR filter's table: float64 (L, W) contiguous on the device, 1 <= L <= 101, W >= 1, L * W within the cap"""
-    if table is None or table.dtype != torch.float64 or table.dim() != 2 or not table.is_contiguous():
-        raise NativeError('a FIR table is a contiguous float64 (taps, columns) tensor')
-    taps, waves = table.shape
-    if not 1 <= taps <= FIR_MAX_TAPS or waves < 1 or taps * waves > FIR_MAX_POINTS:
-        raise NativeError(f'FIR table {tuple(table.shape)}: 1 <= taps <= {FIR_MAX_TAPS}, columns >= 1, taps * columns <= {FIR_MAX_POINTS}')
-    return table.data_ptr(), taps, waves
+    return _device_table(table, torch.float64, 'a FIR table', 'taps, columns',
+                         lambda L, W: 1 <= L <= FIR_MAX_TAPS and W >= 1 and L * W <= FIR_MAX_POINTS,
+                         f'FIR table {{shape}}: 1 <= taps <= {FIR_MAX_TAPS}, columns >= 1, taps * columns <= {FIR_MAX_POINTS}')
 
 
 def fir_taps(rate: int, position: int, block_frames: int, nblocks: int, window: torch.Tensor, history: int,
@@ -561,18 +577,8 @@ def fir_taps(rate: int, position: int, block_frames: int, nblocks: int, window: 
     h[0, w] * x[n] + h[1, w] * x[n - 1] + ... + h[L - 1, w] * x[n - L + 1], summed in ascending k, with w = clip(floor(select[b]), 0,
     W - 1) and x = 0 in front of absolute frame 0.  select: f64 (1 | nblocks, V | 1), None: unplugged = column 0; table: the (L, W)
     float64 taps on the device."""
-    _gpu(window, select, table, out)
-    _audio(window, 'fir in')
-    _audio(out, 'fir out')
-    rows, voices = out.shape
-    if rows != block_frames * nblocks or window.shape[0] != history + rows or window.shape[1] not in (1, voices):
-        raise NativeError(f'fir shapes: in {tuple(window.shape)} history {history} out {tuple(out.shape)} blocks {nblocks}x{block_frames}')
-    sp, ss, srs, srows = _voice_rows(voices, (select, 'select'), form=_ctrl_rows)
-    if srows not in (1, nblocks):
-        raise NativeError(f'select has {srows} rows, launch needs 1 or {nblocks}')
-    _check(lib().sig_fir_taps(rate, position, block_frames, nblocks, history, voices,
-                              window.data_ptr(), _dt(window), window.stride(0), 0 if window.shape[1] == 1 else 1,
-                              sp, ss, srs, srows, *_fir_table(table), out.data_ptr(), _dt(out), out.stride(0), _stream(out)), 'sig_fir_taps')
+    head, tail = _window_launch('fir', rate, position, block_frames, nblocks, window, history, select, 'select', out, also=(table,))
+    _check(lib().sig_fir_taps(*head, *_fir_table(table), *tail), 'sig_fir_taps')
     return out
 
 
@@ -585,13 +591,11 @@ def sampler_play(position: int, rate: int, ratio: torch.Tensor | None, offset: t
     recordings of T frames, each contiguous (the transpose of the node's state).  ratio / offset / gate_on / select: (1|P, V|1) f64
     like `osc_bank`, None: unplugged = 0."""
     named = ((ratio, 'ratio'), (offset, 'offset'), (gate_on, 'gate_on'), (select, 'select'))
-    if table is None or table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
-        raise NativeError('a sampler table is a contiguous float32 (recordings, frames) tensor')
-    waves, frames = table.shape
-    if frames < 2 or waves < 1 or frames * waves > SAMPLER_MAX_POINTS:
-        raise NativeError(f'sampler table of {frames} frames x {waves} recordings: frames >= 2, frames * recordings <= {SAMPLER_MAX_POINTS}')
+    ptr, waves, frames = _device_table(table, torch.float32, 'a sampler table', 'recordings, frames',
+                                       lambda W, T: T >= 2 and W >= 1 and T * W <= SAMPLER_MAX_POINTS,
+                                       f'sampler table of {{cols}} frames x {{rows}} recordings: frames >= 2, frames * recordings <= {SAMPLER_MAX_POINTS}')
     head, rows, tail = _osc_launch(out, position, step, rate, rows_per_param, *named, also=(table,))
-    _check(lib().sig_sampler_play(*head, *(x for row in rows for x in row), table.data_ptr(), frames, waves, loop_start, loop_end, *tail),
+    _check(lib().sig_sampler_play(*head, *(x for row in rows for x in row), ptr, frames, waves, loop_start, loop_end, *tail),
            'sig_sampler_play')
     return out
 

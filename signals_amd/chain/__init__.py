@@ -35,6 +35,7 @@ from signals_amd.chain.nodes import (  # noqa: F401
     ImplicitChannels,
     PassThroughResult,
     Receiver,
+    ResidentCopy,
     Signal,
     adopt_reply,
     as_control,

@@ -15,11 +15,11 @@ from signals_amd.chain import fx
 from signals_amd.chain import (
     BadStateValue,
     BlockCachingEmitter,
-    HostSnapshot,
     ImplicitChannels,
     PassThroughResult,
     Receiver,
     Request,
+    ResidentCopy,
     as_control,
     broadcast_shape,
     port,
@@ -45,7 +45,7 @@ class SumBus(BlockCachingEmitter, Receiver):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float64)
 
     @classmethod
     def flags(cls) -> SignalFlags:
@@ -58,13 +58,7 @@ class SumBus(BlockCachingEmitter, Receiver):
 
     def resident_gains(self) -> typing.Optional[torch.Tensor]:
         gains = self._state.gains
-        if gains is None:
-            return None
-        held = self._resident
-        if held is None or held[0] is not gains or not held[1].matches(gains):
-            host = np.ascontiguousarray(gains, dtype=np.float64)
-            self._resident = held = (gains, HostSnapshot(gains), torch.from_numpy(host.copy()).to(runtime.device()))
-        return held[2]
+        return None if gains is None else self._resident.of(gains)
 
     def _eval(self, request: Request) -> torch.Tensor:
         voices = self.input.channels
@@ -206,19 +200,14 @@ class Wavetable(BlockCachingEmitter, ImplicitChannels):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float32)
 
     @classmethod
     def flags(cls) -> SignalFlags:
         return super().flags() | SignalFlags.GENERATOR
 
     def resident_table(self) -> torch.Tensor:
-        table = self._state.table
-        held = self._resident
-        if held is None or held[0] is not table or not held[1].matches(table):
-            host = np.ascontiguousarray(table, dtype=np.float32)
-            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
-        return held[2]
+        return self._resident.of(self._state.table)
 
     def _eval(self, request: Request) -> torch.Tensor:
         phase = as_control(self.phase.forward_at_block_rate(request))
@@ -499,19 +488,14 @@ class Shaper(BlockCachingEmitter, ImplicitChannels):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float32)
 
     @classmethod
     def flags(cls) -> SignalFlags:
         return super().flags() | SignalFlags.EFFECT
 
     def resident_table(self) -> torch.Tensor:
-        table = self._state.table
-        held = self._resident
-        if held is None or held[0] is not table or not held[1].matches(table):
-            host = np.ascontiguousarray(table, dtype=np.float32)
-            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
-        return held[2]
+        return self._resident.of(self._state.table)
 
     def _eval(self, request: Request) -> torch.Tensor:
         select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
@@ -521,6 +505,33 @@ class Shaper(BlockCachingEmitter, ImplicitChannels):
         frames, voices = broadcast_shape(x.shape, select.shape)
         out = torch.empty((frames, voices), dtype=result_dtype(frames), device=select.device)
         return _native.shaper_table(x, select, self.resident_table(), out)
+
+
+def _window_eval(node, request: Request, control: torch.Tensor, launch) -> torch.Tensor:
+    """One block of a window node (Delay, FIR): `input` is asked for a filter's window -- [<= 100 context rows | block | 100 rows after],
+    the rows after requested and discarded -- and `launch(rate, position, frames, 1, window, history, control, out=...)` renders the
+    block from its first history + frames rows.  `control`: the node's block-rate control reply; it and the window broadcast from width
+    1, narrower than the request otherwise is the IndexError of a narrow `cutoff`; a window that lacks its context rows is the
+    reference's ValueError"""
+    context_frames = node.context_frames()
+    window = node.input.forward_with_context(request, context_frames)
+    loc, shape = request.loc, request.loc.shape
+    for reply in (window, control):
+        if 1 < reply.shape[1] < shape.channels:
+            raise IndexError(f'index {reply.shape[1]} is out of bounds for axis 1 with size {reply.shape[1]}')
+    history = window.shape[0] - shape.frames - context_frames             # rows the `before` request returned
+    if history != min(context_frames, loc.position):
+        raise ValueError(f'could not broadcast input array from shape ({window.shape[0] - context_frames},) '
+                         f'into shape ({shape.frames},)')
+    buf = window[:history + shape.frames, :shape.channels]
+    if buf.dtype not in (torch.float32, torch.float64):
+        buf = buf.to(result_dtype(shape.frames))
+    control = control[:, :shape.channels]
+    if not control.is_contiguous():
+        control = control.contiguous()
+    voices = max(buf.shape[1], control.shape[1])
+    out = torch.empty((shape.frames, voices), dtype=result_dtype(shape.frames), device=buf.device)
+    return launch(loc.rate, loc.position, shape.frames, 1, buf, history, control, out=out)
 
 
 def _validate_taps(instance, attribute, new_value):
@@ -578,25 +589,7 @@ class Delay(BlockCachingEmitter, ImplicitChannels):
 
     def _eval(self, request: Request) -> torch.Tensor:
         time = as_control(self.time.forward_at_block_rate(request))            # unplugged: zeros((1, 1)), no delay
-        context_frames = self.context_frames()
-        window = self.input.forward_with_context(request, context_frames)
-        loc, shape = request.loc, request.loc.shape
-        for reply in (window, time):
-            if 1 < reply.shape[1] < shape.channels:
-                raise IndexError(f'index {reply.shape[1]} is out of bounds for axis 1 with size {reply.shape[1]}')
-        history = window.shape[0] - shape.frames - context_frames             # rows the `before` request returned
-        if history != min(context_frames, loc.position):
-            raise ValueError(f'could not broadcast input array from shape ({window.shape[0] - context_frames},) '
-                             f'into shape ({shape.frames},)')
-        buf = window[:history + shape.frames, :shape.channels]
-        if buf.dtype not in (torch.float32, torch.float64):
-            buf = buf.to(result_dtype(shape.frames))
-        time = time[:, :shape.channels]
-        if not time.is_contiguous():
-            time = time.contiguous()
-        voices = max(buf.shape[1], time.shape[1])
-        out = torch.empty((shape.frames, voices), dtype=result_dtype(shape.frames), device=buf.device)
-        return _native.delay_taps(loc.rate, loc.position, shape.frames, 1, buf, history, time, self.host_taps(), out)
+        return _window_eval(self, request, time, lambda *head, out: _native.delay_taps(*head, self.host_taps(), out))
 
 
 def _validate_fir_taps(instance, attribute, new_value):
@@ -699,7 +692,7 @@ class FIR(fx.CritFilter):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float64)
 
     @classmethod
     def flags(cls) -> SignalFlags:
@@ -717,11 +710,7 @@ class FIR(fx.CritFilter):
 
     def resident_table(self) -> torch.Tensor:
         """the (L, W) float64 device copy of `taps`; an in-place edit or a replaced array is seen at the next render"""
-        taps = self._state.taps
-        held = self._resident
-        if held is None or held[0] is not taps or not held[1].matches(taps):
-            self._resident = held = (taps, HostSnapshot(taps), torch.from_numpy(self.host_taps().copy()).to(runtime.device()))
-        return held[2]
+        return self._resident.of(self._state.taps)
 
     # ---- designers: numpy on the host, one (L, 1) float64 column each
     @staticmethod
@@ -770,25 +759,7 @@ class FIR(fx.CritFilter):
 
     def _eval(self, request: Request) -> torch.Tensor:
         select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
-        context_frames = self.context_frames()
-        window = self.input.forward_with_context(request, context_frames)
-        loc, shape = request.loc, request.loc.shape
-        for reply in (window, select):
-            if 1 < reply.shape[1] < shape.channels:
-                raise IndexError(f'index {reply.shape[1]} is out of bounds for axis 1 with size {reply.shape[1]}')
-        history = window.shape[0] - shape.frames - context_frames             # rows the `before` request returned
-        if history != min(context_frames, loc.position):
-            raise ValueError(f'could not broadcast input array from shape ({window.shape[0] - context_frames},) '
-                             f'into shape ({shape.frames},)')
-        buf = window[:history + shape.frames, :shape.channels]
-        if buf.dtype not in (torch.float32, torch.float64):
-            buf = buf.to(result_dtype(shape.frames))
-        select = select[:, :shape.channels]
-        if not select.is_contiguous():
-            select = select.contiguous()
-        voices = max(buf.shape[1], select.shape[1])
-        out = torch.empty((shape.frames, voices), dtype=result_dtype(shape.frames), device=buf.device)
-        return _native.fir_taps(loc.rate, loc.position, shape.frames, 1, buf, history, select, self.resident_table(), out)
+        return _window_eval(self, request, select, lambda *head, out: _native.fir_taps(*head, self.resident_table(), out))
 
 
 def _validate_recordings(instance, attribute, new_value):
@@ -864,7 +835,7 @@ class Sampler(BlockCachingEmitter, ImplicitChannels):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float32, layout=np.transpose)
 
     @classmethod
     def flags(cls) -> SignalFlags:
@@ -892,12 +863,7 @@ class Sampler(BlockCachingEmitter, ImplicitChannels):
 
     def resident_table(self) -> torch.Tensor:
         """the device copy: float32 (W, T), every recording contiguous -- the transpose of the state's array"""
-        table = self._state.table
-        held = self._resident
-        if held is None or held[0] is not table or not held[1].matches(table):
-            host = np.ascontiguousarray(np.asarray(table, dtype=np.float32).T)
-            self._resident = held = (table, HostSnapshot(table), torch.from_numpy(host.copy()).to(runtime.device()))
-        return held[2]
+        return self._resident.of(self._state.table)
 
     def control_rows(self, fetch, channels: int) -> list:
         """the four control rows (ratio, offset, gate_on, select) as contiguous float64 rows at most `channels` wide"""
@@ -1184,7 +1150,7 @@ class MixMatrix(BlockCachingEmitter, Receiver):
 
     def __init__(self):
         super().__init__()
-        self._resident = None
+        self._resident = ResidentCopy(np.float32)
 
     @classmethod
     def flags(cls) -> SignalFlags:
@@ -1195,12 +1161,7 @@ class MixMatrix(BlockCachingEmitter, Receiver):
         return self.input.channels
 
     def resident_matrix(self) -> torch.Tensor:
-        matrix = self._state.matrix
-        held = self._resident
-        if held is None or held[0] is not matrix or not held[1].matches(matrix):
-            host = np.ascontiguousarray(matrix, dtype=np.float32)
-            self._resident = held = (matrix, HostSnapshot(matrix), torch.from_numpy(host.copy()).to(runtime.device()))
-        return held[2]
+        return self._resident.of(self._state.matrix)
 
     def _eval(self, request: Request) -> torch.Tensor:
         x = self.input.forward(request)

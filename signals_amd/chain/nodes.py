@@ -61,6 +61,32 @@ class HostSnapshot:
         return np.ascontiguousarray(value).tobytes() == self.data.tobytes()
 
 
+def upload(host: np.ndarray) -> torch.Tensor:
+    """the device tensor of a host array (which the tensor may go on sharing where the render device is the CPU)"""
+    return torch.from_numpy(host).to(runtime.device())
+
+
+class ResidentCopy:
+    """The device copy of a host array that a node's state holds (bus gains, a table, a mix matrix), as `dtype` and -- `layout`: a
+    step from the converted array to the one to upload, a transpose for instance -- C-contiguous.  `of(array)` answers the copy it
+    holds while the state holds the same array object with the same bytes (`HostSnapshot`), and uploads anew otherwise: an in-place
+    edit or a replaced array is seen at the next render, an untouched array is not uploaded again."""
+    __slots__ = ('dtype', 'layout', 'held')
+
+    def __init__(self, dtype, layout=None):
+        self.dtype, self.layout = dtype, layout
+        self.held = None                                            # (source array, host snapshot, device tensor)
+
+    def of(self, value: np.ndarray) -> torch.Tensor:
+        held = self.held
+        if held is None or held[0] is not value or not held[1].matches(value):
+            host = np.asarray(value, dtype=self.dtype)
+            if self.layout is not None:
+                host = self.layout(host)
+            self.held = held = (value, HostSnapshot(value), upload(np.array(host, order='C')))       # (np.array: a copy of its own)
+        return held[2]
+
+
 class _Port(property):
     pass
 

@@ -260,22 +260,15 @@ class _Batch:
         return result
 
     def _sched_delay(self, node, channels, hist, rows):
-        """a delay line: the input window of a filter (c0 = min(100, pos) context rows in front; the same NotBatchable for an impure
-        input at N <= 100), one sig_delay_taps launch over the K blocks -- per-block time rows when that port is modulated -- and the
-        node's own history rows from the tail or a fresh block, like `_filter`; the taps go with the launch by value"""
-        o, N, K, pos = self.owner, self.N, self.K, self.pos
-        time, window, c0 = self._filter_window(node, channels, self._control(node.time, 'time'), narrow_ok=True)
+        """a delay line: a window node (`_window_node`), one sig_delay_taps launch over the K blocks -- per-block time rows when that port
+        is modulated; the taps go with the launch by value.  A request-dependent one-column input: `_delay_uncached`"""
         taps = node.host_taps()
-        cols = max(window.shape[1], time.shape[1])
-        result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=window.device)
-        main = result[hist:]
-        if window.shape[1] < channels and not _is_pure(node.input.sig, self._pure):
-            self._delay_uncached(node, channels, window[c0:], time, taps, main)
-        else:
-            o._launch(f'delay_taps[{taps.shape[0]}{",per-block" if time.shape[0] > 1 else ""}]',
-                      lambda: _native.delay_taps(self.rate, pos, N, K, window, c0, time, taps, main), units=N * K * cols)
-        self._own_history(node, cols, hist, result)
-        return result
+
+        def bind(window, c0, time, main):
+            return (f'delay_taps[{taps.shape[0]}{",per-block" if time.shape[0] > 1 else ""}]',
+                    lambda: _native.delay_taps(self.rate, self.pos, self.N, self.K, window, c0, time, taps, main))
+        return self._window_node(node, channels, hist, rows, self._control(node.time, 'time'), bind,
+                                 uncached=lambda blocks, time, main: self._delay_uncached(node, channels, blocks, time, taps, main))
 
     def _delay_uncached(self, node, channels, blocks, time, taps, main):
         """a Delay over a request-dependent input that answers ONE column to a wider request.  The block cache files a reply under the
@@ -745,51 +738,54 @@ class _Batch:
         self._own_history(owner_node or node, channels, hist, result)
         return result
 
-    def _ladder(self, node: ext.Ladder, channels: int, hist: int, rows: int) -> torch.Tensor:
-        """the 4-pole ladder: a filter's window, history rows and tails, one sig_ladder_coldstart launch over the K blocks; the cutoff,
-        the resonance and the drive rows each per block on their own when that port is modulated, the last two None when unplugged.
-        A one-column input broadcasts over the voices where it is position-pure; a request-dependent one is answered afresh for every
-        context request on the eager path (chain/cache.py files a reply under its own shape; `_delay_uncached`), which this schedule
-        does not reproduce: NotBatchable"""
-        o, N, K, pos = self.owner, self.N, self.K, self.pos
-        cutoff, window, c0 = self._filter_window(node, channels, self._narrow(self._control(node.cutoff, 'cutoff'), channels), narrow_ok=True)
-        if window.shape[1] < channels:
-            if not _is_pure(node.input.sig, self._pure):
-                raise NotBatchable(f'{node.cls_name()} over a request-dependent input of one column (the eager path answers its context '
-                                   f'requests afresh)')
-            window = window.expand(-1, channels).contiguous()
-        k, drive = (None if row is None else self._narrow(row, channels)
-                    for row in node.control_rows(lambda bound: self._control(bound, bound.name)))
-        poles = int(node.get_state().poles)
-        swept = any(row is not None and row.shape[0] > 1 for row in (cutoff, k, drive))
-        result = torch.empty((rows, channels), dtype=AUDIO_DTYPE, device=window.device)
-        main = result[hist:]
-        status = o._status_word(node)
-        o._launch(f'ladder_coldstart[{poles}{",drive" if drive is not None else ""}{",blocks" if swept else ""}]',
-                  lambda: _native.ladder_coldstart(self.rate, pos, N, K, CONTEXT, cutoff, k, drive, poles, window, c0, main, status=status),
-                  units=N * K * channels)
-        self._own_history(node, channels, hist, result)
-        return result
-
-    def _fir(self, node: ext.FIR, channels: int, hist: int, rows: int) -> torch.Tensor:
-        """the dense FIR filter: a filter's window (c0 = min(100, pos) context rows in front; the same NotBatchable for an impure input
-        at N <= 100), history rows and tails, one sig_fir_taps launch over the K blocks -- per-block select rows when that port is
-        modulated; the table is the node's resident copy.  A one-column input or select row broadcasts over the voices as a Delay's
-        does; a request-dependent one-column input is answered afresh for every context request on the eager path (`_delay_uncached`
-        has the story), which this schedule does not reproduce: NotBatchable, as `_ladder`"""
-        o, N, K, pos = self.owner, self.N, self.K, self.pos
-        select, window, c0 = self._filter_window(node, channels, self._control(node.select, 'select'), narrow_ok=True)
-        if window.shape[1] < channels and not _is_pure(node.input.sig, self._pure):
-            raise NotBatchable(f'{node.cls_name()} over a request-dependent input of one column (the eager path answers its context '
-                               f'requests afresh)')
-        table = node.resident_table()
-        cols = max(window.shape[1], select.shape[1])
+    def _window_node(self, node, channels: int, hist: int, rows: int, control: torch.Tensor, bind, uncached=None) -> torch.Tensor:
+        """the schedule of a node that takes a filter's window and one launch over the K blocks (ext.Delay, ext.FIR, ext.Ladder): the
+        window with c0 = min(100, pos) context rows in front (`_filter_window`: the same NotBatchable for an impure input at N <= 100),
+        the result as wide as the window and the first control row `control` broadcast, `bind(window, c0, control, main) -> (label,
+        launch)` for rows [hist:], and the node's own history rows from the tail or a fresh block (`_own_history`).  A one-column
+        input or control row broadcasts over the voices.  A request-dependent one-column input is answered afresh for every context
+        request on the eager path (`_delay_uncached` has the story): `uncached(blocks, control, main)` renders that, without one the
+        schedule does not reproduce it: NotBatchable"""
+        control, window, c0 = self._filter_window(node, channels, control, narrow_ok=True)
+        cols = max(window.shape[1], control.shape[1])
         result = torch.empty((rows, cols), dtype=AUDIO_DTYPE, device=window.device)
         main = result[hist:]
-        o._launch(f'fir_taps[{table.shape[0]}{",per-block" if select.shape[0] > 1 else ""}]',
-                  lambda: _native.fir_taps(self.rate, pos, N, K, window, c0, select, table, main), units=N * K * cols)
+        if window.shape[1] < channels and not _is_pure(node.input.sig, self._pure):
+            if uncached is None:
+                raise NotBatchable(f'{node.cls_name()} over a request-dependent input of one column (the eager path answers its context '
+                                   f'requests afresh)')
+            uncached(window[c0:], control, main)
+        else:
+            label, launch = bind(window, c0, control, main)
+            self.owner._launch(label, launch, units=self.N * self.K * cols)
         self._own_history(node, cols, hist, result)
         return result
+
+    def _ladder(self, node: ext.Ladder, channels: int, hist: int, rows: int) -> torch.Tensor:
+        """the 4-pole ladder: a window node (`_window_node`), one sig_ladder_coldstart launch over the K blocks; the cutoff, the
+        resonance and the drive rows each per block on their own when that port is modulated, the last two None when unplugged.  The
+        cutoff is as wide as the voices, so is the result; a position-pure one-column input is widened for the kernel"""
+        def bind(window, c0, cutoff, main):
+            if window.shape[1] < channels:
+                window = window.expand(-1, channels).contiguous()
+            k, drive = (None if row is None else self._narrow(row, channels)
+                        for row in node.control_rows(lambda bound: self._control(bound, bound.name)))
+            poles = int(node.get_state().poles)
+            swept = any(row is not None and row.shape[0] > 1 for row in (cutoff, k, drive))
+            status = self.owner._status_word(node)
+            return (f'ladder_coldstart[{poles}{",drive" if drive is not None else ""}{",blocks" if swept else ""}]',
+                    lambda: _native.ladder_coldstart(self.rate, self.pos, self.N, self.K, CONTEXT, cutoff, k, drive, poles, window, c0, main,
+                                                     status=status))
+        return self._window_node(node, channels, hist, rows, self._narrow(self._control(node.cutoff, 'cutoff'), channels), bind)
+
+    def _fir(self, node: ext.FIR, channels: int, hist: int, rows: int) -> torch.Tensor:
+        """the dense FIR filter: a window node (`_window_node`), one sig_fir_taps launch over the K blocks -- per-block select rows when
+        that port is modulated; the table is the node's resident copy"""
+        def bind(window, c0, select, main):
+            table = node.resident_table()
+            return (f'fir_taps[{table.shape[0]}{",per-block" if select.shape[0] > 1 else ""}]',
+                    lambda: _native.fir_taps(self.rate, self.pos, self.N, self.K, window, c0, select, table, main))
+        return self._window_node(node, channels, hist, rows, self._control(node.select, 'select'), bind)
 
     def _own_history(self, node: Emitter, channels: int, hist: int, result: torch.Tensor) -> None:
         """rows [:hist] of a request-dependent node (filter, or a node with per-block control): the previous

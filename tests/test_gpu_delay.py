@@ -104,6 +104,24 @@ def test_delay_taps_matches_the_reference_bit_for_bit(V, pos):
                             assert same(obuf[:, :V].cpu().numpy(), cast(want)), (V, pos, N, K, U, per_block, t_in, t_out)
 
 
+@pytest.mark.parametrize('N, K', [(220, 2), (221, 1), (110, 4)])
+def test_blocks_that_end_on_the_staging_tile_bit_for_bit(N, K):
+    """the 220-row staging tile's edge: a block that ends exactly on it (220 x 2: a tile per block), one row past it (221: a second tile
+    of one row) and two blocks per tile (110 x 4) -- V on both sides of a wave, positions 0 (zero fill) and 4096, U = 4 with a time row
+    per block, float32 in and out, and the float64 window's gather once per shape"""
+    from signals_amd import _native
+    assert N * K % 220 in (0, 1)                                               # SIG_DELAY_TILE_ROWS
+    for V in (3, 70):
+        for pos in (0, 4096):
+            x, t, taps, want = kernel_case(V, N, K, pos, 4, True)
+            c0 = min(100, pos)
+            for t_in in (torch.float32,) + ((torch.float64,) if (V, pos) == (70, 4096) else ()):
+                obuf = torch.zeros((N * K, V + 3), dtype=torch.float32, device='cuda:0')
+                _native.delay_taps(RATE, pos, N, K, dev(x, t_in), c0, dev(t), taps, obuf[:, :V])
+                assert not obuf[:, V:].any(), (V, pos, t_in)
+                assert same(obuf[:, :V].cpu().numpy(), f32(want)), (V, pos, t_in)
+
+
 def test_identity_shift_broadcast_input_and_unplugged_time():
     from signals_amd import _native
     rng = np.random.default_rng(21)

@@ -107,9 +107,10 @@ def test_fir_taps_matches_the_reference_bit_for_bit(V, pos):
                             assert same(obuf[:, :V].cpu().numpy(), cast(want)), (V, pos, N, K, L, W, per_block, t_in, t_out)
 
 
-@pytest.mark.parametrize('N,K', [(300, 1), (101, 3), (517, 2)])
+@pytest.mark.parametrize('N,K', [(300, 1), (101, 3), (517, 2), (256, 2), (257, 1)])
 def test_rows_that_cross_the_staging_tile_inside_a_block(N, K):
-    """the 256-row tile ends inside a block, at a row that is no multiple of the 8-row run; a padded input beside the padded output"""
+    """the 256-row tile ends inside a block, at a row that is no multiple of the 8-row run; a padded input beside the padded output.
+    (256, 2): a block ends exactly on the tile, a tile per block; (257, 1): one row past it, a second tile of one row"""
     from signals_amd import _native
     V, pos, L, W = 70, 4096, 101, 3
     x, s, h, want = kernel_case(V, N, K, pos, L, W, True)
