@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import base_kernel_cases as K
+from gpu_helpers import gpu_ready
 from signals_amd import _native
 
 pytestmark = pytest.mark.gpu
@@ -37,10 +38,7 @@ AMP_F64_BOUND = 4 * AMP_F64_MEASURED      # 8.88e-16: other inputs of the same r
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from signals_amd import runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def materialise(v: K.View, fill: float, copy: bool = True):

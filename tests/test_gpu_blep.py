@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, gpu_ready, lfo, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, stream
 import blep_reference as BR
 import resonant_reference as RR
@@ -38,16 +39,10 @@ ROUTES = {'per_node': {'fuse': False}, 'always': {'fuse_program': 'always'}, 'sp
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    from signals_amd import _native
+    gpu_ready()
     yield
     _native.voice_program_use_attached(True)
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
 
 
 def rows_of(rng, blocks, width):
@@ -141,18 +136,6 @@ def draw(seed=3):
                 pan=np.stack([np.cos(th), np.sin(th)]), copies16=draw_copies(rng, 16))
 
 
-def lfo(hz, depth, centre):
-    """depth * sin + centre as Mix(Gain(Sine, 2 depth), 2 centre, 0.5): (GPU node, oracle node) -- as in tests/test_gpu_unison.py"""
-    from oracle import chain_ref as R
-    from signals_amd.chain import fx
-    s = mkosc('Sine', [[hz]])
-    g = fx.Gain(); g.left = s; g.right = fix(2.0 * np.asarray(depth))
-    m = fx.Mix(); m.left = g; m.right = fix(2.0 * np.asarray(centre)); m.mix = fix([[0.5]])
-    ref = R.Binary('Mix', R.Binary('Gain', R.Osc('Sine', R.Fixed([[hz]])), R.Fixed(2.0 * np.asarray(depth))),
-                   R.Fixed(2.0 * np.asarray(centre)), R.Fixed([[0.5]]))
-    return m, ref
-
-
 def graph(which, p, kind='Sawtooth', copies=None):
     """(GPU node, oracle node, rendered width); `copies`: the array both sides read (default: the node's one clean copy)"""
     from oracle import chain_ref as R
@@ -204,18 +187,8 @@ def launching(route):
 
 
 def batches(top, channels, position, N, ks, route):
-    from signals_amd import runtime
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
     with launching(route):
-        r = BatchRenderer(top, channels, RATE, timer=timer, **ROUTES[route])
-        parts, pos = [], position
-        for k in ks:
-            parts.append(r.render(pos, N, k).cpu().numpy())
-            pos += N * k
-        torch.cuda.synchronize()
-        runtime.check_status()
-    return np.concatenate(parts), set(timer.summary())
+        return render_batches(top, channels, position, N, ks, names=True, check_status=True, **ROUTES[route])[:2]
 
 
 #        patch, kind, block frames, copies, position, routes
@@ -241,7 +214,7 @@ def test_routes(which, kind, N, U, pos, route):
     p = draw()
     top, _, C = graph(which, p, kind, None if U == 1 else p['copies16'][:U])
     what = (which, kind, N, U, pos, route)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     err = maxerr(eager, f32(want))
     print('blep eager', what, 'max|err|', err, 'tol', tol)
     assert err <= tol, (what, err)
@@ -267,10 +240,7 @@ def test_launches_of_each_route():
     for route in ('per_node', 'default', 'always', 'specialise'):
         timer = KernelTimer()
         with launching(route):
-            r = BatchRenderer(graph('bus', p)[0], 2, RATE, timer=timer, **ROUTES.get(route, {}))
-            r.render(0, 256, 4)
-            torch.cuda.synchronize()
-        names = set(timer.summary())
+            _, names, r = render_batches(graph('bus', p)[0], 2, 0, 256, (4,), timer=timer, names=True, **ROUTES.get(route, {}))
         if route == 'per_node':
             assert names == {'osc_bank_blep[Sawtooth]', 'sum_bus'}, names     # the per-node schedule
         else:
@@ -278,10 +248,8 @@ def test_launches_of_each_route():
             name = next(iter(names))
             assert name.startswith('voice_program_bus[OscBlep]'), (route, names)
             assert ('*specialised' in name) == bool(r.specialise), (route, names)
-    timer = KernelTimer()                                                     # swept controls: per-block rows on the per-node schedule
-    BatchRenderer(graph('swept', p, 'Square')[0], V, RATE, timer=timer, fuse=False).render(0, 256, 4)
-    torch.cuda.synchronize()
-    assert any(n.startswith('osc_bank_blep[Square,per-block]') for n in timer.summary()), set(timer.summary())
+    names = render_batches(graph('swept', p, 'Square')[0], V, 0, 256, (4,), names=True, fuse=False).names      # swept controls: per-block rows on the per-node schedule
+    assert any(n.startswith('osc_bank_blep[Square,per-block]') for n in names), names
 
 
 def test_the_node_in_a_control_path_keeps_the_eager_path():
@@ -312,7 +280,7 @@ def test_an_in_place_edit_of_copies_changes_the_next_render(route):
         r = BatchRenderer(top, C, RATE, **ROUTES[route])
         first = r.render(0, N, K).cpu().numpy()
         want = R.render_stream(ref, 0, N, K, C)
-        tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+        tol = tolerance(want)
         assert maxerr(first, f32(want)) <= tol, route
         copies[:, 0] *= 0.25                                                  # in place: the same array object
         copies[2, 1] = 0.125
@@ -346,7 +314,7 @@ def test_one_specialised_image_serves_two_copies_arrays(tmp_path, monkeypatch):
         got = BatchRenderer(top, C, RATE, timer=timer, specialise=True).render(0, N, K).cpu().numpy()
         torch.cuda.synchronize()
         want = R.render_stream(ref, 0, N, K, C)
-        assert maxerr(got, f32(want)) <= 1e-6 * max(1.0, float(np.abs(want).max()))
+        assert maxerr(got, f32(want)) <= tolerance(want)
         assert set(timer.summary()) == {'voice_program_bus[OscBlep]*specialised'}, set(timer.summary())
         built.append(sorted(f.name for f in tmp_path.glob('vp_*.hsaco')))
         assert len(builds) == 1 and builds[0][0] == (('OscBlep', 2, 0, 0, 0),), builds     # one build, at the first render

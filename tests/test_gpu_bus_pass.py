@@ -29,6 +29,7 @@ import torch
 
 import bus_pass_cases as B
 import envelopes as E
+from gpu_helpers import gpu_ready, tolerance
 from helpers import RATE, f32, fix, maxerr, mkosc
 from signals_amd import _native
 
@@ -43,10 +44,7 @@ LAUNCHES = {}                                      # test -> launches made, agai
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from signals_amd import runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def place(array: np.ndarray, pad: int, ld_extra: int, fill: float, copy: bool = True):
@@ -131,7 +129,7 @@ def held_to(got, b: B.Built, terms=None):
     err32 = np.abs(got - f32(ref).astype(np.float64))
     bound = half + summation + recurrence
     bound32 = bound + np.where(near_midpoint(ref, half, summation + recurrence), 2 * half, 0.0)
-    bar = 1e-6 * max(1.0, float(np.abs(ref).max()))
+    bar = tolerance(ref)
     failures = []
     if not np.isfinite(got).all() or (got == SENTINEL).any():
         failures.append('not finite, or not written')

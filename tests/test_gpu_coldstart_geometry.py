@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import tolerance
 from helpers import f32, maxerr
 import eq_reference as EQ
 import resonant_reference as RR
@@ -146,7 +147,7 @@ def test_first_geometry_against_the_restatement(entry, dtype, geometry, position
     for block in BLOCKS:
         want = restated(entry, position, block)
         have = got[block * N:(block + 1) * N].index_select(1, picked).cpu().numpy().astype(np.float64)
-        bound = 1e-6 if entry in ABSOLUTE else 1e-6 * max(1.0, float(np.abs(want).max()))
+        bound = 1e-6 if entry in ABSOLUTE else tolerance(want)
         err = maxerr(have, f32(want) if dtype == torch.float32 and entry != 'q' else want)   # (the resonant test holds both buffer types to the float64 rows)
         print('coldstart', entry, dtype, position, 'block', block, 'max|err|', err, 'bound', bound, 'max|oracle|', float(np.abs(want).max()))
         assert err <= bound, (entry, dtype, position, block, err, bound)

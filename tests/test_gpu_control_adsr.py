@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import adsr_control_cases as A
+from gpu_helpers import gpu_ready, render_batches
 from helpers import HOUR, RATE, fix, loc, maxerr, mkosc, stream, Probe
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,7 @@ N_ROWS, K_ROWS = 256, 9
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def eager_rows(node, positions, channels):
@@ -192,14 +190,10 @@ def references(which, N, pos):
 
 
 def batches(which, N, pos, **kw):
-    from signals_amd.engine import BatchRenderer, KernelTimer
+    from signals_amd.engine import KernelTimer
     timer = KernelTimer()
-    r = BatchRenderer(graph(which, N, pos)[0], 2, RATE, timer=timer, **kw)
-    parts, at = [], pos
-    for k in BATCHES:
-        parts.append(r.render(at, N, k).cpu().numpy())                # (NotBatchable would surface here)
-        at += N * k
-    return np.concatenate(parts), launched(timer)
+    got = render_batches(graph(which, N, pos)[0], 2, pos, N, BATCHES, timer=timer, **kw).rows           # (NotBatchable would surface here)
+    return got, launched(timer)
 
 
 def close(got, ref, what):

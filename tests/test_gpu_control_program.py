@@ -31,6 +31,7 @@ import pytest
 import torch
 
 import control_program_cases as K
+from gpu_helpers import gpu_ready
 from signals_amd import _native
 
 pytestmark = pytest.mark.gpu
@@ -42,10 +43,7 @@ MEASURED = {}                       # (kind, group) -> largest error / bound, fi
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from signals_amd import runtime
-    runtime.set_device(DEV)
-    _native.lib()
+    gpu_ready(DEV)
 
 
 class Outcome:

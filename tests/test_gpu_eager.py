@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import gpu_ready
 from helpers import HOUR, OSC, RATE, f32, fix, loc, maxerr, mkosc, render, stream, Probe
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +24,7 @@ SINE_TOL = 1.5e-7      # f32 Sine: exact phase reduction + v_sin_f32 (measured m
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()      # fail loudly if the HIP library is missing
+    gpu_ready()
 
 
 @pytest.mark.parametrize('kind', list(OSC))

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_FORCED, dev, gpu_ready, render_batches
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc
 import eq_reference as EQ
 import unison_reference as UR
@@ -24,8 +25,7 @@ import unison_reference as UR
 pytestmark = pytest.mark.gpu
 
 BOUND = 1e-6
-ROUTES = {'per_node': {'fuse': False}, 'always': {'fuse_program': 'always'}, 'specialise': {'fuse_program': 'always', 'specialise': True},
-          'mixed': {'fuse_program': 'always', 'mixed_programs': True}}
+ROUTES = {**ROUTES_FORCED, 'mixed': {'fuse_program': 'always', 'mixed_programs': True}}
 FUSED = ('fused', 'latency', 'cascade', 'steady', 'walk', 'biquad_coldstart[', 'biquad_bus', 'biquad_coldstart_env', 'biquad_coldstart_q[')
 QS, GAINS = (0.5, 1.0 / math.sqrt(2.0), 4.0), (-12.0, 0.0, 12.0)
 V = 70
@@ -35,10 +35,7 @@ GEOMETRY = {'blocks': (128, (1, 2), 0), 'short': (32, (1, 2), 0), 'hour': (128, 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def classes():
@@ -84,18 +81,7 @@ def wanted(kind, unison, geometry):
 
 def batches(top, position, N, ks, check=True, **kw):
     """(the rows of consecutive batches, the labels of the launches that rendered them, the renderer)"""
-    from signals_amd import runtime
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, V, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    if check:
-        runtime.check_status()
-    return np.concatenate(parts), set(timer.summary()), r
+    return render_batches(top, V, position, N, ks, names=True, check_status=check, **kw)
 
 
 def check_labels(names, route):
@@ -176,7 +162,6 @@ def test_kernel_status_bits_one_at_a_time():
     from signals_amd import _native
     N, K = 128, 2
     p = draw()
-    dev = lambda a, dtype=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
     x = dev(f32(np.random.default_rng(1).uniform(-0.25, 0.25, (N * K, V))), torch.float32)
     out = torch.empty((N * K, V), dtype=torch.float32, device='cuda:0')
     status = torch.zeros(1, dtype=torch.int32, device='cuda:0')

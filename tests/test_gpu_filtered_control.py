@@ -7,17 +7,15 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import HOUR, RATE, fix, loc, maxerr, mkosc, stream, Probe
+from gpu_helpers import close, gpu_ready, render_batches
+from helpers import HOUR, RATE, fix, loc, mkosc, stream, Probe
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def smoothed(V, kind='Square', lfo_hz=3.0, cut=4.0, ftype='LowPass', lo=300.0, hi=3000.0):
@@ -42,22 +40,6 @@ def drift(V, base, seed=3):
     g = fx.Gain(); g.left = f; g.right = fix(0.02 * base)
     m = fx.Mix(); m.left = g; m.right = fix(base * 0.99 * 2.0); m.mix = fix([[0.5]])        # 0.5 (0.02 b f) + 0.5 (1.98 b)
     return m
-
-
-def batches(node, channels, position, N, ks, timer=None, **kw):
-    from signals_amd.engine import BatchRenderer
-    r = BatchRenderer(node, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    return np.concatenate(parts)
-
-
-def close(got, ref, what):
-    scale = max(1.0, float(np.max(np.abs(ref))))
-    err = maxerr(got, ref)
-    assert err <= 1e-6 * scale, (what, err, scale)
 
 
 def eager_rows(node, positions, channels):
@@ -177,7 +159,7 @@ def test_per_node_schedule_is_bit_identical_to_eager(name):
     p = draw(V)
     C = 2 if name == 'b_bus' else V
     timer = KernelTimer()
-    got = batches(GRAPHS[name](V, p), C, 0, N, (4, 3), timer=timer, fuse=False)
+    got = render_batches(GRAPHS[name](V, p), C, 0, N, (4, 3), timer=timer, fuse=False).rows
     torch.cuda.synchronize()
     assert any(k.startswith('control_program[') for k in timer.summary()), set(timer.summary())
     want = stream(GRAPHS[name](V, p), 0, N, 7, C)
@@ -194,7 +176,7 @@ def test_fused_schedules_match_eager(name, mode):
     V, N = 64, 256
     p = draw(V, seed=11)
     C = 2 if name == 'b_bus' else V
-    got = batches(GRAPHS[name](V, p), C, 0, N, (4, 3), **kw)
+    got = render_batches(GRAPHS[name](V, p), C, 0, N, (4, 3), **kw).rows
     close(got, stream(GRAPHS[name](V, p), 0, N, 7, C), (name, mode))
 
 
@@ -203,7 +185,7 @@ def test_fm_path_takes_the_fused_walker():
     V, N = 64, 256
     p = draw(V, seed=2)
     timer = KernelTimer()
-    got = batches(graph_b(V, p, bus=True), 2, 0, N, (3, 3), timer=timer)
+    got = render_batches(graph_b(V, p, bus=True), 2, 0, N, (3, 3), timer=timer).rows
     torch.cuda.synchronize()
     names = set(timer.summary())
     assert any('fm' in k or 'fused' in k for k in names), names
@@ -216,7 +198,7 @@ def test_smoothed_lfo_cutoff_against_the_oracle(pos):
     V, N, K = 16, 256, 5
     p = draw(V, seed=4)
     node, ref = graph_a(V, p)
-    got = batches(node, V, pos, N, (K,))
+    got = render_batches(node, V, pos, N, (K,)).rows
     want = R.render_stream(ref, pos, N, K, V)
     close(got, want, ('oracle', pos))
 
@@ -234,7 +216,7 @@ def test_bad_cutoff_raises_the_eager_error():
     node = graph_a(V, p)[0]
     ctl_filter(node).cutoff = fix([[30000.0] * V])
     with pytest.raises(ValueError):
-        batches(node, V, 0, N, (3,), fuse=False)
+        render_batches(node, V, 0, N, (3,), fuse=False).rows
         runtime.check_status()
     for _ in range(8):                                               # (check_status raises at the first word it finds set)
         try:

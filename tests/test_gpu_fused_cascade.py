@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import gpu_ready
 from helpers import RATE, f32, fix, maxerr, mkosc, stream
 
 pytestmark = pytest.mark.gpu
@@ -13,10 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def params(V, seed):

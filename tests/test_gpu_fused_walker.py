@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, tolerance
 from helpers import RATE, f32, maxerr
+from signals_amd.engine import CONTEXT as CTX
 
 pytestmark = pytest.mark.gpu
-CTX = 100
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -32,14 +33,10 @@ def geometry(vpt, span, steady=1):
     _native.set_fused_tuning(vpt, span, steady, 0)
 
 
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device='cuda')
-
-
 def bar(ref, cap=None):
     """BASELINE's bar for a bus: 1e-6 of its full scale (never below 1: a float32 bus of |x| < 1 is compared absolutely),
     and never looser than `cap` where an absolute tolerance was already met"""
-    tol = 1e-6 * max(1.0, float(np.abs(ref).max()))
+    tol = tolerance(ref)
     return tol if cap is None else min(tol, cap)
 
 
@@ -385,7 +382,7 @@ def test_one_launch_latency_kernel_matches_the_oracle(btype):
         for device_pos in (False, True, False):                       # three launches on one workspace: the counter re-arms
             got = run_latency(btype, p, pos, N, C=C, device_pos=device_pos, ws=ws)
             assert np.isfinite(got).all()
-            assert maxerr(got, want) < 1e-6 * max(1.0, float(np.abs(want).max())), (V, N, pos, C, device_pos)
+            assert maxerr(got, want) < tolerance(want), (V, N, pos, C, device_pos)
 
 
 def test_engine_latency_mode_uses_one_launch_and_follows_a_stream():

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import gpu_ready, tolerance
 from helpers import HOUR, RATE, f32, maxerr
 import mixed_patches as MP
 
@@ -40,10 +41,8 @@ COPIES = {'supersaw': 'copies3', 'three': 'copies3'}                          # 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    from signals_amd import _native
+    gpu_ready()
     yield
     _native.set_voice_program_tuning(0, 0)
 
@@ -64,10 +63,6 @@ def wanted(which, geometry):
     want = R.render_stream(ref, pos, N, sum(ks), C)
     want.setflags(write=False)
     return want
-
-
-def tolerance(want):
-    return 1e-6 * max(1.0, float(np.abs(want).max()))
 
 
 @contextlib.contextmanager

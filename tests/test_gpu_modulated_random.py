@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import tolerance
 from helpers import RATE, f32, fix, maxerr, mkosc
 
 pytestmark = pytest.mark.gpu
@@ -91,7 +92,7 @@ def test_random_modulated_voices_against_the_oracle(seed):
         if c['bus']:
             ref = R.sum_bus(ref, c['pan'] if c['bus'] == 2 else None)
         err = maxerr(np.concatenate(parts), f32(ref))
-        assert err < 1e-6 * max(1.0, float(np.abs(ref).max())), (seed, case, c['kind'], c['btype'], V, N, c['start'], c['batches'], c['mods'], c['bus'], err)
+        assert err < tolerance(ref), (seed, case, c['kind'], c['btype'], V, N, c['start'], c['batches'], c['mods'], c['bus'], err)
         rendered += 1
     assert rendered == 24 and short >= 1, (rendered, short)
 

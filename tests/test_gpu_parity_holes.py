@@ -21,11 +21,12 @@ import torch
 
 import bench
 import bench_configs as cfg
+from gpu_helpers import dev
 from helpers import HOUR, RATE, f32, maxerr
+from signals_amd.engine import CONTEXT as CTX
 
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parent.parent
-CTX = 100
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -36,10 +37,6 @@ def _device():
     yield
     _native.set_fused_tuning()
     _native.set_fused_cascade_tuning()
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device='cuda')
 
 
 # ------------------------------------------------------------------------------------------------ (a) 2^24 .. 2^26 cycles

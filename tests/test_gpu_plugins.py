@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import gpu_ready
 from helpers import RATE, Probe, f32, fix, loc, maxerr, stream
 
 pytestmark = pytest.mark.gpu
@@ -13,10 +14,7 @@ V, N = 24, 256
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def pulse(position, frames, channels):

@@ -21,26 +21,20 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_WITH_DEFAULT as ROUTES, dev, gpu_ready, lfo, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, render, stream
+from signals_amd.engine import CONTEXT
 import pm_reference as PR
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ('Sine', 'Square', 'Sawtooth', 'Triangle')
 I_MAX = 4.0
-ROUTES = {'per_node': {'fuse': False}, 'default': {}, 'always': {'fuse_program': 'always'}, 'specialise': {'specialise': True}}
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
+    gpu_ready()
 
 
 # ---------------------------------------------------------------------------------------------- C ABI
@@ -113,18 +107,6 @@ def draw(V, seed=3):
                          release=rng.uniform(0.01, 0.05, (1, V)), gate_on=rng.uniform(0.0, 0.01, (1, V)), gate_off=rng.uniform(0.04, 0.07, (1, V))))
 
 
-def lfo(hz, depth, centre):
-    """depth * sin + centre as Mix(Gain(Sine, 2 depth), 2 centre, 0.5): (GPU node, oracle node)"""
-    from oracle import chain_ref as R
-    from signals_amd.chain import fx
-    s = mkosc('Sine', [[hz]])
-    g = fx.Gain(); g.left = s; g.right = fix(2.0 * np.asarray(depth))
-    m = fx.Mix(); m.left = g; m.right = fix(2.0 * np.asarray(centre)); m.mix = fix([[0.5]])
-    ref = R.Binary('Mix', R.Binary('Gain', R.Osc('Sine', R.Fixed([[hz]])), R.Fixed(2.0 * np.asarray(depth))),
-                   R.Fixed(2.0 * np.asarray(centre)), R.Fixed([[0.5]]))
-    return m, ref
-
-
 def carrier(kind, p, mod, rmod, index=None, rindex=None):
     from oracle import chain_ref as R
     from signals_amd.chain import ext
@@ -176,19 +158,6 @@ def graph(which, p, kind='Sine', ratio=1.0, given=None):
     raise KeyError(which)
 
 
-def batches(node, channels, position, N, ks, **kw):
-    from signals_amd.engine import BatchRenderer
-    r = BatchRenderer(node, channels, RATE, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    return np.concatenate(parts)
-
-
-CONTEXT = 100
-
-
 def reach_of_jumps(near, pos, N, K):
     """the rows a crossed jump at a near-jump sample can reach behind ONE filter: from its row to the end of every block whose
     [<= 100 context rows | block] window holds it (each block is filtered from zero state, fx.py:85-106)"""
@@ -209,7 +178,7 @@ def check_route(route, which, pos, N, ks, V=96, **gkw):
     p = draw(V)
     K = sum(ks)
     node, _, _, C, filtered, _ = graph(which, p, **gkw)
-    got = batches(node, C, pos, N, ks, **ROUTES[route])
+    got = render_batches(node, C, pos, N, ks, **ROUTES[route]).rows
     what = (route, which, pos, N, gkw)
     kind = {'ratio': gkw.get('kind', 'Sine'), 'lowpass': 'Sawtooth'}.get(which, 'Sine')
     scaled = filtered or which == 'bus'
@@ -229,7 +198,7 @@ def check_route(route, which, pos, N, ks, V=96, **gkw):
         if which == 'ratio' and kind != 'Sine':
             assert np.array_equal(got, f32(want)), what                       # bit-exact
             return
-        tol = 1.3e-7 if which == 'ratio' else 1e-6 * max(1.0, float(np.abs(want).max()))
+        tol = 1.3e-7 if which == 'ratio' else tolerance(want)
         err = maxerr(got, want if which == 'ratio' else f32(want))
         print('pm route', what, 'max|err|', err, 'tol', tol, 'own modulator, no mask')
         assert err <= tol, (what, err, tol)
@@ -297,7 +266,7 @@ def test_short_blocks(which, route, pos):
         from signals_amd.engine import NotBatchable
         p = draw(96)
         with pytest.raises(NotBatchable, match='cascaded filters with block size <= 100'):
-            batches(graph(which, p, ratio=2)[0], 96, pos, 64, (5, 6), fuse=False)
+            render_batches(graph(which, p, ratio=2)[0], 96, pos, 64, (5, 6), fuse=False)
         node, ref, _, _, _, _ = graph(which, p, ratio=2)
         want = R.render_stream(ref, pos, 64, 11, 96)
         tol = 1e-6 * (1.0 + PR.SLOPE['Sine'] * I_MAX) * max(1.0, float(np.abs(want).max()))
@@ -339,24 +308,17 @@ def test_unplugged_modulator_or_index_is_the_plain_oscillator_bit_for_bit(kind):
 
 
 def test_launches_of_each_route():
-    from signals_amd.engine import BatchRenderer, KernelTimer
     p = draw(128)
     for route, kw in ROUTES.items():
-        timer = KernelTimer()
-        r = BatchRenderer(graph('bus', p)[0], 2, RATE, timer=timer, **kw)
-        r.render(0, 256, 4)
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        _, names, r = render_batches(graph('bus', p)[0], 2, 0, 256, (4,), names=True, **kw)
         if route == 'per_node':
             assert any(n.startswith('osc_bank_pm[Sine]') for n in names) and not any(n.startswith('voice_program') for n in names), names
         else:
             assert any(n.startswith('voice_program_bus[Osc,OscPM') for n in names), (route, names)
             assert not any(n.startswith(('osc_bank', 'sum_bus')) for n in names), (route, names)
             assert any('*specialised' in n for n in names) == bool(r.specialise), (route, names)      # (SIG_SPECIALISE=1 turns it on for every route)
-    timer = KernelTimer()                                                     # a swept index: per-block rows on the per-node schedule
-    BatchRenderer(graph('enveloped', p)[0], 128, RATE, timer=timer, fuse=False).render(0, 256, 4)
-    torch.cuda.synchronize()
-    assert any(n.startswith('osc_bank_pm[Sine,per-block]') for n in timer.summary()), set(timer.summary())
+    names = render_batches(graph('enveloped', p)[0], 128, 0, 256, (4,), names=True, fuse=False).names      # a swept index: per-block rows on the per-node schedule
+    assert any(n.startswith('osc_bank_pm[Sine,per-block]') for n in names), names
 
 
 def test_a_pm_oscillator_in_a_control_path_keeps_the_eager_path():

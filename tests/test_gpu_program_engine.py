@@ -6,17 +6,15 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import RATE, f32, fix, maxerr, mkosc, stream
+from gpu_helpers import gpu_ready, render_batches
+from helpers import f32, fix, maxerr, mkosc, stream
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    gpu_ready()
 
 
 def draw(V, seed):
@@ -26,16 +24,6 @@ def draw(V, seed):
                 cut1=rng.uniform(200, 8000, (1, V)), cut2=rng.uniform(200, 8000, (1, V)), cut3=rng.uniform(200, 8000, (1, V)),
                 gain=rng.uniform(0.2, 1.0, (1, V)), mix=rng.uniform(0, 1, (1, V)), expo=rng.uniform(0.5, 2.0, (1, V)),
                 pan=np.stack([np.cos(th), np.sin(th)]))
-
-
-def render_batches(node, channels, position, N, batches, timer=None, **kw):
-    from signals_amd.engine import BatchRenderer
-    r = BatchRenderer(node, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in batches:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    return np.concatenate(parts)
 
 
 def launches(timer):
@@ -114,7 +102,7 @@ def test_shapes_beyond_the_fused_kernels_are_one_launch_and_match_the_oracle(whi
     ref = R.render_stream(ref_node, 0, N, sum(batches), V)
     scale = max(1.0, np.nanmax(np.abs(ref)))
     timer = KernelTimer()
-    got = render_batches(node, V, 0, N, batches, timer, fuse_program='always')     # (by default only where it beats one kernel per node)
+    got = render_batches(node, V, 0, N, batches, timer=timer, fuse_program='always').rows     # (by default only where it beats one kernel per node)
     names = launches(timer)
     assert len([n for n in names if n.startswith('voice_program[')]) == 1, names
     assert all(n.startswith(('voice_program[', 'control_program')) for n in names), names
@@ -123,7 +111,7 @@ def test_shapes_beyond_the_fused_kernels_are_one_launch_and_match_the_oracle(whi
     node, ref_node = shapes(p, which)
     bus = ext.SumBus(); bus.input = node; bus.get_state().gains = np.ascontiguousarray(p['pan'])
     timer = KernelTimer()
-    got = render_batches(bus, 2, 0, N, batches, timer, fuse_program='always')
+    got = render_batches(bus, 2, 0, N, batches, timer=timer, fuse_program='always').rows
     names = launches(timer)
     assert any(n.startswith('voice_program_bus[') for n in names) and not any(n.startswith(('sum_bus', 'biquad', 'osc_bank')) for n in names), names
     want = np.nan_to_num(R.render_stream(ref_node, 0, N, sum(batches), V)) @ p['pan'].T if which == 'amp_after_filter' else ref @ p['pan'].T
@@ -132,12 +120,12 @@ def test_shapes_beyond_the_fused_kernels_are_one_launch_and_match_the_oracle(whi
     # a fresh renderer mid-stream answers what a fresh reference graph answers
     node, ref_node = shapes(p, which)
     fresh_ref = R.render_stream(ref_node, 5 * N, N, 2, V)
-    fresh = render_batches(node, V, 5 * N, N, (2,), fuse_program='always')
+    fresh = render_batches(node, V, 5 * N, N, (2,), fuse_program='always').rows
     assert maxerr(fresh, f32(fresh_ref)) < 1e-6 * scale, which
     # the default policy: the interpreter where it beats one kernel per node (programs that fit its small register file)
     node, _ = shapes(p, which)
     timer = KernelTimer()
-    default = render_batches(node, V, 0, N, batches, timer)
+    default = render_batches(node, V, 0, N, batches, timer=timer).rows
     small = which not in ('amp_after_filter', 'three_filters')
     if which != 'three_filters':                          # (there the inner two filters' history block IS a small program)
         assert any(n.startswith('voice_program[') for n in launches(timer)) == small, (which, launches(timer))
@@ -163,11 +151,11 @@ def test_voices_without_a_filter_under_a_bus_are_one_launch(kind):
     batches = (2, 5)
     want = (R.render_stream(R.Binary('Gain', ro, R.Fixed(p['gain'])), 7 * N, N, sum(batches), V)) @ p['pan'].T
     timer = KernelTimer()
-    got = render_batches(bus, 2, 7 * N, N, batches, timer)
+    got = render_batches(bus, 2, 7 * N, N, batches, timer=timer).rows
     names = launches(timer)
     assert all(n.startswith('voice_program_bus[') for n in names), names
     assert maxerr(got, f32(want)) < 1e-6 * max(1.0, np.abs(want).max())
-    per_node = render_batches(bus, 2, 7 * N, N, batches, fuse_program=False)
+    per_node = render_batches(bus, 2, 7 * N, N, batches, fuse_program=False).rows
     assert maxerr(got, per_node) < 1e-6 * max(1.0, np.abs(want).max())
 
 
@@ -193,13 +181,13 @@ def test_blocks_no_longer_than_the_context_are_batched(N):
                                             R.Fixed(p['cut2'])), R.Fixed(p['gain']))
     ref = R.render_stream(ref_cascade, 0, N, sum(batches), V)
     timer = KernelTimer()
-    got = render_batches(cascade(), V, 0, N, batches, timer)
+    got = render_batches(cascade(), V, 0, N, batches, timer=timer).rows
     assert all(n.startswith('voice_program[') for n in launches(timer))
     assert maxerr(got, f32(ref)) < 1e-6 * max(1.0, np.abs(ref).max()), N
     eager = stream(cascade(), 0, N, sum(batches), V)
     assert maxerr(got, eager) < 1e-6 * max(1.0, np.abs(ref).max()), N       # (the eager path rounds every edge to float32)
     bus = ext.SumBus(); bus.input = cascade(); bus.get_state().gains = np.ascontiguousarray(p['pan'])
-    got_bus = render_batches(bus, 2, 0, N, batches)
+    got_bus = render_batches(bus, 2, 0, N, batches).rows
     want = ref @ p['pan'].T
     assert maxerr(got_bus, f32(want)) < 1e-6 * max(1.0, np.abs(want).max()), N
 
@@ -213,7 +201,7 @@ def test_blocks_no_longer_than_the_context_are_batched(N):
         return g, R.Binary('Gain', R.Filter('lp', R.Osc('Sawtooth', rhz, R.Fixed(p['phase'])), rcut), rtrem)
     node, ref_node = fm_voice()
     ref = R.render_stream(ref_node, 0, N, sum(batches), V)
-    got = render_batches(node, V, 0, N, batches)
+    got = render_batches(node, V, 0, N, batches).rows
     assert maxerr(got, f32(ref)) < 1e-6 * max(1.0, np.abs(ref).max()), ('fm', N)
     node, _ = fm_voice()
     assert maxerr(got, stream(node, 0, N, sum(batches), V)) < 1e-6 * max(1.0, np.abs(ref).max()), ('fm eager', N)
@@ -238,7 +226,7 @@ def test_lowpass_test_patch_merge_is_two_launches():
                                 R.Fixed([[1.0]]))
     ref = R.render_stream(R.Merge(rside(p['hertz']), rside(p['hertz2']), V, V), 0, N, K, 2 * V)
     timer = KernelTimer()
-    got = render_batches(m, 2 * V, 0, N, (K,), timer, fuse_program='always')
+    got = render_batches(m, 2 * V, 0, N, (K,), timer=timer, fuse_program='always').rows
     names = launches(timer)
     assert names == {'voice_program[Osc,Gain,Filter,Amp]'}, names
     assert got.shape == (N * K, 2 * V) and maxerr(got, f32(ref)) < 1e-6
@@ -278,15 +266,15 @@ def test_short_block_fixtures_of_the_reference(golden, N):
         for name, build in (('cascade', cascade), ('fm', fm)):
             ref = g[f'small/{name}/n{N}_p{start}']
             timer = KernelTimer()
-            got = render_batches(build(), V, start, N, (1, 4, 2, 5), timer)
+            got = render_batches(build(), V, start, N, (1, 4, 2, 5), timer=timer).rows
             want = 'fused_osc_biquad[' if (name == 'fm' and N >= 100) else 'voice_program['      # (100-frame FM: the walker's own block-rate rows)
             assert any(n.startswith(want) for n in launches(timer))
             assert maxerr(got, f32(ref)) < 1e-6, (name, N, start)
     if N == 32:
         for mode in (True, 'always'):                        # three filters in series: per node by default, one launch on request
-            got = render_batches(cascade(3), V, 0, 256, (2, 1, 3), fuse_program=mode)
+            got = render_batches(cascade(3), V, 0, 256, (2, 1, 3), fuse_program=mode).rows
             assert maxerr(got, f32(g['small/cascade3/n256_p0'])) < 1e-6, mode
-            assert maxerr(render_batches(cascade(3), V, 1000, 256, (1,), fuse_program=mode), f32(g['small/cascade3/fresh_p1000'])) < 1e-6, mode
+            assert maxerr(render_batches(cascade(3), V, 1000, 256, (1,), fuse_program=mode).rows, f32(g['small/cascade3/fresh_p1000'])) < 1e-6, mode
 
 
 @pytest.mark.parametrize('name', ['ringmod', 'mix', 'amp', 'fanout', 'swept_cascade'])
@@ -337,12 +325,12 @@ def test_voice_graph_fixtures_of_the_reference(golden, name):
         modes.append(dict(fuse_program='always', specialise=True))
     for kw in modes:
         timer = KernelTimer()
-        got = render_batches(build(), V, 0, 256, (2, 3, 1), timer, **kw)
+        got = render_batches(build(), V, 0, 256, (2, 3, 1), timer=timer, **kw).rows
         assert np.array_equal(np.isnan(got), np.isnan(ref)), (name, kw)           # (Amp: NaN where the reference has NaN)
         assert maxerr(got, f32(ref)) < 1e-6 * scale, (name, kw)
         if kw.get('fuse_program') == 'always':
             assert any(n.startswith('voice_program[') for n in launches(timer)), (name, launches(timer))
         if kw.get('specialise'):
             assert any(n.endswith('*specialised') for n in launches(timer)), (name, launches(timer))
-        got = render_batches(build(), V, 1000, 256, (1,), **kw)
+        got = render_batches(build(), V, 1000, 256, (1,), **kw).rows
         assert np.array_equal(np.isnan(got), np.isnan(fresh)) and maxerr(got, f32(fresh)) < 1e-6 * scale, (name, kw)

@@ -32,9 +32,9 @@ import functools
 
 import numpy as np
 import pytest
-import torch
 
-from helpers import RATE, f32, maxerr, stream
+from gpu_helpers import gpu_ready, render_batches
+from helpers import f32, maxerr, stream
 import random_ext_graphs as G
 
 pytestmark = pytest.mark.gpu
@@ -49,10 +49,8 @@ RUNS = {'seeds': 0, 'program_renders': 0, 'with_program': 0, 'with_extension_wor
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    from signals_amd import _native
+    gpu_ready()
     yield
     _native.set_voice_program_tuning(0, 0)
 
@@ -64,19 +62,6 @@ def wanted(seed, pos, N, K):
     want = G.oracle_rows(graph, pos, N, K)
     want.setflags(write=False)
     return want, G.tolerance(graph, want)
-
-
-def batches(node, channels, pos, N, ks, **kw):
-    """(rows, launch names) of a fresh renderer over consecutive batches"""
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(node, channels, RATE, timer=timer, **kw)
-    parts = []
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    return np.concatenate(parts), set(timer.summary())
 
 
 def within(leg, got, want, tol, what):
@@ -112,18 +97,18 @@ def test_random_ext_graph_on_every_route(seed):
             eager = stream(graph.node, pos, N, K, graph.channels)
             within('eager', eager, want, tol, what)                                            # 1
             graph = b.build()
-            plain, names = batches(graph.node, graph.channels, pos, N, ks, fuse=False)        # 2 (NotBatchable here fails the test)
+            plain, names, _ = render_batches(graph.node, graph.channels, pos, N, ks, names=True, fuse=False)        # 2 (NotBatchable here fails the test)
             assert not any(w in n for n in names for w in FUSED), names
             assert plain.dtype == np.float32 and np.array_equal(plain, eager, equal_nan=True), (what, maxerr(plain, eager))
             graph = b.build()
-            default, names = batches(graph.node, graph.channels, pos, N, ks)                  # 3
+            default, names, _ = render_batches(graph.node, graph.channels, pos, N, ks, names=True)                  # 3
             within('default', default, want, tol, what)
             RUNS['default_renders'] += 1
             if not any(w in n for n in names for w in FUSED):
                 RUNS['default_bit_equal'] += 1
                 assert np.array_equal(default, eager, equal_nan=True), (what, sorted(names), maxerr(default, eager))
             graph = b.build()
-            program, names = batches(graph.node, graph.channels, pos, N, ks, fuse_program='always', mixed_programs=True)   # 4
+            program, names, _ = render_batches(graph.node, graph.channels, pos, N, ks, names=True, fuse_program='always', mixed_programs=True)   # 4
             within('program', program, want, tol, what)
             RUNS['program_renders'] += 1
             RUNS['with_program'] += any(n.startswith('voice_program') for n in names)
@@ -133,7 +118,7 @@ def test_random_ext_graph_on_every_route(seed):
         graph = b.build()
         RUNS['short_renders'] += 1
         try:
-            short, names = batches(graph.node, graph.channels, pos, N, ks, fuse_program='always', mixed_programs=True)
+            short, names, _ = render_batches(graph.node, graph.channels, pos, N, ks, names=True, fuse_program='always', mixed_programs=True)
         except NotBatchable as e:
             assert str(e).strip(), 'a refusal without a reason'
             print(f'random ext graph {(seed, pos, N)} program: NOT BATCHABLE: {e}')

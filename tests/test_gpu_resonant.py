@@ -19,12 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_FORCED as ROUTES, dev, gpu_ready, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, render, stream
 import resonant_reference as RR
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = {'per_node': {'fuse': False}, 'always': {'fuse_program': 'always'}, 'specialise': {'fuse_program': 'always', 'specialise': True}}
 FUSED = ('fused', 'latency', 'cascade', 'steady', 'walk', 'biquad_coldstart[', 'biquad_bus', 'biquad_coldstart_env')
 QS = (0.5, 1.0 / math.sqrt(2.0), 2.0, 8.0)
 #            voices, block frames, batches, position
@@ -34,14 +34,7 @@ GEOMETRY = {'tile': (130, 128, (2, 3), 0), 'hour': (130, 256, (3,), HOUR), 'four
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
+    gpu_ready()
 
 
 def draw(V):
@@ -51,10 +44,6 @@ def draw(V):
     return dict(cut=np.geomspace(40.0, 0.4 * RATE, V)[None, :] if V > 1 else np.array([[1000.0]]),
                 q=np.array([QS[(v + 3) % 4] for v in range(V)])[None, :],
                 hertz=rng.uniform(55, 1760, (1, V)), phase=rng.uniform(0, 1, (1, V)), pan=np.stack([np.cos(th), np.sin(th)]))
-
-
-def tolerance(want):
-    return 1e-6 * max(1.0, float(np.abs(want).max()))
 
 
 # ---------------------------------------------------------------------------------------------- C ABI
@@ -180,18 +169,8 @@ def wanted(which, geometry):
 
 
 def batches(top, channels, position, N, ks, **kw):
-    """(the rows of consecutive batches, the labels of the launches that rendered them)"""
-    from signals_amd import runtime
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    runtime.check_status()
-    return np.concatenate(parts), set(timer.summary())
+    """(the rows of consecutive batches, the labels of the launches that rendered them); the status word is checked"""
+    return render_batches(top, channels, position, N, ks, names=True, check_status=True, **kw)[:2]
 
 
 def check_labels(names, route, bus=False, plain_filter=False):

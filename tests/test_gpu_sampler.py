@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, gpu_ready, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, render
 import sampler_reference as SR
 
@@ -28,14 +29,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.array(a)).to('cuda:0', dtype)                # (a copy: the shared references are read-only)
+    gpu_ready()
 
 
 def table_dev(table):
@@ -241,19 +235,11 @@ def eager_rows(top, C, pos, N, blocks):
 
 
 def batched_rows(top, C, pos, N, ks, **kw):
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, C, RATE, timer=timer, **kw)
-    parts = []
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    return np.concatenate(parts), set(timer.summary())
+    return render_batches(top, C, pos, N, ks, names=True, **kw)[:2]
 
 
 def bound(want):
-    return 1e-6 * max(1.0, float(np.abs(want).max()))
+    return tolerance(want)
 
 
 def check_routes(which, p, want, pos, N, ks):

@@ -21,26 +21,19 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_WITH_DEFAULT as ROUTES, dev, gpu_ready, render_batches
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, render, stream
 import shaper_reference as SR
 import wavetable_reference as WR
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = {'per_node': {'fuse': False}, 'default': {}, 'always': {'fuse_program': 'always'}, 'specialise': {'specialise': True}}
 V, KS = 200, (3, 3)
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
+    gpu_ready()
 
 
 def inputs(rng, rows, voices, T, dtype, turn=0):
@@ -280,19 +273,6 @@ def wanted(which, pos, N):
     return want, eager
 
 
-def batches(top, channels, position, N, ks, **kw):
-    """(the rows of consecutive batches, the names of the kernels that rendered them)"""
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    return np.concatenate(parts), set(timer.summary())
-
-
 CASES = [(which, N) for which in ('bus', 'plain', 'lowpass_bus', 'filtered', 'adsr', 'wavetable', 'lfo') for N in (64, 256)]
 
 
@@ -316,7 +296,7 @@ def test_routes(which, N, route, pos):
         assert specialise.hipcc() is not None
     want, eager = wanted(which, pos, N)
     top, _, C, exact = graph(which, draw())
-    got, names = batches(top, C, pos, N, KS, **ROUTES[route])
+    got, names, _ = render_batches(top, C, pos, N, KS, names=True, **ROUTES[route])
     what = (which, N, route, pos)
     program = any(n.startswith('voice_program') for n in names)
     whole = program and all(n.startswith(('voice_program', 'control_program')) for n in names)     # one audio-rate launch, oscillator to stored rows
@@ -341,24 +321,17 @@ def test_routes(which, N, route, pos):
 
 
 def test_launches_of_each_route():
-    from signals_amd.engine import BatchRenderer, KernelTimer
     p = draw()
     for route, kw in ROUTES.items():
-        timer = KernelTimer()
-        r = BatchRenderer(graph('bus', p)[0], 2, RATE, timer=timer, **kw)
-        r.render(0, 256, 4)
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        _, names, r = render_batches(graph('bus', p)[0], 2, 0, 256, (4,), names=True, **kw)
         if route == 'per_node':
             assert any(n.startswith('shaper_table[Shaper]') for n in names) and not any(n.startswith('voice_program') for n in names), names
         else:
             assert any(n.startswith('voice_program_bus[') and 'Shape' in n for n in names), (route, names)
             assert not any(n.startswith(('shaper_table', 'osc_bank', 'sum_bus')) for n in names), (route, names)
             assert any('*specialised' in n for n in names) == bool(r.specialise), (route, names)
-    timer = KernelTimer()                                                     # a swept select: per-block rows on the per-node schedule
-    BatchRenderer(graph('lfo', p)[0], V, RATE, timer=timer, fuse=False).render(0, 256, 4)
-    torch.cuda.synchronize()
-    assert any(n.startswith('shaper_table[Shaper,per-block]') for n in timer.summary()), set(timer.summary())
+    names = render_batches(graph('lfo', p)[0], V, 0, 256, (4,), names=True, fuse=False).names      # a swept select: per-block rows on the per-node schedule
+    assert any(n.startswith('shaper_table[Shaper,per-block]') for n in names), names
 
 
 @pytest.mark.parametrize('pos', [0, HOUR])
@@ -369,7 +342,6 @@ def test_a_band_filter_behind_a_shaper_renders_per_node(pos):
     engine does for any input subgraph"""
     from oracle import chain_ref as R
     from signals_amd.chain import fx
-    from signals_amd.engine import BatchRenderer, KernelTimer
     p = draw()
     RS = SR.oracle_node()
     low, high = p['cut1'] * 0.5, p['cut1'] * 0.5 + 900.0
@@ -382,11 +354,7 @@ def test_a_band_filter_behind_a_shaper_renders_per_node(pos):
     want = R.render_stream(ref, pos, 256, sum(KS), V)
     tol = 1e-6 * max(1.0, L) * max(1.0, float(np.abs(want).max()))
     for route in ROUTES:
-        timer = KernelTimer()
-        r = BatchRenderer(build(), V, RATE, timer=timer, **ROUTES[route])
-        got = np.concatenate([r.render(pos, 256, 3).cpu().numpy(), r.render(pos + 768, 256, 3).cpu().numpy()])
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        got, names, _ = render_batches(build(), V, pos, 256, (3, 3), names=True, **ROUTES[route])
         assert any(n.startswith('band_coldstart') for n in names) and any(n.startswith('shaper_table') for n in names), names
         assert not any(n.startswith('voice_program') and 'Band' in n for n in names), names
         if pos or route == 'per_node':

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import render_batches
 from helpers import RATE, f32, maxerr
 import test_gpu_program_engine as E
 
@@ -48,11 +49,11 @@ def test_specialised_kernel_equals_the_interpreter_and_the_oracle(which):
         _native.set_voice_program_tuning(vpl, 2)
         node, _ = E.shapes(p, which)
         _native.voice_program_use_attached(False)                             # (attached kernels are process-wide)
-        plain = E.render_batches(node, V, 0, N, batches, fuse_program='always')
+        plain = render_batches(node, V, 0, N, batches, fuse_program='always').rows
         _native.voice_program_use_attached(True)
         node, _ = E.shapes(p, which)
         timer = KernelTimer()
-        got = E.render_batches(node, V, 0, N, batches, timer, fuse_program='always', specialise=True)
+        got = render_batches(node, V, 0, N, batches, timer=timer, fuse_program='always', specialise=True).rows
         assert any(n.startswith('voice_program[') and n.endswith('*specialised') for n in names(timer)), names(timer)
         assert maxerr(got, f32(ref)) < 1e-6 * scale, (which, vpl)
         assert maxerr(got, plain) <= 2.5e-7 * scale, (which, vpl)             # (the same operations; the compiler may order a sum differently)
@@ -60,12 +61,12 @@ def test_specialised_kernel_equals_the_interpreter_and_the_oracle(which):
         node, _ = E.shapes(p, which)
         bus = ext.SumBus(); bus.input = node; bus.get_state().gains = np.ascontiguousarray(p['pan'])
         _native.voice_program_use_attached(False)
-        plain = E.render_batches(bus, 2, 0, N, batches, fuse_program='always')
+        plain = render_batches(bus, 2, 0, N, batches, fuse_program='always').rows
         _native.voice_program_use_attached(True)
         node, _ = E.shapes(p, which)
         bus = ext.SumBus(); bus.input = node; bus.get_state().gains = np.ascontiguousarray(p['pan'])
         timer = KernelTimer()
-        got = E.render_batches(bus, 2, 0, N, batches, timer, fuse_program='always', specialise=True)
+        got = render_batches(bus, 2, 0, N, batches, timer=timer, fuse_program='always', specialise=True).rows
         assert any(n.startswith('voice_program_bus[') and n.endswith('*specialised') for n in names(timer)), names(timer)
         if which != 'amp_after_filter':
             want = ref @ p['pan'].T
@@ -89,7 +90,7 @@ def test_specialised_kernel_on_blocks_no_longer_than_the_context(N):
     node, ref_node = E.shapes(p, 'modulated_cascade')
     ref = R.render_stream(ref_node, 0, N, sum(batches), V)
     timer = KernelTimer()
-    got = E.render_batches(node, V, 0, N, batches, timer, fuse_program='always', specialise=True)
+    got = render_batches(node, V, 0, N, batches, timer=timer, fuse_program='always', specialise=True).rows
     assert any(n.endswith('*specialised') for n in names(timer)), names(timer)
     assert maxerr(got, f32(ref)) < 1e-6 * max(1.0, np.abs(ref).max()), N
 

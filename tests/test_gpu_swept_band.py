@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import close, gpu_ready, lfo, render_batches
 from helpers import RATE, f32, fix, maxerr, mkosc, stream
 
 pytestmark = pytest.mark.gpu
@@ -16,22 +17,7 @@ CLASSES = (('BandPass', 'bp'), ('BandStop', 'bs'))
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def lfo(hz, depth, centre):
-    """depth * sin + centre as Mix(Gain(Sine, 2 depth), 2 centre, 0.5): (GPU node, oracle node)"""
-    from oracle import chain_ref as R
-    from signals_amd.chain import fx
-    s = mkosc('Sine', [[hz]])
-    g = fx.Gain(); g.left = s; g.right = fix(2.0 * np.asarray(depth))
-    m = fx.Mix(); m.left = g; m.right = fix(2.0 * np.asarray(centre)); m.mix = fix([[0.5]])
-    ref = R.Binary('Mix', R.Binary('Gain', R.Osc('Sine', R.Fixed([[hz]])), R.Fixed(2.0 * np.asarray(depth))),
-                   R.Fixed(2.0 * np.asarray(centre)), R.Fixed([[0.5]]))
-    return m, ref
+    gpu_ready()
 
 
 def draw(V, seed=5):
@@ -57,22 +43,6 @@ def swept(cls, p, behind_lowpass=False, low_depth=0.4, high_depth=0.3):
     return f, R.BandFilter(btype, ref_src, ref_low, ref_high)
 
 
-def batches(node, channels, position, N, ks, timer=None, **kw):
-    from signals_amd.engine import BatchRenderer
-    r = BatchRenderer(node, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    return np.concatenate(parts)
-
-
-def close(got, ref, what):
-    scale = max(1.0, float(np.max(np.abs(ref))))
-    err = maxerr(got, ref)
-    assert err <= 1e-6 * scale, (what, err, scale)
-
-
 @pytest.mark.parametrize('pos', [0, 1000])
 @pytest.mark.parametrize('cls', [c for c, _ in CLASSES])
 def test_per_node_schedule_is_bit_identical_to_eager(cls, pos):
@@ -80,7 +50,7 @@ def test_per_node_schedule_is_bit_identical_to_eager(cls, pos):
     V, N = 96, 256
     p = draw(V)
     timer = KernelTimer()
-    got = batches(swept(cls, p)[0], V, pos, N, (4, 3), timer=timer, fuse=False)
+    got = render_batches(swept(cls, p)[0], V, pos, N, (4, 3), timer=timer, fuse=False).rows
     torch.cuda.synchronize()
     assert any(k.startswith('band_coldstart[') and k.endswith(',blocks]') for k in timer.summary()), set(timer.summary())
     want = stream(swept(cls, p)[0], pos, N, 7, V)
@@ -97,7 +67,7 @@ def test_voice_program_matches_eager(cls, pos, mode):
     kw = {'default': {}, 'always': {'fuse_program': 'always'}, 'specialise': {'specialise': True}}[mode]
     V, N = 96, 256
     p = draw(V)
-    got = batches(swept(cls, p)[0], V, pos, N, (4, 3), **kw)
+    got = render_batches(swept(cls, p)[0], V, pos, N, (4, 3), **kw).rows
     close(got, stream(swept(cls, p)[0], pos, N, 7, V), (cls, pos, mode))
 
 
@@ -118,7 +88,7 @@ def test_bus_over_a_swept_band_is_one_voice_program_launch(mode):
         b = ext.SumBus(); b.input = g; b.get_state().gains = np.ascontiguousarray(pan)
         return b
     timer = KernelTimer()
-    got = batches(build(), 2, 0, N, (4, 4), timer=timer, specialise=(mode == 'specialise'))
+    got = render_batches(build(), 2, 0, N, (4, 4), timer=timer, specialise=(mode == 'specialise')).rows
     names = set(timer.summary())
     assert any(k.startswith('voice_program_bus[') for k in names), names
     assert not any(k.startswith('band_coldstart') for k in names), names
@@ -138,7 +108,7 @@ def test_short_blocks(cls, N, behind_lowpass):
     V = 64
     p = draw(V, seed=11)
     timer = KernelTimer()
-    got = batches(swept(cls, p, behind_lowpass)[0], V, 0, N, (5, 6), timer=timer)
+    got = render_batches(swept(cls, p, behind_lowpass)[0], V, 0, N, (5, 6), timer=timer).rows
     torch.cuda.synchronize()
     assert any(k.startswith('voice_program[') for k in timer.summary()), set(timer.summary())
     close(got, stream(swept(cls, p, behind_lowpass)[0], 0, N, 11, V), (cls, N, behind_lowpass))
@@ -150,7 +120,7 @@ def test_against_the_oracle(cls, btype):
     V, N, K = 1024, 256, 16
     p = draw(V, seed=21)
     node, ref = swept(cls, p)
-    got = batches(node, V, 0, N, (K,))
+    got = render_batches(node, V, 0, N, (K,)).rows
     want = R.render_stream(ref, 0, N, K, V)
     assert maxerr(got, f32(want)) < 5e-7, cls
 

@@ -19,27 +19,20 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_WITH_DEFAULT as ROUTES, dev, gpu_ready, lfo, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, render, stream
 import unison_reference as UR
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ('Sine', 'Square', 'Sawtooth', 'Triangle')
-ROUTES = {'per_node': {'fuse': False}, 'default': {}, 'always': {'fuse_program': 'always'}, 'specialise': {'specialise': True}}
 V = 96
 KS = (4, 3)                                                                   # two consecutive batches
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
+    gpu_ready()
 
 
 def draw_copies(rng, U):
@@ -145,18 +138,6 @@ def draw(seed=3):
                          release=rng.uniform(0.01, 0.05, (1, V)), gate_on=rng.uniform(0.0, 0.01, (1, V)), gate_off=rng.uniform(0.04, 0.07, (1, V))))
 
 
-def lfo(hz, depth, centre):
-    """depth * sin + centre as Mix(Gain(Sine, 2 depth), 2 centre, 0.5): (GPU node, oracle node) -- as in tests/test_gpu_pm.py"""
-    from oracle import chain_ref as R
-    from signals_amd.chain import fx
-    s = mkosc('Sine', [[hz]])
-    g = fx.Gain(); g.left = s; g.right = fix(2.0 * np.asarray(depth))
-    m = fx.Mix(); m.left = g; m.right = fix(2.0 * np.asarray(centre)); m.mix = fix([[0.5]])
-    ref = R.Binary('Mix', R.Binary('Gain', R.Osc('Sine', R.Fixed([[hz]])), R.Fixed(2.0 * np.asarray(depth))),
-                   R.Fixed(2.0 * np.asarray(centre)), R.Fixed([[0.5]]))
-    return m, ref
-
-
 def graph(which, p, kind='Sawtooth', copies=None):
     """(GPU node, oracle node, rendered width) of one voice shape; `copies`: the array both sides read (default: the node's seven)"""
     from oracle import chain_ref as R
@@ -216,19 +197,6 @@ def wanted(which, kind, pos, N):
     return want, eager
 
 
-def batches(top, channels, position, N, ks, **kw):
-    """(the rows of consecutive batches, the names of the kernels that rendered them, the renderer)"""
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    return np.concatenate(parts), set(timer.summary()), r
-
-
 FIXED = ([('stored', kind, N) for kind in KINDS for N in (64, 256)]
          + [(which, kind, N) for which, kind in (('bus', 'Sawtooth'), ('lowpass', 'Sawtooth'), ('adsr', 'Square'), ('mix', 'Triangle'))
             for N in (64, 256)] + [('cascade', 'Sawtooth', 256), ('bus_unplugged', 'Sawtooth', 256), ('lowpass_unplugged', 'Square', 256)])
@@ -244,10 +212,10 @@ def test_routes(which, kind, N, route, pos):
         assert specialise.hipcc() is not None
     want, eager = wanted(which, kind, pos, N)
     top, _, C = graph(which, draw(), kind)
-    got, names, _ = batches(top, C, pos, N, KS, **ROUTES[route])
+    got, names, _ = render_batches(top, C, pos, N, KS, names=True, **ROUTES[route])
     what = (which, kind, N, route, pos)
     program = any(n.startswith('voice_program') for n in names)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     err = maxerr(eager, f32(want))
     print('unison eager', what, 'max|err|', err, 'tol', tol)
     assert err <= tol, (what, err)
@@ -268,14 +236,11 @@ def test_routes(which, kind, N, route, pos):
 
 # ---------------------------------------------------------------------------------------------- what ran
 def test_launches_of_each_route():
-    from signals_amd.engine import BatchRenderer, KernelTimer
+    from signals_amd.engine import KernelTimer
     p = draw()
     for route, kw in ROUTES.items():
         timer = KernelTimer()
-        r = BatchRenderer(graph('bus', p)[0], 2, RATE, timer=timer, **kw)
-        r.render(0, 256, 4)
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        _, names, r = render_batches(graph('bus', p)[0], 2, 0, 256, (4,), timer=timer, names=True, **kw)
         if route == 'per_node':
             assert names == {'osc_bank_unison[Sawtooth]', 'sum_bus'}, names   # the per-node schedule
         else:
@@ -283,10 +248,8 @@ def test_launches_of_each_route():
             name = next(iter(names))
             assert name.startswith('voice_program_bus[OscUni]'), (route, names)
             assert ('*specialised' in name) == bool(r.specialise), (route, names)         # (SIG_SPECIALISE=1 turns it on for every route)
-    timer = KernelTimer()                                                     # a swept spread: per-block rows on the per-node schedule
-    BatchRenderer(graph('lfo_spread', p, 'Sine')[0], V, RATE, timer=timer, fuse=False).render(0, 256, 4)
-    torch.cuda.synchronize()
-    assert any(n.startswith('osc_bank_unison[Sine,per-block]') for n in timer.summary()), set(timer.summary())
+    names = render_batches(graph('lfo_spread', p, 'Sine')[0], V, 0, 256, (4,), names=True, fuse=False).names      # a swept spread: per-block rows on the per-node schedule
+    assert any(n.startswith('osc_bank_unison[Sine,per-block]') for n in names), names
 
 
 @pytest.mark.parametrize('pos', [0, HOUR])
@@ -301,9 +264,9 @@ def test_a_band_filter_behind_a_unison_oscillator_renders_per_node(pos):
         bp = fx.BandPass(); bp.input = graph('stored', p)[0]; bp.low = fix(low); bp.high = fix(high)
         return bp
     want = R.render_stream(R.BandFilter('bp', graph('stored', p)[1], R.Fixed(low), R.Fixed(high)), pos, 256, sum(KS), V)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     for route, kw in ROUTES.items():
-        got, names, _ = batches(build(), V, pos, 256, KS, **kw)
+        got, names, _ = render_batches(build(), V, pos, 256, KS, names=True, **kw)
         assert any(n.startswith('osc_bank_unison') for n in names) and not any(n.startswith('voice_program') for n in names), (route, names)
         err = maxerr(got, f32(want))
         assert err <= tol, (route, pos, err, tol)
@@ -338,7 +301,7 @@ def test_an_in_place_edit_of_copies_changes_the_next_render(which, route):
     r = BatchRenderer(top, C, RATE, **ROUTES[route])
     first = r.render(0, N, K).cpu().numpy()
     want = R.render_stream(ref, 0, N, K, C)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     assert maxerr(first, f32(want)) <= tol, (which, route)
     copies[:, 0] *= 0.25                                                      # in place: the same array object
     copies[2, 1] = 0.125
@@ -381,7 +344,7 @@ def test_one_specialised_image_serves_every_detune_layout(tmp_path, monkeypatch)
         got = BatchRenderer(top, C, RATE, timer=timer, specialise=True).render(0, N, K).cpu().numpy()
         torch.cuda.synchronize()
         want = R.render_stream(ref, 0, N, K, C)
-        assert maxerr(got, f32(want)) <= 1e-6 * max(1.0, float(np.abs(want).max()))
+        assert maxerr(got, f32(want)) <= tolerance(want)
         assert set(timer.summary()) == {'voice_program_bus[OscUni]*specialised'}, set(timer.summary())     # the launch log: the image ran
         built.append(sorted(f.name for f in tmp_path.glob('vp_*.hsaco')))
         assert len(builds) == 1 and builds[0][0] == (('OscUni', 2, 0, 0, 0),), builds      # one build, at the first render, none after

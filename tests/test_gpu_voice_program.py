@@ -7,9 +7,9 @@ import pytest
 import torch
 
 from helpers import RATE, f32, maxerr
+from signals_amd.engine import CONTEXT as CTX
 
 pytestmark = pytest.mark.gpu
-CTX = 100
 KINDS = {'Sine': 0, 'Square': 1, 'Sawtooth': 2, 'Triangle': 3}
 
 

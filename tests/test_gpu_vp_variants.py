@@ -190,11 +190,9 @@ def check_label(family, sink, names):
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    import torch
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
+    from gpu_helpers import gpu_ready
+    from signals_amd import _native
+    gpu_ready()
     yield
     _native.set_voice_program_tuning(0, 0)
     _native.voice_program_use_attached(True)

@@ -16,25 +16,18 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import ROUTES_WITH_DEFAULT as ROUTES, dev, gpu_ready, render_batches, tolerance
 from helpers import HOUR, RATE, f32, fix, maxerr, mkosc, render, stream
 import wavetable_reference as WR
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = {'per_node': {'fuse': False}, 'default': {}, 'always': {'fuse_program': 'always'}, 'specialise': {'specialise': True}}
 V, KS = 200, (3, 3)
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime
-    runtime.set_device('cuda:0')
-    _native.lib()
-
-
-def dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0', dtype)
+    gpu_ready()
 
 
 def tables(T, W, seed=0):
@@ -128,17 +121,17 @@ def test_the_widest_table_fills_the_most_lds():
     want = WR.wavetable(table, HOUR, rows, hz, ph, sel)
     assert np.array_equal(out.cpu().numpy(), f32(want))
     N, ks = 128, (2, 1)                                                       # the same voices as a program: stored, and under a mono bus
-    stored, names = batches(node(table, hz, ph, sel), voices, HOUR, N, ks, fuse_program='always')
+    stored, names, _ = render_batches(node(table, hz, ph, sel), voices, HOUR, N, ks, names=True, fuse_program='always')
     gain = rng.uniform(0.2, 1.0, (1, voices))
     g = fx.Gain(); g.left = node(table, hz, ph, sel); g.right = fix(gain)
     bus = ext.SumBus(); bus.input = g
-    summed, bus_names = batches(bus, 1, HOUR, N, ks, fuse_program='always')
+    summed, bus_names, _ = render_batches(bus, 1, HOUR, N, ks, names=True, fuse_program='always')
     assert any(n.startswith('voice_program_bus[OscTable') for n in bus_names), bus_names
     block = WR.wavetable(table, HOUR, N * sum(ks), hz, ph, sel)
     if any(n.startswith('voice_program') for n in names):                     # (a single node may stay its own kernel)
         assert np.array_equal(stored, f32(block))
     ref = np.sum(block * gain, axis=1, keepdims=True)
-    assert maxerr(summed, f32(ref)) <= 1e-6 * max(1.0, float(np.abs(ref).max()))
+    assert maxerr(summed, f32(ref)) <= tolerance(ref)
 
 
 # ---------------------------------------------------------------------------------------------- the eager node
@@ -276,19 +269,6 @@ def wanted(which, pos, N):
     return want, eager
 
 
-def batches(top, channels, position, N, ks, **kw):
-    """(the rows of consecutive batches, the names of the kernels that rendered them)"""
-    from signals_amd.engine import BatchRenderer, KernelTimer
-    timer = KernelTimer()
-    r = BatchRenderer(top, channels, RATE, timer=timer, **kw)
-    parts, pos = [], position
-    for k in ks:
-        parts.append(r.render(pos, N, k).cpu().numpy())
-        pos += N * k
-    torch.cuda.synchronize()
-    return np.concatenate(parts), set(timer.summary())
-
-
 CASES = [(which, N) for which in ('bus', 'lowpass_bus', 'adsr', 'lfo', 'mix') for N in (64, 256)] + [('cascade', 256)]
 
 
@@ -301,10 +281,10 @@ def test_routes(which, N, route, pos):
         assert specialise.hipcc() is not None
     want, eager = wanted(which, pos, N)
     top, _, C, exact = graph(which, draw())
-    got, names = batches(top, C, pos, N, KS, **ROUTES[route])
+    got, names, _ = render_batches(top, C, pos, N, KS, names=True, **ROUTES[route])
     what = (which, N, route, pos)
     program = any(n.startswith('voice_program') for n in names)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     err = maxerr(eager, f32(want))
     print('wavetable eager', what, 'max|err|', err, 'tol', tol)
     assert err <= tol, (what, err)                                            # (float32 between its nodes: never bit-equal to the oracle)
@@ -321,24 +301,17 @@ def test_routes(which, N, route, pos):
 
 
 def test_launches_of_each_route():
-    from signals_amd.engine import BatchRenderer, KernelTimer
     p = draw()
     for route, kw in ROUTES.items():
-        timer = KernelTimer()
-        r = BatchRenderer(graph('bus', p)[0], 2, RATE, timer=timer, **kw)
-        r.render(0, 256, 4)
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        _, names, r = render_batches(graph('bus', p)[0], 2, 0, 256, (4,), names=True, **kw)
         if route == 'per_node':
             assert any(n.startswith('osc_bank_table[Table]') for n in names) and not any(n.startswith('voice_program') for n in names), names
         else:
             assert any(n.startswith('voice_program_bus[OscTable') for n in names), (route, names)
             assert not any(n.startswith(('osc_bank', 'sum_bus')) for n in names), (route, names)
             assert any('*specialised' in n for n in names) == bool(r.specialise), (route, names)
-    timer = KernelTimer()                                                     # a swept hertz: per-block rows on the per-node schedule
-    BatchRenderer(graph('lfo', p)[0], V, RATE, timer=timer, fuse=False).render(0, 256, 4)
-    torch.cuda.synchronize()
-    assert any(n.startswith('osc_bank_table[Table,per-block]') for n in timer.summary()), set(timer.summary())
+    names = render_batches(graph('lfo', p)[0], V, 0, 256, (4,), names=True, fuse=False).names      # a swept hertz: per-block rows on the per-node schedule
+    assert any(n.startswith('osc_bank_table[Table,per-block]') for n in names), names
 
 
 @pytest.mark.parametrize('pos', [0, HOUR])
@@ -346,7 +319,6 @@ def test_a_band_filter_behind_a_wavetable_renders_per_node(pos):
     """no interpreter variant has both instructions: the engine keeps the graph one kernel per node, on every route"""
     from oracle import chain_ref as R
     from signals_amd.chain import fx
-    from signals_amd.engine import BatchRenderer, KernelTimer
     p = draw()
     RW = WR.oracle_node()
     low, high = p['cut1'] * 0.5, p['cut1'] * 0.5 + 900.0
@@ -356,13 +328,9 @@ def test_a_band_filter_behind_a_wavetable_renders_per_node(pos):
         return bp
     ref = R.BandFilter('bp', RW(TABLE, R.Fixed(p['hertz']), R.Fixed(p['phase']), R.Fixed(p['select'])), R.Fixed(low), R.Fixed(high))
     want = R.render_stream(ref, pos, 256, sum(KS), V)
-    tol = 1e-6 * max(1.0, float(np.abs(want).max()))
+    tol = tolerance(want)
     for route in ('default', 'always'):
-        timer = KernelTimer()
-        r = BatchRenderer(build(), V, RATE, timer=timer, **ROUTES[route])
-        got = np.concatenate([r.render(pos, 256, 3).cpu().numpy(), r.render(pos + 768, 256, 3).cpu().numpy()])
-        torch.cuda.synchronize()
-        names = set(timer.summary())
+        got, names, _ = render_batches(build(), V, pos, 256, (3, 3), names=True, **ROUTES[route])
         assert any(n.startswith('osc_bank_table') for n in names) and not any(n.startswith('voice_program') for n in names), names
         assert maxerr(got, f32(want)) <= tol, (route, pos, maxerr(got, f32(want)), tol)
 

@@ -11,6 +11,8 @@ import pytest
 import torch
 
 from helpers import HOUR, RATE, Probe, f32, fix, loc, maxerr, mkosc
+import gpu_helpers as GH
+from gpu_helpers import render_batches
 import test_gpu_filtered_control as FC
 import test_gpu_voice_program as VP
 
@@ -23,10 +25,8 @@ POSITIONS = (0, 1, 2 ** 31 - 40, 2 ** 32 - 40, HOUR, 2 ** 40 - 17)
 
 @pytest.fixture(scope='module', autouse=True)
 def _gpu():
-    assert torch.cuda.is_available()
-    from signals_amd import _native, runtime, specialise
-    runtime.set_device('cuda:0')
-    _native.lib()
+    from signals_amd import _native, specialise
+    GH.gpu_ready()
     yield
     torch.cuda.synchronize()
     specialise.forget()                                                       # (attached kernels and the tuning are process-wide)
@@ -41,8 +41,8 @@ def need_hipcc():
 
 
 def close(got, ref, what):
-    """the `close` of tests/test_gpu_filtered_control.py; returns max |ref|"""
-    FC.close(got, ref, what)
+    """the `close` of tests/gpu_helpers.py; returns max |ref|"""
+    GH.close(got, ref, what)
     return float(np.max(np.abs(ref)))
 
 
@@ -344,7 +344,7 @@ def test_filtered_white_in_the_voice_program(ftype, N):
         want = R.render_stream(build()[1], pos, N, 5, V)
         for kw in modes:
             timer = KernelTimer()
-            got = FC.batches(build()[0], V, pos, N, (3, 2), timer=timer, **kw)
+            got = render_batches(build()[0], V, pos, N, (3, 2), timer=timer, **kw).rows
             assert any(n.startswith('voice_program[Noise,Filter]') for n in names(timer)), names(timer)
             assert 'specialise' not in kw or any(n.endswith('*specialised') for n in names(timer)), names(timer)
             close(got, want, (ftype, N, pos, kw))
@@ -364,7 +364,7 @@ def test_two_filters_over_white():
         return outer
     want = R.render_stream(R.Filter('lp', R.Filter('lp', R.White(seed, V), R.Fixed(c1)), R.Fixed(c2)), 0, N, 6, V)
     for kw in [{'fuse_program': 'always'}] + ([{'fuse_program': 'always', 'specialise': True}] if specialise.hipcc() is not None else []):
-        close(FC.batches(build(), V, 0, N, (3, 1, 2), **kw), want, kw)
+        close(render_batches(build(), V, 0, N, (3, 1, 2), **kw).rows, want, kw)
 
 
 @pytest.mark.parametrize('mode', ['per-node', 'default', 'always', 'specialise'])
@@ -397,7 +397,7 @@ def test_subtractive_voice_under_a_bus(V, mode):
     voice = R.render_stream(R.Binary('RingMod', R.Filter('lp', R.White(seed, V), R.Fixed(cut)), R.Adsr(**env)), 0, N, 7, V)
     for gains in (None, pan):
         want = R.sum_bus(voice, gains)
-        got = FC.batches(build(gains), want.shape[1], 0, N, (4, 3), **kw)
+        got = render_batches(build(gains), want.shape[1], 0, N, (4, 3), **kw).rows
         close(got, want, (V, mode, gains is None))
 
 
@@ -448,5 +448,5 @@ def test_whole_graphs_against_the_oracle(name, V, mode):
     if mode == 'specialise':
         need_hipcc()
     build, C, want = whole_graph(name, V)
-    got = FC.batches(build(), C, 0, 256, (4, 3), **SCHEDULES[mode])
+    got = render_batches(build(), C, 0, 256, (4, 3), **SCHEDULES[mode]).rows
     close(got, want, (name, V, mode))
