@@ -113,6 +113,27 @@ int sig_osc_bank_table(int64_t position, int64_t position_step, int32_t rate, in
                        const float* table, int32_t table_points, int32_t table_waves,
                        void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Additive oscillator, chain/ext.py Additive: up to SIG_ADDITIVE_MAX_PARTIALS harmonics per voice with amplitudes from a table, the
+ * partials above half the rate dropped per voice and parameter row.  `table` float32 (H, W) row-major in device memory, row h - 1
+ * the amplitude of harmonic h for each of W spectra, 1 <= H <= SIG_ADDITIVE_MAX_PARTIALS, W >= 1, H * W <= SIG_TABLE_MAX_POINTS:
+ *   t  = (position + n * position_step) / rate * hertz[v] + phase[v];  m = np.mod(t, 1.0)         (f64, that order)
+ *   w  = clip(floor(select[v]), 0, W - 1)                                   (NaN -> 0; select NULL = unplugged = column 0)
+ *   nf = (0.5 * rate) / |hertz[v]|;  k = clip(ceil(nf) - 1, 0, H);  g = min(1.0, nf - k)
+ *   out[n,v] = sum over h = 1 .. k of a[h-1, w] * (h == k ? g : 1) * sin(2 pi h m)                  a = (double) table
+ * k == 0 (|hertz| >= rate / 2, +-inf too): exactly 0.0; a NaN hertz: NaN; a non-finite phase with k >= 1: NaN.  hertz / phase /
+ * select rows like sig_osc_bank_table (per block with rows_per_param).  Position-pure.  Held to a bound, not to bits: both stores
+ * within 1e-6 * max(1, A) of the definition with the sum in extended precision, A the largest column sum of |a| (measured:
+ * DESIGN.md).  A null table / hertz / out, H or H * W out of range, out_ld < voices, a negative position or a stride other than
+ * 0 / 1: hipErrorInvalidValue, nothing launched; rows == 0: no launch. */
+enum { SIG_ADDITIVE_MAX_PARTIALS = 64 };
+int sig_osc_bank_additive(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                          int32_t voices, int32_t rows_per_param,
+                          const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                          const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                          const double* select, int32_t select_stride, int64_t select_row_stride,
+                          const float* table, int32_t table_partials, int32_t table_waves,
+                          void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Unison oscillator, chain/ext.py UnisonSine / UnisonSquare / UnisonSawtooth / UnisonTriangle: `copies` detuned copies of one waveform
  * per voice, summed and divided by their number (the supersaw, detuned square leads, thickened sines).  For row n and voice v, in
  * f64, every operation rounded, u = 0 .. copies - 1 ascending:

@@ -72,6 +72,7 @@ VP_FAMILIES = {'band': ('Band',), 'pm': ('OscPM',), 'table': VP_TABLE_OPS, 'reso
 VP_VARIANTS = ('plain', 'band', 'pm', 'table', 'shape', 'resonant', 'unison', 'blep', 'mixed')    # SIG_VP_FAMILY_*: the interpreter's variants (`voice_program_variant`)
 UNISON_MAX_COPIES = 16                      # SIG_UNISON_MAX_COPIES: copies of a unison oscillator (ext.py UnisonOsc)
 TABLE_MAX_POINTS = 16384                    # SIG_TABLE_MAX_POINTS: entries of a wavetable or a shaper table (of a voice program's tables together)
+ADDITIVE_MAX_PARTIALS = 64                  # SIG_ADDITIVE_MAX_PARTIALS: rows of an additive oscillator's table (ext.py Additive): harmonics per voice
 DELAY_CONTEXT = 100                         # SIG_DELAY_CONTEXT: the rows of context in front of a delay line's block, the filters' window
 DELAY_MAX_FRAMES = 99                       # SIG_DELAY_MAX_FRAMES: the longest delay (ext.py Delay): the context minus the one further row the interpolation reads
 DELAY_MAX_TAPS = 16                         # SIG_DELAY_MAX_TAPS: taps of a delay line
@@ -140,6 +141,7 @@ def _argtypes() -> dict:
         'sig_osc_bank_pm': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64,
                             vp, i32, i64, i32, vp, i32, i64, vp],
         'sig_osc_bank_table': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
+        'sig_osc_bank_additive': [i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, vp, i32, i32, vp, i32, i64, vp],
         'sig_osc_bank_unison': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_osc_bank_blep': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
         'sig_osc_bank_sync': [cint, i64, i64, i32, i64, i32, i32, dp, i32, i64, dp, i32, i64, dp, i32, i64, dp, i32, i64, i32, dp, dp, vp, i32, i64, vp],
@@ -454,6 +456,25 @@ def osc_bank_table(position: int, rate: int, hertz: torch.Tensor, phase: torch.T
     head, (h, p, s), tail = _osc_launch(out, position, step, rate, rows_per_param, (hertz, 'hertz'), (phase, 'phase'), (select, 'select'),
                                         also=(table,))
     _check(lib().sig_osc_bank_table(*head, *h, *p, *s, *_table(table), *tail), 'sig_osc_bank_table')
+    return out
+
+
+def _spectra(table: torch.Tensor):
+    """(ptr, partials, waves) of an additive oscillator's amplitudes: float32 (H, W) contiguous on the device, 1 <= H <=
+    ADDITIVE_MAX_PARTIALS, H * W within the cap"""
+    return _device_table(table, torch.float32, 'a table of partial amplitudes', 'partials, waves',
+                         lambda H, W: 1 <= H <= ADDITIVE_MAX_PARTIALS and W >= 1 and H * W <= TABLE_MAX_POINTS,
+                         f'table {{shape}}: 1 <= partials <= {ADDITIVE_MAX_PARTIALS}, partials * waves <= {TABLE_MAX_POINTS}')
+
+
+def osc_bank_additive(position: int, rate: int, hertz: torch.Tensor, phase: torch.Tensor | None, select: torch.Tensor | None,
+                      table: torch.Tensor, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- additive oscillator (sig_osc_bank_additive): the sum of the harmonics h = 1 .. k of the phase
+    np.mod(n / rate * hertz + phase, 1) with the amplitudes of column clip(floor(select), 0, W - 1) of the (H, W) float32 `table`, k the
+    partials below half the rate per voice and parameter row.  hertz / phase / select: (1|P, V|1) f64 like `osc_bank`."""
+    head, (h, p, s), tail = _osc_launch(out, position, step, rate, rows_per_param, (hertz, 'hertz'), (phase, 'phase'), (select, 'select'),
+                                        also=(table,))
+    _check(lib().sig_osc_bank_additive(*head, *h, *p, *s, *_spectra(table), *tail), 'sig_osc_bank_additive')
     return out
 
 

@@ -219,6 +219,112 @@ class Wavetable(BlockCachingEmitter, ImplicitChannels):
         return _native.osc_bank_table(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
 
 
+def _validate_spectra(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
+          and 1 <= new_value.shape[0] <= _native.ADDITIVE_MAX_PARTIALS and new_value.shape[1] >= 1
+          and new_value.shape[0] * new_value.shape[1] <= _native.TABLE_MAX_POINTS
+          and bool(np.isfinite(new_value).all()))
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a finite 2D real array (partials, waves), 1 <= partials <= {_native.ADDITIVE_MAX_PARTIALS}, '
+                            f'partials * waves <= {_native.TABLE_MAX_POINTS}')
+
+
+def _harmonics(H: int) -> np.ndarray:
+    """1 .. H as float64, H checked against the node's limit"""
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= _native.ADDITIVE_MAX_PARTIALS:
+        raise ValueError(f'partials must be an integer 1 .. {_native.ADDITIVE_MAX_PARTIALS}, got {H!r}')
+    return np.arange(1, int(H) + 1, dtype=np.float64)
+
+
+class Additive(Wavetable):
+    """Band-limited additive oscillator: up to 64 harmonics per voice with amplitudes from a table, the partials above half the rate
+    dropped per voice and block -- organ drawbars, formant and vocal spectra, and saws, squares and triangles that stay clean up to
+    Nyquist under a pitch envelope, which neither `Wavetable` (it aliases as the pitch rises; mip columns cannot follow a sweep) nor
+    `BlepOsc` (three fixed shapes) does.  `Wavetable` -- the same three block-rate ports hertz, phase and select, the same `table` state
+    name and resident float32 device copy, the same phase t bit for bit -- with the table read as a spectrum: an (H, W) array, row
+    h - 1 the amplitude of harmonic h for each of W spectra, 1 <= H <= 64, W >= 1, H * W <= 16384, no power-of-two rule, every value
+    finite, negative amplitudes allowed (a triangle needs them); integer arrays convert as they do for `Wavetable`.  The default
+    [[1.0]] is a sine.  With `select` it switches timbres, through `fx.Mix` of two nodes it cross-fades them.  With a = float32(table)
+    widened to float64, for row n and voice v, in float64 and every operation rounded:
+        t  = frame_range / rate * hertz + phase                            (osc.py's order)
+        m  = np.mod(t, 1.0)
+        w  = clip(floor(select), 0, W - 1)                                 (NaN and unplugged: column 0, as Wavetable)
+        nf = (0.5 * rate) / abs(hertz)                                     (IEEE divide; 0 Hz gives inf)
+        k  = clip(ceil(nf) - 1, 0, H)                                      (the partials h with h |hertz| < rate / 2; inf gives H)
+        g  = min(1.0, nf - k)                                              (the weight of the top kept partial only)
+        out = sum over h = 1 .. k of c_h * sin(2 pi h m),   c_h = a[h-1, w] * (g if h == k else 1)
+    (kernel: sig_osc_bank_additive; restated in numpy by tests/additive_reference.py).  k and g are per voice and per block, since
+    `hertz` is block-rate.  g makes the output continuous in `hertz`: a partial fades linearly to nothing over the last harmonic
+    spacing before it reaches Nyquist, so a pitch sweep does not click when a partial drops out; only one partial per voice and block
+    is ever scaled.  k = 0 (|hertz| >= rate / 2, +-inf too) gives exactly 0.0 whatever the phase; a NaN `hertz` gives NaN; with
+    k >= 1 a non-finite `phase` (or t) gives NaN.  hertz < 0 uses |hertz| for k and g, and its sign enters through t.  There is no
+    normalisation: the peak is bounded by the column's sum of |a|.
+    Because of the sine the kernel is held to a bound, not to bits: every sample, float32 rows and the float64 of a one-frame request
+    alike, within 1e-6 * max(1, A) of the definition with the partial sum in extended precision, A the largest column sum of |a|.
+    The kernel takes one sine / cosine pair of 2 pi m per sample and turns it h times by a plane rotation, whose error grows linearly
+    in h at every pitch.  Measured on an MI355X over the kernel cases of tests/test_gpu_additive.py: 1.8e-15 at most in front of the float64 store (A up to 2.6, H up
+    to 64, the 0.01 Hz voice 7e-16), 5.9e-8 behind the float32 store, which is that store's own rounding of a sample above 1/2: 17 times
+    inside the bar.
+    Position-pure: no carried phase, no history.  The batched engine renders the node with one kernel per batch; it has no
+    voice-program word, so a graph that contains one runs one kernel per node (the nodes around it keep their routes, as with
+    `Ladder`), `mixed_programs` and `specialise` or not.
+    Spectra (static, numpy on the host, one float64 column each): `Additive.sawtooth(H)`, `Additive.square(H)`,
+    `Additive.triangle(H)` converge to `osc.Sawtooth`, `osc.Square`, `osc.Triangle` at the same phase as H grows;
+    `Additive.cycle(column, T)` renders a column to a T-point single cycle for a `Wavetable`.
+    Out of scope: cosine (phase) terms per partial (a second table and a second accumulation: the spectra here are odd functions of
+    the phase); inharmonic partial ratios (the node is a pure function of the wrapped phase m, and sin(2 pi r m) is one only for an
+    integer r); a frame-rate `hertz` or `select` (k, g and the column are hoisted per block); per-voice private tables (one table per
+    launch sits in LDS); a voice-program word and the closed-form, row-walker and cascade fused kernels (they keep matching `osc.Osc`
+    only); the node inside a block-rate control path (the batched engine answers NotBatchable with the reason and the graph keeps
+    the eager path, which serves frames == 1 in float64); more than 64 partials (the table's rows, and the recurrence's error bound,
+    are sized for 64)."""
+
+    @state
+    class State(Wavetable.State):
+        table: np.ndarray = attr.ib(factory=lambda: np.array([[1.0]]), validator=_validate_spectra, on_setattr=attr.setters.validate)
+
+    # ---- spectra: numpy on the host, one (H, 1) float64 column each
+    @staticmethod
+    def sawtooth(H: int = 64) -> np.ndarray:
+        """the first H harmonics of osc.Sawtooth, 2 mod(t - 1/2, 1) - 1 = sum 2 / (pi h) (-1)^(h+1) sin(2 pi h t)"""
+        h = _harmonics(H)
+        return (2.0 / (np.pi * h) * np.where(h % 2 == 1, 1.0, -1.0)).reshape(-1, 1)
+
+    @staticmethod
+    def square(H: int = 64) -> np.ndarray:
+        """the first H harmonics of osc.Square, sign(1/2 - mod(t, 1)) = sum over odd h of 4 / (pi h) sin(2 pi h t)"""
+        h = _harmonics(H)
+        return np.where(h % 2 == 1, 4.0 / (np.pi * h), 0.0).reshape(-1, 1)
+
+    @staticmethod
+    def triangle(H: int = 64) -> np.ndarray:
+        """the first H harmonics of osc.Triangle (peak +1 at t = 1/4): sum over odd h of 8 / (pi h)^2 (-1)^((h-1)/2) sin(2 pi h t)"""
+        h = _harmonics(H)
+        return np.where(h % 2 == 1, 8.0 / (np.pi * h) ** 2 * np.where(h % 4 == 1, 1.0, -1.0), 0.0).reshape(-1, 1)
+
+    @staticmethod
+    def cycle(column, T: int = 2048) -> np.ndarray:
+        """one column of amplitudes as a (T, 1) single cycle, sum_h a_h sin(2 pi h i / T) for i = 0 .. T - 1 with every partial
+        at full weight: what a `Wavetable` of T points plays where it does not alias (T > 2 H keeps the partials apart)"""
+        a = np.asarray(column, dtype=np.float64).reshape(-1)
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 2:
+            raise ValueError(f'a cycle has an integer number of points >= 2, got {T!r}')
+        i = np.arange(int(T), dtype=np.float64)
+        h = np.arange(1, a.shape[0] + 1, dtype=np.float64)
+        angle = np.mod(np.outer(i, h), float(T)) / float(T)                    # exact: i * h < 2**53
+        return (np.sin(2.0 * np.pi * angle) @ a).reshape(-1, 1)
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        phase = as_control(self.phase.forward_at_block_rate(request))
+        hertz = as_control(self.hertz.forward_at_block_rate(request))
+        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
+        loc = request.loc
+        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, select.shape)
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
+        return _native.osc_bank_additive(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
+
+
 UNISON_DETUNE = (-0.11002313, -0.06288439, -0.01952356, 0.0, 0.01991221, 0.06216538, 0.10745242)
 
 

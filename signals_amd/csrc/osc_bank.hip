@@ -251,6 +251,141 @@ __global__ __launch_bounds__(64 * kTableWaves) void osc_bank_table_kernel(OscArg
     }
 }
 
+// ---- additive: out = sum over h = 1 .. k of c_h sin(2 pi h m), m = np.mod(n / rate * hertz + phase, 1), the amplitudes a (H, W) float32
+// table -- row h - 1 the harmonic h, column w = clip(floor(select), 0, W - 1) per voice -- and k, g the band limit per voice and
+// parameter row (chain/ext.py Additive): nf = (rate / 2) / |hertz|, k = clip(ceil(nf) - 1, 0, H), g = min(1, nf - k) on partial k alone.
+// The wavetable kernel's workgroup, rows and stores: 512 threads stage the table in LDS once (column-major, sig_table.h's
+// stage_columns; the column stride H | 1 where that fits 64 KiB, so that equal harmonics of different columns fall on different
+// banks, else H) and each wave walks `groups` 16-row groups of its 64 * VEC voices.
+// Hoisted, once per voice and parameter row: the IEEE divide for nf, k, the column's first float, and the wave's largest k, which
+// bounds the partial loop (a butterfly over the lanes; the loop counter is then scalar).  The weight of partial h is
+//   clamp(nf - h, 0, 1)  ==  1 for h < k,  g for h == k,  0 for h > k
+// in the definition's own bits (nf - h >= 1 below k and <= 0 above it, since k >= nf - 1; at h == k the subtraction IS the
+// definition's; a k clipped to H leaves h <= H only): lanes with a smaller k than the wave's are predicated off by a zero weight,
+// and no lane compares h with its k.  k == 0 is answered 0.0 and a NaN hertz NaN by a select behind the loop (0 * NaN is no zero).
+// Per sample: t and m as every oscillator here (two roundings, np.mod), ONE sine / cosine pair of 2 pi m (sig_osc::cycle_sincos,
+// < 3e-16 each), then the plane rotation
+//   s_{h+1} = s_h C + c_h S,   c_{h+1} = c_h C - s_h S,   acc += c_h_weighted * s_h          (S, C = sin, cos of 2 pi m; 2 mul + 3 fma)
+// Why this holds 1e-6 * max(1, sum |a|) everywhere, the 0.01 Hz voice included: a rotation by a matrix whose entries are off by
+// < 3e-16 keeps |(s, c)| within 1 + 5e-16 per step and turns the angle by theta (1 + O(1e-16)) + O(3e-16), so after h steps s_h is
+// within ~ h * 1e-15 of sin(h theta) -- linear in h, < 7e-14 at h = 64 -- whatever theta is; nothing divides by theta or by
+// 2 - 2 cos(theta), which is where the three-term recurrence s_{h+1} = 2 cos(theta) s_h - s_{h-1} loses eps h^2 / theta.  The sum
+// adds < 64 roundings of terms bounded by |a_h|.  The float32 store's own rounding (6e-8 relative) is what is left.
+// R consecutive rows of a voice go through the partial loop together: one LDS read, one conversion and one weight feed R chains of
+// 5 dependent float64 operations each, VEC * R independent chains per lane.  Passes are cut where the parameter row changes.
+// Roofline: 4 B written per voice-sample against 5 k float64 operations: float64-VALU-bound from a few partials on.
+struct AddArgs {
+    const float* table; int H, W, S;                               // (H, W) row-major, device memory; S: the column stride in LDS
+    const double* select; int ss; int64_t srs;                     // (1|P, V|1) f64 like hertz / phase; NULL: unplugged = column 0
+    int groups;                                                    // 16-row groups per wave
+};
+
+template <int VEC, int R, typename OUT>
+__global__ __launch_bounds__(64 * kTableWaves) void osc_bank_additive_kernel(OscArgs a, AddArgs ad, OUT* __restrict__ out, int64_t ld, int voice_tiles)
+{
+    extern __shared__ float tab[];                                 // [W][S]
+    const int H = ad.H, W = ad.W, S = ad.S;
+    sig_table::stage_columns<64 * kTableWaves>(tab, ad.table, H, W, S);
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int vt = blockIdx.x % voice_tiles;
+    const int64_t rt = blockIdx.x / voice_tiles;
+    const int v0 = (vt * SIG_WAVE + lane) * VEC;
+    const double nyquist = 0.5 * a.rate;
+
+    double hz[VEC], ph[VEC], nf[VEC];
+    int col[VEC], kk[VEC];                                         // the voice's column: its first float in `tab`; its k
+    int kmax = 0;                                                  // the wave's largest k (wave-uniform)
+    int64_t loaded = -1;                                           // parameter row currently in registers
+    for (int g = 0; g < ad.groups; ++g) {
+        const int64_t r0 = ((rt * ad.groups + g) * kTableWaves + wave) * kRowsPerWave;
+        if (r0 >= a.rows) break;                                   // wave-uniform
+        const int nrows = (int)((a.rows - r0 < (int64_t)kRowsPerWave) ? a.rows - r0 : (int64_t)kRowsPerWave);
+        const double q_lane = row_quotients(a, r0, lane);
+        for (int j = 0; j < nrows;) {                              // passes of up to R rows of one parameter row (wave-uniform bounds)
+            const int64_t row = r0 + j;
+            const int64_t prow = a.rpp ? row / a.rpp : 0;
+            int n = (nrows - j < R) ? nrows - j : R;
+            if (a.rpp) {
+                const int64_t left = (prow + 1) * a.rpp - row;
+                if (left < (int64_t)n) n = (int)left;
+            }
+            if (prow != loaded) {
+                loaded = prow;
+                int top = 0;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const int v = v0 + i;
+                    const bool live = v < a.voices;
+                    hz[i] = live ? a.hertz[prow * a.hrs + (int64_t)v * a.hs] : 0.0;
+                    ph[i] = (live && a.phase) ? a.phase[prow * a.prs + (int64_t)v * a.ps] : 0.0;
+                    col[i] = sig_table::column((live && ad.select) ? ad.select[prow * ad.srs + (int64_t)v * ad.ss] : 0.0, W) * S;
+                    nf[i] = nyquist / fabs(hz[i]);                 // IEEE divide; 0 Hz: inf, every partial at weight 1
+                    const double kd = ceil(nf[i]) - 1.0;
+                    kk[i] = (live && kd >= 1.0) ? ((kd >= (double)H) ? H : (int)kd) : 0;      // clip; NaN -> 0 (answered NaN below)
+                    top = (kk[i] > top) ? kk[i] : top;
+                }
+#pragma unroll
+                for (int mask = 1; mask < SIG_WAVE; mask <<= 1) {
+                    const int other = __shfl_xor(top, mask, SIG_WAVE);
+                    top = (other > top) ? other : top;
+                }
+                kmax = __builtin_amdgcn_readfirstlane(top);
+            }
+            double s[R][VEC], c[R][VEC], S1[R][VEC], C1[R][VEC], acc[R][VEC];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double q = sig_readlane_f64(q_lane, (j + r) & (kRowsPerWave - 1));      // (rows past n: computed, not stored)
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const double t = q * hz[i] + ph[i];            // two roundings, like numpy
+                    sig_osc::cycle_sincos(sig_npmod_pow2<1>(t), S1[r][i], C1[r][i]);
+                    s[r][i] = S1[r][i]; c[r][i] = C1[r][i]; acc[r][i] = 0.0;
+                }
+            }
+            for (int h = 1; h <= kmax; ++h) {                      // scalar bounds; h <= kmax <= H, so col + h - 1 stays inside the column
+                const double hd = (double)h;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const double weight = fmin(fmax(nf[i] - hd, 0.0), 1.0);
+                    const double amp = (double)tab[col[i] + h - 1] * weight;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        acc[r][i] = fma(amp, s[r][i], acc[r][i]);
+                        const double sn = fma(s[r][i], C1[r][i], c[r][i] * S1[r][i]);
+                        c[r][i] = fma(c[r][i], C1[r][i], -(s[r][i] * S1[r][i]));
+                        s[r][i] = sn;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (r < n) {                                       // wave-uniform
+                    OUT y[VEC];
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        y[i] = (OUT)((hz[i] != hz[i]) ? hz[i] : ((kk[i] == 0) ? 0.0 : acc[r][i]));
+                    OUT* dst = out + (row + r) * ld + v0;
+                    if (VEC == 4) {
+                        if (v0 < a.voices) {                       // voices % 4 == 0 on this path
+                            typename sig_vec4<OUT>::type o;
+                            o.x = y[0]; o.y = y[1]; o.z = y[2]; o.w = y[3];
+                            *reinterpret_cast<typename sig_vec4<OUT>::type*>(dst) = o;
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i)
+                            if (v0 + i < a.voices) dst[i] = y[i];
+                    }
+                }
+            }
+            j += n;
+        }
+    }
+}
+
 // ---- unison: the mean of `copies` detuned copies of one waveform per voice (chain/ext.py UnisonOsc),
 //   r_u = 1 + spread * d[u];  h_u = hertz * r_u;  q_u = phase + p[u];  t_u = n / rate * h_u + q_u;  out = (sum_u w(t_u)) / copies
 // every operation rounded in that order, the sum in u ascending.  Same mapping as osc_bank_kernel (a wave = 64 * VEC voices x 16
@@ -604,6 +739,27 @@ int run_table(const OscArgs& a, TableArgs tb, void* out, int32_t out_dtype, int6
     });
 }
 
+// rows of a voice that go through the partial loop together (R of osc_bank_additive_kernel): 8 chains per lane with four voices,
+// 4 with one -- 16 chains spill (256 VGPRs and scratch), these compile to 195 and 96 VGPRs without any
+template <int VEC> constexpr int kAdditiveRows = (VEC == 4) ? 2 : 4;
+
+int run_additive(const OscArgs& a, AddArgs ad, void* out, int32_t out_dtype, int64_t ld, hipStream_t s)
+{
+    return dispatch_out(out, out_dtype, [&](auto* o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        const VoiceTiling vt = voice_tiling(a, o, ld);
+        const int64_t rows_per_pass = (int64_t)kRowsPerWave * kTableWaves;
+        const int64_t passes = (a.rows + rows_per_pass - 1) / rows_per_pass;
+        // run_table's rule: as many row groups per wave as still leave two workgroups for every CU of an MI355X
+        ad.groups = 8;
+        while (ad.groups > 1 && ((passes + ad.groups - 1) / ad.groups) * vt.voice_tiles < 512) ad.groups >>= 1;
+        const size_t lds = (size_t)ad.S * ad.W * sizeof(float);
+        return launch_tiles(vt, (passes + ad.groups - 1) / ad.groups, [&](auto vec, unsigned nwg, int voice_tiles) {
+            osc_bank_additive_kernel<decltype(vec)::value, kAdditiveRows<decltype(vec)::value>, OUT><<<nwg, 64 * kTableWaves, lds, s>>>(a, ad, o, ld, voice_tiles);
+        });
+    });
+}
+
 // the three launches of (OscArgs, UniArgs[, SyncArgs]) kernels: LAUNCH(Const<KIND>, Const<VEC>, out, workgroups, voice_tiles)
 template <int... KINDS, typename LAUNCH>
 int run_copies(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t ld, LAUNCH&& launch)
@@ -736,6 +892,28 @@ extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32
     if (rows == 0 || voices == 0) return 0;
     const TableArgs tb{table, table_points, table_waves, select, select_stride, select_row_stride, 1};
     return run_table(a, tb, out, out_dtype, out_ld, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sig_osc_bank_additive(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                                     int32_t voices, int32_t rows_per_param,
+                                     const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                                     const double* phase, int32_t phase_stride, int64_t phase_row_stride,
+                                     const double* select, int32_t select_stride, int64_t select_row_stride,
+                                     const float* table, int32_t table_partials, int32_t table_waves,
+                                     void* out, int32_t out_dtype, int64_t out_ld, void* stream)
+{
+    OscArgs a;
+    SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
+                     phase, phase_stride, phase_row_stride, out, out_ld));
+    SIG_CHECK_ARG(row_strides_ok(select_stride, select_row_stride));
+    SIG_CHECK_ARG(table != nullptr && table_partials >= 1 && table_partials <= SIG_ADDITIVE_MAX_PARTIALS && table_waves >= 1 &&
+                  (int64_t)table_partials * table_waves <= SIG_TABLE_MAX_POINTS);
+    SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
+    if (rows == 0 || voices == 0) return 0;
+    const int odd = table_partials | 1;                            // (the odd stride where the table still fits 64 KiB of LDS)
+    const int stride = ((int64_t)odd * table_waves <= SIG_TABLE_MAX_POINTS) ? odd : table_partials;
+    const AddArgs ad{table, table_partials, table_waves, stride, select, select_stride, select_row_stride, 1};
+    return run_additive(a, ad, out, out_dtype, out_ld, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step, int32_t rate, int64_t rows,

@@ -253,6 +253,38 @@ __device__ __forceinline__ double osc_sync(double t, double d, double inv_d, con
     return ((naive + edge) - sync_residual(sb - kb, ds, inv_ds, kb >= 1.0, kb + 0.5 < r.R)) + reset;
 }
 
+// ---- additive oscillator (chain/ext.py Additive): sin and cos of 2 pi m for a phase m = mod(t, 1) in [0, 1], the seed of the
+// harmonic recurrence of osc_bank_additive_kernel.  cos(x) for |x| <= pi/2 + eps, even Taylor polynomial through x^22 (remainder
+// < 1e-19), beside sin_poly.
+__device__ __forceinline__ double cos_poly(double x) {
+    const double s = x * x;
+    double p = -8.8967913924505741e-22;                 // -1/22!
+    p = fma(p, s, 4.1103176233121648e-19);              //  1/20!
+    p = fma(p, s, -1.5619206968586225e-16);             // -1/18!
+    p = fma(p, s, 4.7794773323873853e-14);              //  1/16!
+    p = fma(p, s, -1.1470745597729725e-11);             // -1/14!
+    p = fma(p, s, 2.0876756987868100e-09);              //  1/12!
+    p = fma(p, s, -2.7557319223985888e-07);             // -1/10!
+    p = fma(p, s, 2.4801587301587302e-05);              //  1/8!
+    p = fma(p, s, -1.3888888888888889e-03);             // -1/6!
+    p = fma(p, s, 4.1666666666666664e-02);              //  1/4!
+    p = fma(p, s, -0.5);
+    return fma(p, s, 1.0);
+}
+
+// K = rint(2m) by sine_phase's magic-number add, r = m - K/2 exact with |r| <= 1/4, x = 2 pi r to an ulp (2 fl(pi) and its tail),
+// both polynomials on [-pi/2, pi/2], an odd K flips both signs.  Absolute error of either < 3e-16.  A NaN m gives NaNs.
+__device__ __forceinline__ void cycle_sincos(double m, double& sn, double& cs) {
+    const double u = fma(m, 2.0, kRoundMagic);
+    const double k = u - kRoundMagic;
+    const double r = fma(k, -0.5, m);
+    const double x = fma(r, kTwoPiHi, r * kTwoPiLo);
+    const int flip = (int)(((unsigned)__double2loint(u) & 1u) << 31);
+    const double s = sin_poly(x), c = cos_poly(x);
+    sn = __hiloint2double(__double2hiint(s) ^ flip, __double2loint(s));
+    cs = __hiloint2double(__double2hiint(c) ^ flip, __double2loint(c));
+}
+
 template <int KIND, typename OUT> __device__ __forceinline__ OUT osc_wave(double t) {
     if (KIND == SIG_OSC_SINE) {
         if (sizeof(OUT) == 4) return (OUT)osc_sine_f32(t);

@@ -28,6 +28,20 @@ __device__ __forceinline__ void stage(float* tab, const float* table, int T, int
     for (int w = threadIdx.x; w < W; w += THREADS) tab[w * S + T] = table[w];
 }
 
+// The same staging for a table that is read one entry at a time (the additive oscillator's (H, W) amplitudes, osc_bank.hip): column
+// stride S >= T given by the caller, no guard entry -- entry (i, w) at tab[w * S + i], S * W floats in all.
+template <int THREADS>
+__device__ __forceinline__ void stage_columns(float* tab, const float* table, int T, int W, int S)
+{
+    const int di = THREADS / W, dw = THREADS - di * W;
+    int si = (int)threadIdx.x / W, sw = (int)threadIdx.x - si * W;
+    for (int k = threadIdx.x; k < T * W; k += THREADS) {
+        tab[sw * S + si] = table[k];
+        si += di; sw += dw;
+        if (sw >= W) { sw -= W; ++si; }
+    }
+}
+
 // the column a `select` value picks: clip(floor(select), 0, W - 1), NaN -> 0
 __device__ __forceinline__ int column(double select, int W)
 {

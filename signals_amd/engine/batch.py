@@ -215,13 +215,18 @@ class _Batch:
         return self._osc_launch(node, 'osc_bank_pm', _native.osc_bank_pm, (hertz, phase, index, x), hist, rows)
 
     def _sched_table(self, node, channels, hist, rows):
-        """a wavetable oscillator: one sig_osc_bank_table launch, per-block hertz / phase / select rows when one is modulated"""
+        """a wavetable oscillator: one sig_osc_bank_table launch, per-block hertz / phase / select rows when one is modulated.  An
+        additive one (ext.Additive): one sig_osc_bank_additive launch, the same rows, the table read as a spectrum"""
         hertz, phase, select = (self._control(p, p.name) for p in (node.hertz, node.phase, node.select))
         table = node.resident_table()
+        if isinstance(node, ext.Additive):
+            label, entry, kind = 'osc_bank_additive', _native.osc_bank_additive, f'Additive{table.shape[0]}'
+        else:
+            label, entry, kind = 'osc_bank_table', _native.osc_bank_table, 'Table'
 
         def bank(kind, position, rate, hertz, phase, select, out, **kw):
-            return _native.osc_bank_table(position, rate, hertz, phase, select, table, out, **kw)
-        return self._osc_launch(node, 'osc_bank_table', bank, (hertz, phase, select), hist, rows, kind='Table')
+            return entry(position, rate, hertz, phase, select, table, out, **kw)
+        return self._osc_launch(node, label, bank, (hertz, phase, select), hist, rows, kind=kind)
 
     def _sched_unison(self, node, channels, hist, rows):
         """a unison oscillator: one sig_osc_bank_unison launch (sig_osc_bank_blep for a band-limited one, ext.BlepOsc), per-block
