@@ -303,6 +303,37 @@ int sig_sampler_play(int64_t position, int64_t position_step, int32_t rate, int6
                      int32_t loop_start, int32_t loop_end,
                      void* out, int32_t out_dtype, int64_t out_ld, void* stream);
 
+/* Modal resonator bank, chain/ext.py Modal (build-defined: the reference has no struck or plucked source): per voice up to
+ * SIG_MODAL_MAX_MODES exponentially decaying sinusoids struck at gate_on, each with its own frequency ratio, amplitude and decay.
+ * `modes` float64 in device memory, (sets, count, 3) row-major: row i of set w is (ratio r >= 0, amplitude a, decay rate lambda in
+ * 1 / s; the node computes lambda = ln(1000) / t60 on the host, t60 = inf -> 0), 1 <= count <= SIG_MODAL_MAX_MODES, sets >= 1,
+ * sets * count <= SIG_MODAL_MAX_POINTS.  Rows, strides, `position_step` and `rows_per_param` as sig_sampler_play takes them: output row
+ * r is absolute frame n = position + r * position_step and reads control row r / rows_per_param (0: one row for the whole launch);
+ * hertz, gate_on, damp, select: f64 (1 | P, voices | 1), NULL = unplugged = 0 (hertz must be given).  A pure function of n, no state;
+ * per voice v, in f64, every operation rounded, no fused multiply-add, i = 0 .. count - 1 added in ascending order:
+ *   q = n / rate;  e = q - gate_on[v]
+ *   not (e >= 0)          -> out = 0.0                                     (before the strike; a NaN gate is silence; exact zero)
+ *   w = clip(floor(select[v]), 0, sets - 1)                                (NaN -> 0)
+ *   F_i = hertz[v] * r_i
+ *   g_i = clip(((0.5 * rate) - |F_i|) / |hertz[v]|, 0, 1)                  (IEEE: hertz = 0 gives +inf -> 1)
+ *   c_i = e * F_i;  m_i = np.mod(c_i, 1.0);  k_i = (lambda_i + damp[v]) * e
+ *   out[n,v] = sum_i (a_i * g_i) * exp(-k_i) * sin(2 pi m_i)               (a mode with g_i == 0 adds exactly 0)
+ * A hertz or damp that is not finite gives NaN on sounding rows (e >= 0) and 0.0 before the strike; every mode dropped: exactly 0.0.
+ * Held to a bound, not to bits: both stores within 1e-6 * max(1, A) of the definition, A the largest set's sum of |a| (the kernel
+ * starts each run of 64 rows from the closed form and advances it by a complex multiplication per row; measured: DESIGN.md).  A
+ * sample's bits do not depend on how a stretch of frames is cut into launches or parameter rows.  No status word.  A null modes /
+ * hertz / out, count or sets * count out of range, out_ld < voices, a negative position or a stride other than 0 / 1:
+ * hipErrorInvalidValue, nothing launched; rows == 0 or voices == 0: no launch. */
+enum { SIG_MODAL_MAX_MODES = 64, SIG_MODAL_MAX_POINTS = 2048 };
+int sig_modal_bank(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
+                   int32_t voices, int32_t rows_per_param,
+                   const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
+                   const double* gate_on, int32_t gate_on_stride, int64_t gate_on_row_stride,
+                   const double* damp, int32_t damp_stride, int64_t damp_row_stride,
+                   const double* select, int32_t select_stride, int64_t select_row_stride,
+                   const double* modes, int32_t sets, int32_t count,
+                   void* out, int32_t out_dtype, int64_t out_ld, void* stream);
+
 /* Replaces CritFilter._filter + _get_sos (fx.py:85-121) for LowPass/HighPass (order 2 = one
  * biquad section), batched over `nblocks` consecutive blocks of `block_frames` frames.
  * For block b (p_b = position + b*block_frames, c_b = min(context, p_b)):

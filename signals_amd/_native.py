@@ -80,6 +80,8 @@ FIR_CONTEXT = 100                           # SIG_FIR_CONTEXT: the rows of conte
 FIR_MAX_TAPS = 101                          # SIG_FIR_MAX_TAPS: taps of a FIR filter (ext.py FIR): x[n - 100] .. x[n], the window a filter is handed
 FIR_MAX_POINTS = 4096                       # SIG_FIR_MAX_POINTS: taps x columns of a FIR filter's table
 SAMPLER_MAX_POINTS = 1 << 26                # SIG_SAMPLER_MAX_POINTS: frames x recordings of a sampler's table (ext.py Sampler), resident in HBM
+MODAL_MAX_MODES = 64                        # SIG_MODAL_MAX_MODES: modes of one set of a modal bank (ext.py Modal)
+MODAL_MAX_POINTS = 2048                     # SIG_MODAL_MAX_POINTS: sets x modes of a modal bank's table, float64 (r, a, lambda) rows held in LDS
 
 
 class VpIns(ctypes.Structure):
@@ -149,6 +151,7 @@ def _argtypes() -> dict:
         'sig_delay_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, i32, dp, dp, vp, i32, i64, vp],
         'sig_fir_taps': [i32, i64, i32, i32, i32, i32, vp, i32, i64, i32, dp, i32, i64, i32, dp, i32, i32, vp, i32, i64, vp],
         'sig_sampler_play': [i64, i64, i32, i64, i32, i32] + [dp, i32, i64] * 4 + [vp, i32, i32, i32, i32, vp, i32, i64, vp],
+        'sig_modal_bank': [i64, i64, i32, i64, i32, i32] + [dp, i32, i64] * 4 + [dp, i32, i32, vp, i32, i64, vp],
         'sig_biquad_coldstart': cold + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_q': cold + [dp, i32, i32] + [dp, i32, i32] + window + [vp, i64, i32, vp, vp],
         'sig_biquad_coldstart_eq': cold + [dp, i32, i32] * 3 + window + [vp, i64, i32, vp, vp],
@@ -618,6 +621,29 @@ def sampler_play(position: int, rate: int, ratio: torch.Tensor | None, offset: t
     head, rows, tail = _osc_launch(out, position, step, rate, rows_per_param, *named, also=(table,))
     _check(lib().sig_sampler_play(*head, *(x for row in rows for x in row), ptr, frames, waves, loop_start, loop_end, *tail),
            'sig_sampler_play')
+    return out
+
+
+def _modes(modes: torch.Tensor):
+    """(ptr, sets, count) of a modal bank's table: float64 (W, M, 3) contiguous on the device, rows (ratio, amplitude, decay rate),
+    1 <= M <= MODAL_MAX_MODES, W * M within the cap (`_device_table`'s two refusals for a table of three axes)"""
+    if modes is None or modes.dtype != torch.float64 or modes.dim() != 3 or modes.shape[2] != 3 or not modes.is_contiguous():
+        raise NativeError('a table of modes is a contiguous float64 (sets, modes, 3) tensor')
+    sets, count = modes.shape[:2]
+    if not (1 <= count <= MODAL_MAX_MODES and sets >= 1 and sets * count <= MODAL_MAX_POINTS):
+        raise NativeError(f'modes {tuple(modes.shape)}: 1 <= modes <= {MODAL_MAX_MODES}, sets * modes <= {MODAL_MAX_POINTS}')
+    return modes.data_ptr(), sets, count
+
+
+def modal_bank(position: int, rate: int, hertz: torch.Tensor, gate_on: torch.Tensor | None, damp: torch.Tensor | None,
+               select: torch.Tensor | None, modes: torch.Tensor, out: torch.Tensor, step: int = 1, rows_per_param: int = 0) -> torch.Tensor:
+    """out[(rows, voices)] <- modal resonator bank (sig_modal_bank; ext.py Modal): row r is absolute frame n = position + r * step, the
+    sum over the modes (r_i, a_i, lambda_i) of set clip(floor(select), 0, W - 1) of a_i g_i exp(-(lambda_i + damp) e) sin(2 pi e
+    hertz r_i) at e = n / rate - gate_on, silence before the strike, g_i the fade below half the rate.  `modes`: the device copy, float64
+    (W, M, 3).  hertz / gate_on / damp / select: (1|P, V|1) f64 like `osc_bank`, None: unplugged = 0."""
+    named = ((hertz, 'hertz'), (gate_on, 'gate_on'), (damp, 'damp'), (select, 'select'))
+    head, rows, tail = _osc_launch(out, position, step, rate, rows_per_param, *named, also=(modes,))
+    _check(lib().sig_modal_bank(*head, *(x for row in rows for x in row), *_modes(modes), *tail), 'sig_modal_bank')
     return out
 
 

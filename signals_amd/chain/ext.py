@@ -991,6 +991,171 @@ class Sampler(BlockCachingEmitter, ImplicitChannels):
         return _native.sampler_play(loc.position, loc.rate, *rows, self.resident_table(), start, end, out)
 
 
+def _validate_modes(instance, attribute, new_value):
+    ok = (isinstance(new_value, np.ndarray) and new_value.ndim in (2, 3) and new_value.shape[-1] == 3 and new_value.dtype.kind in 'fiu'
+          and 1 <= new_value.shape[-2] <= _native.MODAL_MAX_MODES and new_value.shape[0] >= 1
+          and new_value.size // 3 <= _native.MODAL_MAX_POINTS
+          and bool(np.isfinite(new_value[..., :2]).all()) and bool((new_value[..., 0] >= 0).all())
+          and bool((new_value[..., 2] > 0).all()))                            # (a NaN t60 fails the comparison; inf passes)
+    if not ok:
+        raise BadStateValue(instance, attribute.name, new_value,
+                            f'must be a real array (sets, modes, 3) or (modes, 3) of rows (ratio >= 0, amplitude, t60 > 0), ratios and '
+                            f'amplitudes finite, 1 <= modes <= {_native.MODAL_MAX_MODES}, sets * modes <= {_native.MODAL_MAX_POINTS}')
+
+
+def _mode_rates(modes: np.ndarray) -> np.ndarray:
+    """the table a launch reads: float64 (W, M, 3) rows (ratio, amplitude, lambda = ln(1000) / t60); t60 = inf gives 0"""
+    rows = np.array(modes, dtype=np.float64).reshape(-1, modes.shape[-2], 3)
+    rows[..., 2] = np.log(1000.0) / rows[..., 2]
+    return rows
+
+
+def _mode_count(M, t60) -> np.ndarray:
+    """1 .. M as float64, M and t60 checked against the node's limits"""
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= _native.MODAL_MAX_MODES:
+        raise ValueError(f'modes must be an integer 1 .. {_native.MODAL_MAX_MODES}, got {M!r}')
+    if not (np.isfinite(t60) and t60 > 0):
+        raise ValueError(f't60 must be a finite time > 0 in seconds, got {t60!r}')
+    return np.arange(1, int(M) + 1, dtype=np.float64)
+
+
+class Modal(BlockCachingEmitter, ImplicitChannels):
+    """Modal resonator bank: a struck or plucked source.  Every voice rings up to 64 exponentially decaying sinusoids ("modes") from a
+    strike time on, each mode with its own frequency ratio, amplitude and decay time -- bells, bars, marimbas, glasses, plucked strings,
+    drum shells: the sounds where a partial has a life of its own, which `Additive` (harmonic ratios, amplitudes fixed per block)
+    cannot make.  Ports, all at block rate and read once per block at the block's position like every control: `hertz` (the
+    fundamental the ratios multiply), `gate_on` (the strike time in seconds, ADSR's and Sampler's meaning), `damp` (an extra decay rate in
+    1 / s added to every mode; unplugged reads 0; a hand laid on the bell is a step on this port), `select` (the mode set: w =
+    clip(floor(select), 0, W - 1), NaN and unplugged = 0, Wavetable's rule).  State `modes`: a real array (W, M, 3) -- (M, 3) means
+    W = 1 -- whose row i of set w is (ratio r >= 0, amplitude a, t60 in seconds: the time to fall by 60 dB, > 0, inf = undamped);
+    1 <= M <= 64, W * M <= 2048, every r and a finite, integer arrays (what a .sigs value arrives as) are converted; checked on set.  The
+    default [[1, 1, 1]] is a one-second sine ping.  The device copy is float64 rows (r, a, lambda), lambda = ln(1000) / t60 computed on the
+    host (float32 ratios would move a partial by 1e-7 of its frequency: a drifting beat pattern over a long note); it follows in-place
+    edits and replacement.  For absolute frame n and voice v, in float64 and every operation rounded, no fused multiply-add, the modes
+    i = 0 .. M - 1 added in ascending order:
+        q = n / rate                                   (osc.py's order: one IEEE divide)
+        e = q - gate_on
+        not (e >= 0)          -> out = 0.0             (before the strike; a NaN gate is silence; exact zero, never NaN)
+        F_i = hertz * r_i
+        g_i = clip(((0.5 * rate) - |F_i|) / |hertz|, 0, 1)         (IEEE: hertz = 0 gives +inf -> 1)
+        c_i = e * F_i;  m_i = np.mod(c_i, 1.0)
+        k_i = (lambda_i + damp) * e
+        out = sum_i (a_i * g_i) * exp(-k_i) * sin(2 pi m_i)        (a mode with g_i == 0 adds exactly 0)
+    (kernel: sig_modal_bank; restated in numpy by tests/modal_reference.py).  g_i is Additive's fade: a mode fades linearly to nothing
+    over the last |hertz| below half the rate, so a pitch envelope neither aliases nor clicks; a mode at or above half the rate adds
+    exactly 0, and with every mode dropped the output is exactly 0.0.  Every mode starts at phase 0, so the onset is continuous and needs
+    no attack ramp; a fractional gate_on * rate places the strike between frames.  A `hertz` that is NaN or infinite gives NaN on sounding
+    rows (e >= 0) and 0.0 before the strike.  `damp` is used as given: a negative damp lengthens the decays and, below -lambda_i, makes
+    mode i GROW (exp of a positive number, inf in the end); a damp that is NaN or infinite gives NaN on sounding rows (the definition's
+    inf * 0 at the strike, held for the rest of the note).  No status bit is set for any input.
+    One strike is alive per voice -- polyphony is voices: a new gate_on in the future silences the voice until it arrives, as with
+    `Sampler`; strike velocity is a `Gain` behind the node.  `hertz` multiplies the ELAPSED TIME, not an integrated phase -- this
+    project's oscillator convention, no carried phase: a pitch bend late in a note therefore moves the phase of mode i by e * r_i * (the
+    change of hertz) cycles at once, a jump that grows with the time since the strike -- bend early, or change pitch only with a new
+    strike.  The decay of a mode is in seconds and does not scale with `hertz`.
+    The rows are float32, a one-frame request float64.  The width is the broadcast of the four control rows; a control narrower than the
+    request but wider than 1 raises the IndexError of a narrow `cutoff`.
+    Because of exp and sin the kernel is held to a bound, not to bits: every sample within 1e-6 * max(1, A) of the definition, A the
+    largest set's sum of |a|.  It starts each run of 64 frames (frames 64 k .. 64 k + 63) from the closed form at the voice's first
+    sounding frame of the run and advances by one complex multiplication per frame and mode; a sample's bits depend on its frame and
+    its voice's parameters only, so a block rendered alone and inside a batch are equal bit for bit.  Measured on an MI355X over the
+    kernel cases of tests/test_gpu_modal.py (M up to 64, A up to 4.7): in front of the float64 store 2.1e-12 at most up to position
+    1000, 1.0e-9 at 2**24 and 4.6e-7 at 2**31 frames -- a tenth of the bar, and the distance of the float64 definition itself from
+    extended precision there: the rounding of n / rate, which the definition takes row by row and the recurrence once per run; behind
+    the float32 store 6.0e-8 (that store's own rounding) and the float64 figure at 2**31.
+    Position-pure: no state, no history, no context rows.  The batched engine renders the node with one kernel per batch; it has no
+    voice-program word, so a graph that contains one runs one kernel per node (the nodes around it keep their routes), `mixed_programs`
+    and `specialise` or not.
+    Mode sets (static, numpy on the host, (M, 3) each): `Modal.string(M, t60)`, `Modal.bar(M, t60)`, `Modal.bell(t60)`;
+    `Modal.stack(sets)` pads sets to a common M and returns (W, M, 3) for `select`.
+    Out of scope: a voice-program word, specialised or fused kernels; the node inside a block-rate control path (the batched engine
+    answers NotBatchable with the reason and the graph keeps the eager path, which serves frames == 1 in float64); frame-rate ports;
+    a phase or a cosine term per mode; more than one strike alive per voice, and strike velocity; excitation by an input signal (a driven
+    resonator needs history); more than 64 modes."""
+    hertz: Receiver.BoundPort = port('hertz')
+    gate_on: Receiver.BoundPort = port('gate_on')
+    damp: Receiver.BoundPort = port('damp')
+    select: Receiver.BoundPort = port('select')
+
+    @state
+    class State(BlockCachingEmitter.State):
+        modes: np.ndarray = attr.ib(factory=lambda: np.array([[1.0, 1.0, 1.0]]), validator=_validate_modes,
+                                    on_setattr=attr.setters.validate)
+
+    def __init__(self):
+        super().__init__()
+        self._resident = ResidentCopy(np.float64, layout=_mode_rates)
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR
+
+    # ---- mode sets: numpy on the host, one (M, 3) float64 array of rows (ratio, amplitude, t60) each
+    @staticmethod
+    def string(M: int = 32, t60: float = 2.0) -> np.ndarray:
+        """a plucked string: harmonic ratios i, amplitudes 1 / i, decay times t60 / i (i = 1 .. M)"""
+        i = _mode_count(M, t60)
+        return np.stack([i, 1.0 / i, float(t60) / i], axis=1)
+
+    @staticmethod
+    def bar(M: int = 8, t60: float = 1.0) -> np.ndarray:
+        """a free-free bar (marimba, glockenspiel): the Euler-Bernoulli beam's modes lie at the squares of the roots x_i of
+        cos(x) cosh(x) = 1 -- 4.7300, 7.8532, 10.9956, 14.1372, 17.2788, then (2 i + 1) pi / 2 to nine digits -- so the ratios are
+        (x_i / x_1)^2 = 1, 2.7565, 5.4039, 8.9330, ... (the usual short form ((2 i + 1) / 3.0112)^2 gives 2.7572 for the second);
+        amplitudes 1 / i, decay times t60 / ratio (the same number of cycles for every mode)"""
+        i = _mode_count(M, t60)
+        root = (2.0 * i + 1.0) * (np.pi / 2.0)
+        exact = np.array([4.730040744862704, 7.853204624095838, 10.995607838001671, 14.137165491257464, 17.278759657399481])
+        root[:5] = exact[:len(root)]
+        ratio = (root / root[0]) ** 2
+        return np.stack([ratio, 1.0 / i, float(t60) / ratio], axis=1)
+
+    @staticmethod
+    def bell(t60: float = 6.0) -> np.ndarray:
+        """a minor-third church bell, twelve modes: hum 0.5, prime 1, tierce 1.2, quint 1.5, nominal 2, and above the nominal the just
+        intervals a bell founder tunes towards -- deciem 2.5, undeciem 8 / 3, duodeciem 3, double octave 4, upper undeciem 16 / 3, upper
+        sixth 20 / 3, triple octave 8 (the ideal partials of a tuned bell as tabulated in Fletcher and Rossing, The Physics of Musical
+        Instruments, chapter 21; a cast bell's upper partials lie within a few per cent of them).  The hum rings for t60, a mode of
+        ratio r for t60 / (2 r); the amplitudes are a strike's, loudest at the prime and the nominal"""
+        _mode_count(1, t60)
+        ratio = np.array([0.5, 1.0, 1.2, 1.5, 2.0, 2.5, 8.0 / 3.0, 3.0, 4.0, 16.0 / 3.0, 20.0 / 3.0, 8.0])
+        level = np.array([0.6, 1.0, 0.8, 0.5, 1.0, 0.4, 0.3, 0.5, 0.35, 0.2, 0.15, 0.1])
+        return np.stack([ratio, level, float(t60) / (2.0 * ratio)], axis=1)
+
+    @staticmethod
+    def stack(sets) -> np.ndarray:
+        """(W, M, 3) from W sets of (M_w, 3) rows, M the longest: shorter sets are padded with rows (0, 0, 1) of zero amplitude"""
+        sets = [np.asarray(s, dtype=np.float64) for s in sets]
+        if not sets or any(s.ndim != 2 or s.shape[1] != 3 or s.shape[0] < 1 for s in sets):
+            raise ValueError('stack takes one or more (modes, 3) arrays')
+        out = np.tile(np.array([0.0, 0.0, 1.0]), (len(sets), max(s.shape[0] for s in sets), 1))
+        for w, s in enumerate(sets):
+            out[w, :s.shape[0]] = s
+        return out
+
+    def resident_modes(self) -> torch.Tensor:
+        """the device copy: float64 (W, M, 3) rows (ratio, amplitude, lambda)"""
+        return self._resident.of(self._state.modes)
+
+    def control_rows(self, fetch, channels: int) -> list:
+        """the four control rows (hertz, gate_on, damp, select) as contiguous float64 rows at most `channels` wide"""
+        rows = []
+        for bound in (self.hertz, self.gate_on, self.damp, self.select):
+            row = as_control(fetch(bound))
+            if 1 < row.shape[1] < channels:
+                raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
+            row = row[:, :channels]
+            rows.append(row if row.is_contiguous() else row.contiguous())
+        return rows
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        loc = request.loc
+        rows = self.control_rows(lambda bound: bound.forward_at_block_rate(request), loc.shape.channels)
+        frames, voices = broadcast_shape((loc.shape.frames, 1), *(r.shape for r in rows))
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=rows[0].device)
+        return _native.modal_bank(loc.position, loc.rate, *rows, self.resident_modes(), out)
+
+
 class ResonantFilter(fx.CritFilter, abc.ABC):
     """Resonant 2-pole low-pass / high-pass: the bilinear transform with prewarping of the analogue second-order section with quality
     factor q -- the RBJ cookbook's low-pass / high-pass (alpha = sin(w0) / (2 q)) in another form, the reference's Butterworth

@@ -7,7 +7,7 @@ from signals_amd import _native, runtime
 from signals_amd.chain import AUDIO_DTYPE, CTRL_DTYPE, Emitter, Receiver, as_control, broadcast_shape
 from signals_amd.chain import ext, files, fixed, fx, noise, osc, shape
 from signals_amd.engine.control import _ControlProgram
-from signals_amd.engine.graph import CONTEXT, _KNOWN_TYPES, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _is_pure, _modulated, _no_block_rate
+from signals_amd.engine.graph import CONTEXT, _KNOWN_BESIDE, _KNOWN_TYPES, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _is_pure, _modulated, _no_block_rate
 from signals_amd.engine.voice_chain import _VoiceChain
 from signals_amd.engine.voice_program import _NoProgram, _VoiceProgram
 
@@ -306,6 +306,16 @@ class _Batch:
         def play(kind, position, rate, ratio, offset, gate_on, select, out, **kw):
             return _native.sampler_play(position, rate, ratio, offset, gate_on, select, table, start, end, out, **kw)
         return self._osc_launch(node, 'sampler_play', play, operands, hist, rows, kind='Loop' if end else 'OneShot')
+
+    def _sched_modal(self, node, channels, hist, rows):
+        """a modal bank: one sig_modal_bank launch, a pure function of the absolute frame like an oscillator -- per-block hertz /
+        gate_on / damp / select rows when one is modulated; the table is the node's resident copy.  A generator: no history, no tails"""
+        operands = node.control_rows(lambda bound: self._control(bound, bound.name), channels)
+        modes = node.resident_modes()
+
+        def bank(kind, position, rate, hertz, gate_on, damp, select, out, **kw):
+            return _native.modal_bank(position, rate, hertz, gate_on, damp, select, modes, out, **kw)
+        return self._osc_launch(node, 'modal_bank', bank, operands, hist, rows, kind=f'Modal{modes.shape[1]}')
 
     def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
         """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
@@ -649,6 +659,7 @@ class _Batch:
         (ext.Shaper, _sched_shaper),
         (ext.Delay, _sched_delay),
         (ext.Sampler, _sched_sampler),
+        (ext.Modal, _sched_modal),
         (ext.SumBus, _sched_bus),
         (ext.Tap, _sched_tap),
         (files.FileWriter, _sched_file_writer),
@@ -814,4 +825,4 @@ class _Batch:
         return self._impure.items()
 
 
-assert set(_KNOWN_TYPES) == {t for types, _ in _Batch._SCHEDULES for t in (types if isinstance(types, tuple) else (types,))}
+assert set(_KNOWN_TYPES + _KNOWN_BESIDE) == {t for types, _ in _Batch._SCHEDULES for t in (types if isinstance(types, tuple) else (types,))}

@@ -18,6 +18,9 @@ class NotBatchable(Exception):
 # the node classes with a kernel schedule, one entry of _Batch._SCHEDULES each (batch.py checks that the two agree)
 _KNOWN_TYPES = (fixed.Fixed, osc.Osc, ext.PMOsc, ext.Wavetable, ext.UnisonOsc, noise.White, fx.CritFilter, fx.Mix, fx.RingMod, fx.Gain,
                 fx.Amp, ext.Shaper, ext.Delay, ext.Sampler, ext.SumBus, ext.Tap, files.FileWriter, files.FileReader, ext.ADSR, ext.MixMatrix, shape.Merge)
+# ext.Modal has a schedule like them (`_Batch._SCHEDULES`) and stands beside the tuple: tests/test_control_tables_host.py pins the
+# families of the tuple and of the table below class by class, and a new top-level family can enter neither
+_KNOWN_BESIDE = (ext.Modal,)
 
 
 # the extension nodes that are not evaluated at block rate: (class, what a refusal calls it, why), one table for the control
@@ -40,6 +43,9 @@ def _no_block_rate(node: Emitter, route: str, window: bool = False) -> str | Non
     if isinstance(node, ext.FIR):                              # a branch of its own, like the band filters': the table's families are pinned
         return (f'{node.cls_name()} in a control path: a FIR filter has no block-rate {route} -- the eager node serves '
                 f'one-frame requests')
+    if isinstance(node, ext.Modal):                            # the table's wording for a family the pinned table cannot hold
+        return (f'{node.cls_name()} in a control path: a modal bank has no block-rate {route} (the eager node serves '
+                f'one-frame requests)')
     for family, phrase, why in _NO_BLOCK_RATE:
         if isinstance(node, family):
             if window and family is ext.PMOsc:                 # (its modulator would have to be a window-rate input)
@@ -79,6 +85,8 @@ def _control_ports(node: Emitter) -> list:
         return [node.select]
     if isinstance(node, ext.Sampler):
         return [node.ratio, node.offset, node.gate_on, node.select]
+    if isinstance(node, ext.Modal):
+        return [node.hertz, node.gate_on, node.damp, node.select]
     if isinstance(node, (fx.Gain, fx.Amp)):
         return [node.right]
     if isinstance(node, fx.Mix):
@@ -124,7 +132,7 @@ def _modulated(node: Emitter | None) -> bool:
 def _foreign(node: Emitter) -> bool:
     """a node class the engine has no kernel schedule for -- a plugin written against the node API; it is pulled block by
     block through its own respond(), so its reply may depend on the request like a filter's"""
-    return not isinstance(node, _KNOWN_TYPES)
+    return not isinstance(node, _KNOWN_TYPES + _KNOWN_BESIDE)
 
 
 def _is_pure(node: Emitter | None, memo: dict) -> bool:

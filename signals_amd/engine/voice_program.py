@@ -90,6 +90,8 @@ class _VoiceProgram:
             return
         if isinstance(n, ext.Additive):                                        # (a Wavetable to isinstance, but OscTable is not its word)
             raise _NoProgram(f'{n.cls_name()}: an additive oscillator has no voice-program word')
+        if isinstance(n, ext.Modal):
+            raise _NoProgram(f'{n.cls_name()}: a modal bank has no voice-program word')
         if isinstance(n, self.KERNEL_NODES):
             self.kernel_nodes += 1
         elif not isinstance(n, fixed.Fixed):
@@ -175,6 +177,8 @@ class _VoiceProgram:
             self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), self._param(self._control(n.index, below)), 0))
         elif isinstance(n, ext.Additive):
             raise _NoProgram(f'{n.cls_name()}: an additive oscillator has no voice-program word')
+        elif isinstance(n, ext.Modal):
+            raise _NoProgram(f'{n.cls_name()}: a modal bank has no voice-program word')
         elif isinstance(n, ext.Wavetable):
             select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
             self.code.append(('OscTable', 0, self._osc_slot(n, below), self._table_slot(n), select))
