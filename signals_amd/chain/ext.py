@@ -164,6 +164,47 @@ class PMTriangle(PMOsc):
         return 'Triangle'
 
 
+class BankEmitter(BlockCachingEmitter, ImplicitChannels, abc.ABC):
+    """A generator that is a pure function of the absolute frame and whose only inputs are block-rate rows: it states its launch
+    once (`bank`), for this eager path and for the batched engine's schedule (engine/batch.py: `_sched_bank`)."""
+
+    @classmethod
+    def flags(cls) -> SignalFlags:
+        return super().flags() | SignalFlags.GENERATOR
+
+    @abc.abstractmethod
+    def bank(self, fetch, channels: int) -> tuple:
+        """(label, kind, rows, call): the launch is named `label[kind]`; `rows` are the control rows, each port's block-rate reply
+        through `fetch`, read with a request `channels` wide; `call(position, rate, *rows, out, **kw)` is the `_native` entry with
+        what else it takes -- a table, the copies, the loop bounds -- bound in as the node's state holds it now"""
+        raise NotImplementedError
+
+    def _eval(self, request: Request) -> torch.Tensor:
+        loc = request.loc
+        _, _, rows, call = self.bank(lambda bound: bound.forward_at_block_rate(request), loc.shape.channels)
+        frames, voices = broadcast_shape((loc.shape.frames, 1), *(r.shape for r in rows))
+        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=rows[0].device)
+        return call(loc.position, loc.rate, *rows, out)
+
+
+def _bound(entry, *payload, head=()):
+    """`call` of a `bank`: the entry with `head` in front of the position and `payload` between the rows and `out`"""
+    return lambda position, rate, *rows_and_out, **kw: entry(*head, position, rate, *rows_and_out[:-1], *payload, rows_and_out[-1], **kw)
+
+
+def _request_rows(fetch, ports, channels: int) -> list:
+    """the block-rate replies of `ports` as contiguous float64 rows at most `channels` wide; a reply narrower than that but wider
+    than 1 is the IndexError of a narrow `cutoff` (Sampler, Modal)"""
+    rows = []
+    for bound in ports:
+        row = as_control(fetch(bound))
+        if 1 < row.shape[1] < channels:
+            raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
+        row = row[:, :channels]
+        rows.append(row if row.is_contiguous() else row.contiguous())
+    return rows
+
+
 def _validate_table(instance, attribute, new_value):
     ok = (isinstance(new_value, np.ndarray) and new_value.ndim == 2 and new_value.dtype.kind in 'fiu'
           and new_value.shape[0] >= 2 and new_value.shape[0] & (new_value.shape[0] - 1) == 0 and new_value.shape[1] >= 1
@@ -174,7 +215,7 @@ def _validate_table(instance, attribute, new_value):
                             f'{_native.TABLE_MAX_POINTS}')
 
 
-class Wavetable(BlockCachingEmitter, ImplicitChannels):
+class Wavetable(BankEmitter):
     """Wavetable oscillator: the state `table` holds W single-cycle waveforms of T points each as a (T, W) array (the
     reference's (frames, channels) orientation), read with linear interpolation at the oscillator phase of chain/osc.py.
     With tbl = float32(table) widened to float64, in float64 and every operation rounded:
@@ -202,21 +243,18 @@ class Wavetable(BlockCachingEmitter, ImplicitChannels):
         super().__init__()
         self._resident = ResidentCopy(np.float32)
 
-    @classmethod
-    def flags(cls) -> SignalFlags:
-        return super().flags() | SignalFlags.GENERATOR
-
     def resident_table(self) -> torch.Tensor:
         return self._resident.of(self._state.table)
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        phase = as_control(self.phase.forward_at_block_rate(request))
-        hertz = as_control(self.hertz.forward_at_block_rate(request))
-        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
-        loc = request.loc
-        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, select.shape)
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
-        return _native.osc_bank_table(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
+    def _entry(self, table: torch.Tensor) -> tuple:
+        """(label, kind, the `_native` entry) of the launch that reads `table`"""
+        return 'osc_bank_table', 'Table', _native.osc_bank_table
+
+    def bank(self, fetch, channels: int) -> tuple:
+        rows = [as_control(fetch(bound)) for bound in (self.hertz, self.phase, self.select)]   # (select unplugged: zeros((1, 1)) = column 0)
+        table = self.resident_table()
+        label, kind, entry = self._entry(table)
+        return label, kind, rows, _bound(entry, table)
 
 
 def _validate_spectra(instance, attribute, new_value):
@@ -315,14 +353,8 @@ class Additive(Wavetable):
         angle = np.mod(np.outer(i, h), float(T)) / float(T)                    # exact: i * h < 2**53
         return (np.sin(2.0 * np.pi * angle) @ a).reshape(-1, 1)
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        phase = as_control(self.phase.forward_at_block_rate(request))
-        hertz = as_control(self.hertz.forward_at_block_rate(request))
-        select = as_control(self.select.forward_at_block_rate(request))        # unplugged: zeros((1, 1)) = column 0
-        loc = request.loc
-        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, select.shape)
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
-        return _native.osc_bank_additive(loc.position, loc.rate, hertz, phase, select, self.resident_table(), out)
+    def _entry(self, table: torch.Tensor) -> tuple:
+        return 'osc_bank_additive', f'Additive{table.shape[0]}', _native.osc_bank_additive
 
 
 UNISON_DETUNE = (-0.11002313, -0.06288439, -0.01952356, 0.0, 0.01991221, 0.06216538, 0.10745242)
@@ -343,7 +375,7 @@ def _validate_copies(instance, attribute, new_value):
                             f'{_native.UNISON_MAX_COPIES}')
 
 
-class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
+class UnisonOsc(BankEmitter, abc.ABC):
     """Unison oscillator: U detuned copies of one waveform of chain/osc.py per voice, summed and divided by U -- the supersaw, detuned
     square leads, thickened sines.  The state `copies` is a (U, 2) array, 1 <= U <= 16: column 0 the relative detune d[u] of copy u,
     column 1 its phase offset p[u] in cycles.  Ports, all block-rate: hertz, phase, spread (dimensionless; unplugged means zeros,
@@ -374,10 +406,6 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
         copies: np.ndarray = attr.ib(factory=_default_copies, validator=_validate_copies, on_setattr=attr.setters.validate)
 
     @classmethod
-    def flags(cls) -> SignalFlags:
-        return super().flags() | SignalFlags.GENERATOR
-
-    @classmethod
     @abc.abstractmethod
     def kind(cls) -> str:
         """kernel selector: 'Sine' | 'Square' | 'Sawtooth' | 'Triangle'"""
@@ -393,15 +421,15 @@ class UnisonOsc(BlockCachingEmitter, ImplicitChannels, abc.ABC):
         """the (U, 2) float64 array a launch takes by value, as the state holds it now"""
         return np.ascontiguousarray(self._state.copies, dtype=np.float64)
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        phase = as_control(self.phase.forward_at_block_rate(request))
-        hertz = as_control(self.hertz.forward_at_block_rate(request))
-        spread = as_control(self.spread.forward_at_block_rate(request))        # unplugged: zeros((1, 1)), every copy at `hertz`
-        loc = request.loc
-        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, spread.shape)
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
-        bank = _native.osc_bank_blep if self.bandlimited() else _native.osc_bank_unison
-        return bank(self.kind(), loc.position, loc.rate, hertz, phase, spread, self.host_copies(), out)
+    def _entry(self) -> tuple:
+        """(the name of the `_native` entry, which is the launch's label too; the ports whose rows it takes, in its order)"""
+        return 'osc_bank_blep' if self.bandlimited() else 'osc_bank_unison', (self.hertz, self.phase, self.spread)
+
+    def bank(self, fetch, channels: int) -> tuple:
+        label, ports = self._entry()
+        rows = [as_control(fetch(bound)) for bound in ports]                   # (unplugged: zeros((1, 1)) -- every copy at `hertz`, R = 1)
+        kind = self.kind()
+        return label, kind, rows, _bound(getattr(_native, label), self.host_copies(), head=(kind,))
 
 
 class UnisonSine(UnisonOsc):
@@ -532,15 +560,8 @@ class SyncOsc(BlepOsc, abc.ABC):
     with an equaliser biquad (`EqFilter`) in one voice program (such a graph stays one kernel per node)."""
     ratio: Receiver.BoundPort = port('ratio')
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        phase = as_control(self.phase.forward_at_block_rate(request))
-        hertz = as_control(self.hertz.forward_at_block_rate(request))
-        spread = as_control(self.spread.forward_at_block_rate(request))
-        ratio = as_control(self.ratio.forward_at_block_rate(request))          # unplugged: zeros((1, 1)), R = 1
-        loc = request.loc
-        frames, voices = broadcast_shape((loc.shape.frames, 1), hertz.shape, phase.shape, spread.shape, ratio.shape)
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=hertz.device)
-        return _native.osc_bank_sync(self.kind(), loc.position, loc.rate, hertz, phase, spread, ratio, self.host_copies(), out)
+    def _entry(self) -> tuple:
+        return 'osc_bank_sync', (self.hertz, self.phase, self.spread, self.ratio)
 
 
 class SyncSawtooth(SyncOsc):
@@ -889,7 +910,7 @@ def _validate_loop(instance, attribute, new_value):
         raise BadStateValue(instance, attribute.name, new_value, f'a loop needs loop_start < loop_end, got {start} and {end}')
 
 
-class Sampler(BlockCachingEmitter, ImplicitChannels):
+class Sampler(BankEmitter):
     """Sample playback: the state `table` holds W recordings of T frames each as a (T, W) array (the reference's (frames, channels)
     orientation), recorded at the graph's rate; every voice plays one of them from a trigger time, at its own speed and start, with
     linear interpolation -- a drum hit per voice, a multisample transposed per voice, a looped pad.  Ports, all at block rate and read
@@ -945,7 +966,7 @@ class Sampler(BlockCachingEmitter, ImplicitChannels):
 
     @classmethod
     def flags(cls) -> SignalFlags:
-        return super().flags() | SignalFlags.GENERATOR | SignalFlags.EPOCH
+        return super().flags() | SignalFlags.EPOCH
 
     @staticmethod
     def table_from_wav(path) -> np.ndarray:
@@ -973,22 +994,12 @@ class Sampler(BlockCachingEmitter, ImplicitChannels):
 
     def control_rows(self, fetch, channels: int) -> list:
         """the four control rows (ratio, offset, gate_on, select) as contiguous float64 rows at most `channels` wide"""
-        rows = []
-        for bound in (self.ratio, self.offset, self.gate_on, self.select):
-            row = as_control(fetch(bound))
-            if 1 < row.shape[1] < channels:
-                raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
-            row = row[:, :channels]
-            rows.append(row if row.is_contiguous() else row.contiguous())
-        return rows
+        return _request_rows(fetch, (self.ratio, self.offset, self.gate_on, self.select), channels)
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        loc = request.loc
-        rows = self.control_rows(lambda bound: bound.forward_at_block_rate(request), loc.shape.channels)
-        frames, voices = broadcast_shape((loc.shape.frames, 1), *(r.shape for r in rows))
-        start, end = self.loop()
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=rows[0].device)
-        return _native.sampler_play(loc.position, loc.rate, *rows, self.resident_table(), start, end, out)
+    def bank(self, fetch, channels: int) -> tuple:
+        rows = self.control_rows(fetch, channels)
+        table, (start, end) = self.resident_table(), self.loop()               # (the loop checked against the table as it is now)
+        return 'sampler_play', 'Loop' if end else 'OneShot', rows, _bound(_native.sampler_play, table, start, end)
 
 
 def _validate_modes(instance, attribute, new_value):
@@ -1019,7 +1030,7 @@ def _mode_count(M, t60) -> np.ndarray:
     return np.arange(1, int(M) + 1, dtype=np.float64)
 
 
-class Modal(BlockCachingEmitter, ImplicitChannels):
+class Modal(BankEmitter):
     """Modal resonator bank: a struck or plucked source.  Every voice rings up to 64 exponentially decaying sinusoids ("modes") from a
     strike time on, each mode with its own frequency ratio, amplitude and decay time -- bells, bars, marimbas, glasses, plucked strings,
     drum shells: the sounds where a partial has a life of its own, which `Additive` (harmonic ratios, amplitudes fixed per block)
@@ -1086,10 +1097,6 @@ class Modal(BlockCachingEmitter, ImplicitChannels):
         super().__init__()
         self._resident = ResidentCopy(np.float64, layout=_mode_rates)
 
-    @classmethod
-    def flags(cls) -> SignalFlags:
-        return super().flags() | SignalFlags.GENERATOR
-
     # ---- mode sets: numpy on the host, one (M, 3) float64 array of rows (ratio, amplitude, t60) each
     @staticmethod
     def string(M: int = 32, t60: float = 2.0) -> np.ndarray:
@@ -1139,21 +1146,11 @@ class Modal(BlockCachingEmitter, ImplicitChannels):
 
     def control_rows(self, fetch, channels: int) -> list:
         """the four control rows (hertz, gate_on, damp, select) as contiguous float64 rows at most `channels` wide"""
-        rows = []
-        for bound in (self.hertz, self.gate_on, self.damp, self.select):
-            row = as_control(fetch(bound))
-            if 1 < row.shape[1] < channels:
-                raise IndexError(f'index {row.shape[1]} is out of bounds for axis 1 with size {row.shape[1]}')
-            row = row[:, :channels]
-            rows.append(row if row.is_contiguous() else row.contiguous())
-        return rows
+        return _request_rows(fetch, (self.hertz, self.gate_on, self.damp, self.select), channels)
 
-    def _eval(self, request: Request) -> torch.Tensor:
-        loc = request.loc
-        rows = self.control_rows(lambda bound: bound.forward_at_block_rate(request), loc.shape.channels)
-        frames, voices = broadcast_shape((loc.shape.frames, 1), *(r.shape for r in rows))
-        out = torch.empty((frames, voices), dtype=result_dtype(frames), device=rows[0].device)
-        return _native.modal_bank(loc.position, loc.rate, *rows, self.resident_modes(), out)
+    def bank(self, fetch, channels: int) -> tuple:
+        rows, modes = self.control_rows(fetch, channels), self.resident_modes()
+        return 'modal_bank', f'Modal{modes.shape[1]}', rows, _bound(_native.modal_bank, modes)
 
 
 class ResonantFilter(fx.CritFilter, abc.ABC):

@@ -32,12 +32,15 @@
 // Roofline: 4 B written per voice-sample against 7 M float64 operations: float64-VALU-bound from the first mode on.
 #include <type_traits>
 
-#include "sig_common.h"
 #include "sig_modal.h"
 #include "sig_osc.h"
+#include "sig_param_rows.h"
 #include "sig_table.h"
 
 namespace {
+
+using sig_rows::row_value;
+using Rows = sig_rows::Row;                                       // one control row: (1 | P, V | 1) f64, NULL = unplugged = 0
 
 constexpr int kRun = sig_modal::kRun;
 constexpr int kWavesPerWg = 4;
@@ -47,9 +50,6 @@ static_assert(kRun == SIG_WAVE, "lane l holds the quotient of a run's row l");
 static_assert(sig_modal::kMaxModes == SIG_MODAL_MAX_MODES && sig_modal::kMaxPoints == SIG_MODAL_MAX_POINTS,
               "sig_modal.h and signals_amd.h disagree");
 
-// One control row: (1 | P, V | 1) f64, NULL = unplugged = 0
-struct Rows { const double* p; int stride; int64_t row_stride; };
-
 struct ModalArgs {
     int64_t position, step; double rate; int64_t rows; int voices; int64_t rpp;   // rpp == 0: one control row for the launch
     Rows hertz, gate, damp, select;
@@ -57,11 +57,6 @@ struct ModalArgs {
     int64_t base, first_run, runs;                                 // position / step; the first run's index; runs the launch touches
     int per_wave;                                                  // runs a wave renders
 };
-
-__device__ __forceinline__ double row_value(const Rows& r, int64_t prow, int v, bool live)
-{
-    return (r.p && live) ? r.p[prow * r.row_stride + (int64_t)v * r.stride] : 0.0;
-}
 
 template <typename OUT>
 __global__ __launch_bounds__(64 * kWavesPerWg) void modal_bank_kernel(ModalArgs a, OUT* __restrict__ out, int64_t ld, int voice_tiles)
@@ -184,8 +179,6 @@ int launch_modal(ModalArgs& a, OUT* out, int64_t ld, hipStream_t s)
     return sig_launch_status();
 }
 
-bool rows_ok(int32_t stride, int64_t row_stride) { return (stride == 0 || stride == 1) && row_stride >= 0; }
-
 }  // namespace
 
 extern "C" int sig_modal_bank(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -197,11 +190,11 @@ extern "C" int sig_modal_bank(int64_t position, int64_t position_step, int32_t r
                               const double* modes, int32_t sets, int32_t count,
                               void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(sig_rows::head_ok(position, position_step, rate, rows, voices, rows_per_param));
     SIG_CHECK_ARG(modes != nullptr && hertz != nullptr && out != nullptr && out_ld >= voices);
     SIG_CHECK_ARG(sig_modal::shape_ok(sets, count));
-    SIG_CHECK_ARG(rows_ok(hertz_stride, hertz_row_stride) && rows_ok(gate_on_stride, gate_on_row_stride) &&
-                  rows_ok(damp_stride, damp_row_stride) && rows_ok(select_stride, select_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(hertz_stride, hertz_row_stride) && sig_rows::strides_ok(gate_on_stride, gate_on_row_stride) &&
+                  sig_rows::strides_ok(damp_stride, damp_row_stride) && sig_rows::strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
     ModalArgs a{};
@@ -215,6 +208,5 @@ extern "C" int sig_modal_bank(int64_t position, int64_t position_step, int32_t r
     a.first_run = a.base / kRun;
     a.runs = (a.base + rows - 1) / kRun - a.first_run + 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return launch_modal(a, static_cast<float*>(out), out_ld, s);
-    return launch_modal(a, static_cast<double*>(out), out_ld, s);
+    return sig_rows::dispatch_out(out, out_dtype, [&](auto* o) { return launch_modal(a, o, out_ld, s); });
 }

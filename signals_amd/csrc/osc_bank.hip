@@ -11,11 +11,13 @@
 #include <type_traits>
 
 #include "sig_osc.h"
+#include "sig_param_rows.h"
 #include "sig_table.h"
 
 namespace {
 
 using sig_osc::osc_wave;
+using sig_rows::dispatch_out;
 
 constexpr int kRowsPerWave = 16;
 constexpr int kWavesPerWg = 4;
@@ -680,15 +682,6 @@ int dispatch_kind(int kind, F&& f)
     return (int)hipErrorInvalidValue;
 }
 
-// f(out as float* | double*), hipErrorInvalidValue without a call for any other `out_dtype`
-template <typename F>
-int dispatch_out(void* out, int32_t out_dtype, F&& f)
-{
-    if (out_dtype == SIG_F32) return f(static_cast<float*>(out));
-    if (out_dtype == SIG_F64) return f(static_cast<double*>(out));
-    return (int)hipErrorInvalidValue;
-}
-
 int run_osc(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t ld, void* stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -771,17 +764,14 @@ int run_copies(int kind, const OscArgs& a, void* out, int32_t out_dtype, int64_t
     });
 }
 
-// One parameter's strides as every entry takes them
-bool row_strides_ok(int32_t stride, int64_t row_stride) { return (stride == 0 || stride == 1) && row_stride >= 0; }
-
 // The arguments common to the entries, checked, as OscArgs
 int osc_args(OscArgs& a, int64_t position, int64_t position_step, int32_t rate, int64_t rows, int32_t voices, int32_t rows_per_param,
              const double* hertz, int32_t hertz_stride, int64_t hertz_row_stride,
              const double* phase, int32_t phase_stride, int64_t phase_row_stride, const void* out, int64_t out_ld)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(sig_rows::head_ok(position, position_step, rate, rows, voices, rows_per_param));
     SIG_CHECK_ARG(hertz != nullptr && out != nullptr && out_ld >= voices);
-    SIG_CHECK_ARG(row_strides_ok(hertz_stride, hertz_row_stride) && row_strides_ok(phase_stride, phase_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(hertz_stride, hertz_row_stride) && sig_rows::strides_ok(phase_stride, phase_row_stride));
     a = OscArgs{position, position_step, (double)rate, rows, voices, hertz, hertz_stride, hertz_row_stride,
                 phase, phase_stride, phase_row_stride, rows_per_param};
     return 0;
@@ -791,7 +781,7 @@ int osc_args(OscArgs& a, int64_t position, int64_t position_step, int32_t rate, 
 int uni_args(UniArgs& un, const double* spread, int32_t spread_stride, int64_t spread_row_stride,
              int32_t copies, const double* detune, const double* offsets)
 {
-    SIG_CHECK_ARG(row_strides_ok(spread_stride, spread_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(spread_stride, spread_row_stride));
     SIG_CHECK_ARG(copies >= 1 && copies <= SIG_UNISON_MAX_COPIES && detune != nullptr && offsets != nullptr);
     un = UniArgs{spread, spread_stride, spread_row_stride, copies, {0.0}, {0.0}};
     for (int u = 0; u < copies; ++u) { un.detune[u] = detune[u]; un.offset[u] = offsets[u]; }
@@ -817,7 +807,7 @@ extern "C" int sig_osc_bank_sync(int kind, int64_t position, int64_t position_st
     SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
                      phase, phase_stride, phase_row_stride, out, out_ld));
     SIG_TRY(uni_args(un, spread, spread_stride, spread_row_stride, copies, detune, offsets));
-    SIG_CHECK_ARG(row_strides_ok(ratio_stride, ratio_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(ratio_stride, ratio_row_stride));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
     const SyncArgs sy{ratio, ratio_stride, ratio_row_stride};
@@ -885,7 +875,7 @@ extern "C" int sig_osc_bank_table(int64_t position, int64_t position_step, int32
     OscArgs a;
     SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
                      phase, phase_stride, phase_row_stride, out, out_ld));
-    SIG_CHECK_ARG(row_strides_ok(select_stride, select_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(table != nullptr && table_points >= 2 && (table_points & (table_points - 1)) == 0 && table_waves >= 1 &&
                   (int64_t)table_points * table_waves <= SIG_TABLE_MAX_POINTS);
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
@@ -905,7 +895,7 @@ extern "C" int sig_osc_bank_additive(int64_t position, int64_t position_step, in
     OscArgs a;
     SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
                      phase, phase_stride, phase_row_stride, out, out_ld));
-    SIG_CHECK_ARG(row_strides_ok(select_stride, select_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(table != nullptr && table_partials >= 1 && table_partials <= SIG_ADDITIVE_MAX_PARTIALS && table_waves >= 1 &&
                   (int64_t)table_partials * table_waves <= SIG_TABLE_MAX_POINTS);
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
@@ -927,7 +917,7 @@ extern "C" int sig_osc_bank_pm(int kind, int64_t position, int64_t position_step
     OscArgs a;
     SIG_TRY(osc_args(a, position, position_step, rate, rows, voices, rows_per_param, hertz, hertz_stride, hertz_row_stride,
                      phase, phase_stride, phase_row_stride, out, out_ld));
-    SIG_CHECK_ARG(row_strides_ok(index_stride, index_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(index_stride, index_row_stride));
     SIG_CHECK_ARG(mod == nullptr || ((mod_dtype == SIG_F32 || mod_dtype == SIG_F64) && (mod_stride == 0 || mod_stride == 1) &&
                                      (mod_ld == 0 || mod_ld >= (mod_stride ? voices : 1))));
     if (rows == 0 || voices == 0) return 0;

@@ -16,10 +16,13 @@
 // Roofline: 4 B written + 4 * max(ratio, 1/32) B of table lines read per voice-sample (f32 out).
 #include <type_traits>
 
-#include "sig_common.h"
+#include "sig_param_rows.h"
 #include "sig_sampler.h"
 
 namespace {
+
+using sig_rows::row_value;
+using Rows = sig_rows::Row;                                       // one control row: (1 | P, V | 1) f64, NULL = unplugged = 0
 
 constexpr int kRowsPerWave = 32;
 constexpr int kWavesPerWg = 4;
@@ -29,20 +32,12 @@ static_assert(kRowsPerWave % kRowsInFlight == 0 && kRowsPerWave <= 64, "the row 
 
 static_assert(sig_sampler::kMaxPoints == SIG_SAMPLER_MAX_POINTS, "sig_sampler.h and signals_amd.h disagree");
 
-// One control row: (1 | P, V | 1) f64, NULL = unplugged = 0
-struct Rows { const double* p; int stride; int64_t row_stride; };
-
 struct SamplerArgs {
     int64_t position, step; double rate; int64_t rows; int voices; int64_t rpp;   // rpp == 0: one control row for the launch
     Rows ratio, offset, gate, select;
     const float* table; int W;                                     // (W, T) row-major: recording w at table + w * T
     sig_sampler::Shape sh;
 };
-
-__device__ __forceinline__ double row_value(const Rows& r, int64_t prow, int v, bool live)
-{
-    return (r.p && live) ? r.p[prow * r.row_stride + (int64_t)v * r.stride] : 0.0;
-}
 
 template <bool LOOP, typename OUT>
 __global__ __launch_bounds__(64 * kWavesPerWg) void sampler_play_kernel(SamplerArgs a, OUT* __restrict__ out, int64_t ld, int voice_tiles)
@@ -112,8 +107,6 @@ int launch_sampler(const SamplerArgs& a, OUT* out, int64_t ld, hipStream_t s)
     return sig_launch_status();
 }
 
-bool rows_ok(int32_t stride, int64_t row_stride) { return (stride == 0 || stride == 1) && row_stride >= 0; }
-
 }  // namespace
 
 extern "C" int sig_sampler_play(int64_t position, int64_t position_step, int32_t rate, int64_t rows,
@@ -126,11 +119,11 @@ extern "C" int sig_sampler_play(int64_t position, int64_t position_step, int32_t
                                 int32_t loop_start, int32_t loop_end,
                                 void* out, int32_t out_dtype, int64_t out_ld, void* stream)
 {
-    SIG_CHECK_ARG(rows >= 0 && voices >= 0 && rate > 0 && position >= 0 && position_step >= 1 && rows_per_param >= 0);
+    SIG_CHECK_ARG(sig_rows::head_ok(position, position_step, rate, rows, voices, rows_per_param));
     SIG_CHECK_ARG(table != nullptr && out != nullptr && out_ld >= voices);
     SIG_CHECK_ARG(sig_sampler::shape_ok(table_frames, table_waves, loop_start, loop_end));
-    SIG_CHECK_ARG(rows_ok(ratio_stride, ratio_row_stride) && rows_ok(offset_stride, offset_row_stride) &&
-                  rows_ok(gate_on_stride, gate_on_row_stride) && rows_ok(select_stride, select_row_stride));
+    SIG_CHECK_ARG(sig_rows::strides_ok(ratio_stride, ratio_row_stride) && sig_rows::strides_ok(offset_stride, offset_row_stride) &&
+                  sig_rows::strides_ok(gate_on_stride, gate_on_row_stride) && sig_rows::strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(out_dtype == SIG_F32 || out_dtype == SIG_F64);
     if (rows == 0 || voices == 0) return 0;
     SamplerArgs a{};
@@ -142,6 +135,5 @@ extern "C" int sig_sampler_play(int64_t position, int64_t position_step, int32_t
     a.table = table; a.W = table_waves;
     a.sh = sig_sampler::shape(table_frames, loop_start, loop_end);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_dtype == SIG_F32) return launch_sampler(a, static_cast<float*>(out), out_ld, s);
-    return launch_sampler(a, static_cast<double*>(out), out_ld, s);
+    return sig_rows::dispatch_out(out, out_dtype, [&](auto* o) { return launch_sampler(a, o, out_ld, s); });
 }

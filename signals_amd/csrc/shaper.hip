@@ -11,6 +11,7 @@
 // loads are in flight per wave.  The gather is one paired LDS read per sample at a data-dependent address: neighbouring voices
 // with nearby sample values in one column fall on nearby banks, equal values on one address (a broadcast, no conflict).
 // Roofline: 4 B read + 4 B written per voice-sample (f32 in and out).
+#include "sig_param_rows.h"
 #include "sig_table.h"
 
 namespace {
@@ -138,10 +139,9 @@ int launch_shaper(ShaperArgs a, OUT* out, int64_t ld, hipStream_t stream)
 }
 
 template <typename IN>
-int dispatch_out(const ShaperArgs& a, void* out, int32_t out_dtype, int64_t out_ld, hipStream_t s)
+int run_shaper(const ShaperArgs& a, void* out, int32_t out_dtype, int64_t out_ld, hipStream_t s)
 {
-    if (out_dtype == SIG_F32) return launch_shaper<IN, float>(a, static_cast<float*>(out), out_ld, s);
-    return launch_shaper<IN, double>(a, static_cast<double*>(out), out_ld, s);
+    return sig_rows::dispatch_out(out, out_dtype, [&](auto* o) { return launch_shaper<IN>(a, o, out_ld, s); });
 }
 
 }  // namespace
@@ -156,13 +156,13 @@ extern "C" int sig_shaper_table(int64_t rows, int32_t voices,
     SIG_CHECK_ARG(in != nullptr && out != nullptr && out_ld >= voices);
     SIG_CHECK_ARG((in_dtype == SIG_F32 || in_dtype == SIG_F64) && (out_dtype == SIG_F32 || out_dtype == SIG_F64));
     SIG_CHECK_ARG((in_stride == 0 || in_stride == 1) && (in_ld == 0 || in_ld >= (in_stride ? voices : 1)));
-    SIG_CHECK_ARG((select_stride == 0 || select_stride == 1) && select_row_stride >= 0);
+    SIG_CHECK_ARG(sig_rows::strides_ok(select_stride, select_row_stride));
     SIG_CHECK_ARG(table != nullptr && table_points >= 2 && table_waves >= 1 &&
                   (int64_t)table_points * table_waves <= SIG_TABLE_MAX_POINTS);
     if (rows == 0 || voices == 0) return 0;
     const ShaperArgs a{rows, voices, in, in_ld, in_stride, select, select_stride, select_row_stride, rows_per_select,
                        table, table_points, table_waves, 1};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (in_dtype == SIG_F32) return dispatch_out<float>(a, out, out_dtype, out_ld, s);
-    return dispatch_out<double>(a, out, out_dtype, out_ld, s);
+    if (in_dtype == SIG_F32) return run_shaper<float>(a, out, out_dtype, out_ld, s);
+    return run_shaper<double>(a, out, out_dtype, out_ld, s);
 }

@@ -1,13 +1,15 @@
 """The per-node scheduler: one render call's buffers, one schedule per node family."""
 from __future__ import annotations
 
+import functools
+
 import torch
 
 from signals_amd import _native, runtime
 from signals_amd.chain import AUDIO_DTYPE, CTRL_DTYPE, Emitter, Receiver, as_control, broadcast_shape
 from signals_amd.chain import ext, files, fixed, fx, noise, osc, shape
 from signals_amd.engine.control import _ControlProgram
-from signals_amd.engine.graph import CONTEXT, _KNOWN_BESIDE, _KNOWN_TYPES, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _is_pure, _modulated, _no_block_rate
+from signals_amd.engine.graph import CONTEXT, _KNOWN_TYPES, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _family, _is_pure, _modulated, _no_block_rate
 from signals_amd.engine.voice_chain import _VoiceChain
 from signals_amd.engine.voice_program import _NoProgram, _VoiceProgram
 
@@ -138,11 +140,12 @@ class _Batch:
         self._need[key] = hist
         if not node.get_state().enabled and not isinstance(node, (ext.Tap, files.FileWriter)):
             return
-        if isinstance(node, (fx.CritFilter, ext.Delay)):
+        family = _family(node)
+        if family.window:
             hist = min(CONTEXT, self.pos)
         elif _modulated(node):
             hist = 0                                              # own history comes from the tail / a fresh block
-        own_width = isinstance(node, (ext.SumBus, shape.Merge))   # these ask with their ports' own widths
+        own_width = family.own_width                              # (a bus, a Merge: they ask with their ports' own widths)
         for port in _audio_ports(node):
             self._require(port.sig, port.channels if own_width else channels, hist)
 
@@ -206,43 +209,22 @@ class _Batch:
 
     def _sched_osc(self, node, channels, hist, rows):
         hertz, phase = self._control(node.hertz, 'hertz'), self._control(node.phase, 'phase')
-        return self._osc_launch(node, 'osc_bank', _native.osc_bank, (hertz, phase), hist, rows)
+        kind = node.kind()
+        return self._osc_launch(node, 'osc_bank', kind, functools.partial(_native.osc_bank, kind), (hertz, phase), hist, rows)
 
     def _sched_pm(self, node, channels, hist, rows):
         """a phase-modulation oscillator: one sig_osc_bank_pm launch over the modulator's rows"""
         hertz, phase, index = (self._control(p, p.name) for p in (node.hertz, node.phase, node.index))
         x = self._operand(node.mod, channels, 0 if _modulated(node) else hist)   # a modulated node's history comes from its tail
-        return self._osc_launch(node, 'osc_bank_pm', _native.osc_bank_pm, (hertz, phase, index, x), hist, rows)
+        kind = node.kind()
+        return self._osc_launch(node, 'osc_bank_pm', kind, functools.partial(_native.osc_bank_pm, kind), (hertz, phase, index, x), hist, rows)
 
-    def _sched_table(self, node, channels, hist, rows):
-        """a wavetable oscillator: one sig_osc_bank_table launch, per-block hertz / phase / select rows when one is modulated.  An
-        additive one (ext.Additive): one sig_osc_bank_additive launch, the same rows, the table read as a spectrum"""
-        hertz, phase, select = (self._control(p, p.name) for p in (node.hertz, node.phase, node.select))
-        table = node.resident_table()
-        if isinstance(node, ext.Additive):
-            label, entry, kind = 'osc_bank_additive', _native.osc_bank_additive, f'Additive{table.shape[0]}'
-        else:
-            label, entry, kind = 'osc_bank_table', _native.osc_bank_table, 'Table'
-
-        def bank(kind, position, rate, hertz, phase, select, out, **kw):
-            return entry(position, rate, hertz, phase, select, table, out, **kw)
-        return self._osc_launch(node, label, bank, (hertz, phase, select), hist, rows, kind=kind)
-
-    def _sched_unison(self, node, channels, hist, rows):
-        """a unison oscillator: one sig_osc_bank_unison launch (sig_osc_bank_blep for a band-limited one, ext.BlepOsc), per-block
-        hertz / phase / spread rows when one is modulated; the copies go with the launch by value, as the node's state holds them now.
-        A hard-sync one (ext.SyncOsc): one sig_osc_bank_sync launch, the ratio rows with the other three"""
-        hertz, phase, spread = (self._control(p, p.name) for p in (node.hertz, node.phase, node.spread))
-        copies = node.host_copies()
-        if isinstance(node, ext.SyncOsc):
-            label, operands = 'osc_bank_sync', (hertz, phase, spread, self._control(node.ratio, 'ratio'))
-        else:
-            label, operands = 'osc_bank_blep' if node.bandlimited() else 'osc_bank_unison', (hertz, phase, spread)
-        entry = getattr(_native, label)
-
-        def bank(kind, position, rate, *rows_and_out, **kw):       # the copies go between the parameter rows and `out`
-            return entry(kind, position, rate, *rows_and_out[:-1], copies, rows_and_out[-1], **kw)
-        return self._osc_launch(node, label, bank, operands, hist, rows)
+    def _sched_bank(self, node, channels, hist, rows):
+        """a generator that is a pure function of the absolute frame and of block-rate rows (ext.Wavetable, ext.Additive, ext.UnisonOsc,
+        ext.SyncOsc, ext.Sampler, ext.Modal): one launch of the entry the node states (`bank`), per-block rows when a port is
+        modulated; tables, copies and loop bounds go with the call as the node's state holds them now.  No history, no tails"""
+        label, kind, operands, call = node.bank(lambda bound: self._control(bound, bound.name), channels)
+        return self._osc_launch(node, label, kind, call, operands, hist, rows)
 
     def _sched_shaper(self, node, channels, hist, rows):
         """a waveshaper: one sig_shaper_table launch over its input's rows (history rows included when a filter reads it), scheduled
@@ -297,40 +279,21 @@ class _Batch:
             o._launch(f'delay_taps[{taps.shape[0]},uncached-input]',
                       lambda: _native.delay_taps(self.rate, p, N, 1, window, c, row, taps, out), units=N * out.shape[1])
 
-    def _sched_sampler(self, node, channels, hist, rows):
-        """a sampler: one sig_sampler_play launch, a pure function of the absolute frame like an oscillator -- per-block ratio / offset /
-        gate_on / select rows when one is modulated; the table is the node's resident copy, the loop checked against it now"""
-        operands = node.control_rows(lambda bound: self._control(bound, bound.name), channels)
-        table, (start, end) = node.resident_table(), node.loop()
-
-        def play(kind, position, rate, ratio, offset, gate_on, select, out, **kw):
-            return _native.sampler_play(position, rate, ratio, offset, gate_on, select, table, start, end, out, **kw)
-        return self._osc_launch(node, 'sampler_play', play, operands, hist, rows, kind='Loop' if end else 'OneShot')
-
-    def _sched_modal(self, node, channels, hist, rows):
-        """a modal bank: one sig_modal_bank launch, a pure function of the absolute frame like an oscillator -- per-block hertz /
-        gate_on / damp / select rows when one is modulated; the table is the node's resident copy.  A generator: no history, no tails"""
-        operands = node.control_rows(lambda bound: self._control(bound, bound.name), channels)
-        modes = node.resident_modes()
-
-        def bank(kind, position, rate, hertz, gate_on, damp, select, out, **kw):
-            return _native.modal_bank(position, rate, hertz, gate_on, damp, select, modes, out, **kw)
-        return self._osc_launch(node, 'modal_bank', bank, operands, hist, rows, kind=f'Modal{modes.shape[1]}')
-
-    def _osc_launch(self, node, name, bank, operands, hist, rows, kind=None):
-        """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast"""
-        o, kind = self.owner, kind or node.kind()
+    def _osc_launch(self, node, name, kind, call, operands, hist, rows):
+        """one launch of an oscillator bank over the batch's rows, as wide as its operands broadcast: `call(position, rate, *operands,
+        out, **kw)`"""
+        o = self.owner
         _, voices = broadcast_shape((1, 1), *((1, t.shape[1]) for t in operands))
         result = torch.empty((rows, voices), dtype=AUDIO_DTYPE, device=runtime.device())
         if _modulated(node):
             # the parameters are re-read every block: K parameter rows, N output rows each
             main = result[hist:]
             o._launch(f'{name}[{kind},per-block]',
-                      lambda: bank(kind, self.pos, self.rate, *operands, main, rows_per_param=self.N), units=main.shape[0] * voices)
+                      lambda: call(self.pos, self.rate, *operands, main, rows_per_param=self.N), units=main.shape[0] * voices)
             self._own_history(node, voices, hist, result)
         else:
             start = self.pos - hist
-            o._launch(f'{name}[{kind}]', lambda: bank(kind, start, self.rate, *operands, result), units=rows * voices)
+            o._launch(f'{name}[{kind}]', lambda: call(start, self.rate, *operands, result), units=rows * voices)
         return result
 
     def _sched_noise(self, node, channels, hist, rows):
@@ -651,15 +614,12 @@ class _Batch:
         (fixed.Fixed, _sched_fixed),
         (osc.Osc, _sched_osc),
         (ext.PMOsc, _sched_pm),
-        (ext.Wavetable, _sched_table),
-        (ext.UnisonOsc, _sched_unison),
+        ((ext.Wavetable, ext.UnisonOsc, ext.Sampler, ext.Modal), _sched_bank),
         (noise.White, _sched_noise),
         (fx.CritFilter, _sched_filter),
         ((fx.Mix, fx.RingMod, fx.Gain, fx.Amp), _sched_elementwise),
         (ext.Shaper, _sched_shaper),
         (ext.Delay, _sched_delay),
-        (ext.Sampler, _sched_sampler),
-        (ext.Modal, _sched_modal),
         (ext.SumBus, _sched_bus),
         (ext.Tap, _sched_tap),
         (files.FileWriter, _sched_file_writer),
@@ -825,4 +785,4 @@ class _Batch:
         return self._impure.items()
 
 
-assert set(_KNOWN_TYPES + _KNOWN_BESIDE) == {t for types, _ in _Batch._SCHEDULES for t in (types if isinstance(types, tuple) else (types,))}
+assert set(_KNOWN_TYPES) == {t for types, _ in _Batch._SCHEDULES for t in (types if isinstance(types, tuple) else (types,))}

@@ -7,7 +7,7 @@ from signals_amd import _native
 from signals_amd.chain import Emitter, as_control
 from signals_amd.chain import ext, fixed, fx, noise, osc
 from signals_amd.engine.control import _ProgramRows
-from signals_amd.engine.graph import CONTEXT, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _is_pure, _modulated
+from signals_amd.engine.graph import CONTEXT, NotBatchable, _audio_ports, _ctl_const, _ctl_unplugged, _is_pure, _modulated, _no_voice_program
 
 
 class _NoProgram(Exception):
@@ -88,10 +88,8 @@ class _VoiceProgram:
         self.uses[n] = self.uses.get(n, 0) + 1
         if self.uses[n] > 1:
             return
-        if isinstance(n, ext.Additive):                                        # (a Wavetable to isinstance, but OscTable is not its word)
-            raise _NoProgram(f'{n.cls_name()}: an additive oscillator has no voice-program word')
-        if isinstance(n, ext.Modal):
-            raise _NoProgram(f'{n.cls_name()}: a modal bank has no voice-program word')
+        if _no_voice_program(n) is not None:                                   # (every node `_emit` reaches has passed here first)
+            raise _NoProgram(_no_voice_program(n))
         if isinstance(n, self.KERNEL_NODES):
             self.kernel_nodes += 1
         elif not isinstance(n, fixed.Fixed):
@@ -175,10 +173,6 @@ class _VoiceProgram:
         elif isinstance(n, ext.PMOsc):
             depth = self._emit(n.mod.sig, below)                               # the modulator's sample: in the accumulator
             self.code.append(('OscPM', _native.OSC_KINDS[n.kind()], self._osc_slot(n, below), self._param(self._control(n.index, below)), 0))
-        elif isinstance(n, ext.Additive):
-            raise _NoProgram(f'{n.cls_name()}: an additive oscillator has no voice-program word')
-        elif isinstance(n, ext.Modal):
-            raise _NoProgram(f'{n.cls_name()}: a modal bank has no voice-program word')
         elif isinstance(n, ext.Wavetable):
             select = -1 if _ctl_unplugged(n.select) else self._param(self._control(n.select, below))
             self.code.append(('OscTable', 0, self._osc_slot(n, below), self._table_slot(n), select))

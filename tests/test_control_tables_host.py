@@ -1,6 +1,6 @@
 """Two tables that used to be kept by hand in two places each, checked without a GPU: the files a specialised image is keyed by
 (`specialise._sources`: the quoted-include closure of the two kernels) and the extension nodes that are refused in a control path
-(`graph._NO_BLOCK_RATE`, worded by `_ControlProgram._emit` and `_Batch._control_node`)."""
+(the `no_block_rate` column of `graph._FAMILIES`, worded by `_ControlProgram._emit` and `_Batch._control_node`)."""
 import pathlib
 import re
 import shutil
@@ -45,11 +45,12 @@ def test_a_byte_of_an_included_header_changes_the_digest(tmp_path, monkeypatch):
     assert specialise._source_digest() != before
 
 
-# what each refusal said before there was one table: class -> (what it is called, why)
-EAGER = 'the eager node serves one-frame requests'
-REFUSED = {ext.PMOsc: ('a phase-modulation oscillator', 'its modulator is a frame-rate input'), ext.Wavetable: ('a wavetable oscillator', EAGER),
+# what each refusal said before there was one table: class -> (what it is called, how the sentence ends)
+EAGER = ' (the eager node serves one-frame requests)'
+REFUSED = {ext.PMOsc: ('a phase-modulation oscillator', ' (its modulator is a frame-rate input)'), ext.Wavetable: ('a wavetable oscillator', EAGER),
            ext.UnisonOsc: ('a unison oscillator', EAGER), ext.Shaper: ('a waveshaper', EAGER), ext.ResonantFilter: ('a resonant filter', EAGER),
-           ext.Ladder: ('a ladder filter', EAGER), ext.Delay: ('a delay line', EAGER), ext.Sampler: ('a sampler', EAGER)}
+           ext.Ladder: ('a ladder filter', EAGER), ext.Delay: ('a delay line', EAGER), ext.Sampler: ('a sampler', EAGER),
+           ext.FIR: ('a FIR filter', ' -- the eager node serves one-frame requests'), ext.Modal: ('a modal bank', EAGER)}
 
 
 def node_of(cls):
@@ -63,20 +64,22 @@ def emit(node, window=False):
 
 
 def test_both_sites_word_every_entry_as_before():
-    assert {family for family, _, _ in graph._NO_BLOCK_RATE} == set(REFUSED)
+    refusing = {row.cls: row.no_block_rate for row in graph._FAMILIES if row.no_block_rate is not None}
+    assert {cls for cls in refusing if not any(issubclass(cls, above) for above in refusing if above is not cls)} == set(REFUSED)
+    assert all(refusing[cls] == next(said for family, said in REFUSED.items() if issubclass(cls, family)) for cls in refusing)
     batch = _Batch(types.SimpleNamespace(rate=48000), 0, 256, 4, False)
-    for cls, (phrase, why) in REFUSED.items():
+    for cls, (phrase, tail) in REFUSED.items():
         name, node = cls.__name__, node_of(cls)
         with pytest.raises(NotBatchable) as e:
             emit(node)
-        assert str(e.value) == f'{name} in a control path: {phrase} has no block-rate program ({why})'
+        assert str(e.value) == f'{name} in a control path: {phrase} has no block-rate program{tail}'
         with pytest.raises(NotBatchable) as e:
             emit(node, window=True)
         assert str(e.value) == (f'{name} inside a control filter\'s input: {phrase} has no window-rate program' if cls is ext.PMOsc else
-                                f'{name} in a control path: {phrase} has no block-rate program ({why})')
+                                f'{name} in a control path: {phrase} has no block-rate program{tail}')
         with pytest.raises(NotBatchable) as e:
             batch._control_node(node, 'cutoff')
-        assert str(e.value) == f'cutoff: {name} in a control path: {phrase} has no block-rate schedule ({why})'
+        assert str(e.value) == f'cutoff: {name} in a control path: {phrase} has no block-rate schedule{tail}'
 
 
 def test_every_known_class_is_emitted_or_in_the_table():
@@ -90,7 +93,7 @@ def test_every_known_class_is_emitted_or_in_the_table():
         except NotBatchable as e:
             if str(e).startswith('no block-rate program for'):
                 generic.add(cls)
-            elif 'has no block-rate program (' in str(e):
+            elif ' has no block-rate program' in str(e):
                 tabled.add(cls)
             else:
                 branched.add(cls)                           # (a refusal of its own: the band filters')
